@@ -6,17 +6,22 @@ resident in HBM, produce the scalar loss -mean_{i>j} d(S_i,S_j) and dloss/dS.
 Workload (default) = BASELINE.json configs[2] "c3": C=1000 classes, n_dim=784, n_filters=16,
 float32, SecondMomentsSQFA (m=16), synthetic Gaussians of SURVEY.md 8(d).
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1: spawns one rank per GPU itself)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N > 1: spawns one rank per GPU itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 With N > 1 every rank holds the same S, evaluates the tile shard (bi+bj) % N == rank and the
 partial loss / flags / gradient are summed with one RCCL all-reduce per step ("strong" scaling:
 the problem is fixed, `value` is whole-job evaluations per second).
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (pair tile kernel; its duration is measured live with
+A plain run measures the headline only: it builds the input, runs the headline's own kernel for PREWARM_SECONDS
+("prewarm": the chip reaches its sustained clock), then the W warm-up and K timed steps.  --dump-outputs DIR writes
+what the last timed step returned (loss, non-finite counts [nan, inf], dL/dS) as DIR/<name>.npy in the run's dtype.
+With --full the c4 pair leg below takes the prewarm's place.
+
+Rank 0 prints ONE JSON line.  With --full it also carries: "roofline" (pair tile kernel; its duration is measured live with
 HIP events on the launch stream in a short pass right AFTER the timed region, which itself runs with profiling
 off), "cpu_baseline" (the oracle's torch-CPU port of the reference op sequence: ONE timed full-size evaluation on every
-core the process is entitled to, plus a one-thread figure on a bounded sample), "prewarm" (what ran before the headline's own warm-up steps), "c3_sqfa" (the same configuration with the
+core the process is entitled to, plus a one-thread figure on a bounded sample), "c3_sqfa" (the same configuration with the
 reference's default model, sqfa.model.SQFA: m = K+1 = 17, own roofline), "scaling_c4_pairs" (BASELINE config 4's
 pair stage, m=32, same sharding) and "scaling_c4_closure" (config 4 end to end at every N: class-sharded
 (C,2048,2048) statistics, projection + all-gather + pair shard + all-reduce + backward + gradient all-reduce
@@ -38,6 +43,7 @@ if ROOT not in sys.path:
 FP32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: f32 vector == f32 MFMA dense peak
 FP64_PEAK_TFLOPS = 78.6    # MI355X public specification (FP64 vector = half the FP32 vector rate); the guide's table has no f64 row
 HBM_PEAK_GBS = 8000.0
+PREWARM_SECONDS = 0.3      # plain run; the --full run's c4 pair leg (0.3-0.5 s) warms the chip for its headline instead
 PMC_FILE = "r4_pmc_c3.json"   # committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE summary the `traffic` fields quote
 
 WORKLOADS = {
@@ -473,6 +479,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: pair-kernel roofline, c4 pair and closure legs, c3_sqfa, "
+                         "closure (M2) and the CPU baseline; the --no-* options and --fit act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-closure", action="store_true", help="skip the secondary full-closure measurement (N=1)")
     ap.add_argument("--no-c4-pairs", action="store_true", help="skip the second (m=32) pair workload of the scaling curve")
@@ -481,6 +491,8 @@ def main():
     ap.add_argument("--fit", action="store_true", help="also time model.fit() (metric M3) inside the closure object")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -531,9 +543,11 @@ def main():
 
     graphs_used = []   # N > 1: whether each pair workload's launches were replayed from a captured graph
 
-    def time_pair_workload(S, scale, warmup, steps):
+    def time_pair_workload(S, scale, warmup, steps, profile=True, prewarm_seconds=0.0):
         """W untimed + K timed loss+grad evaluations of the pair workload S; returns
-        (seconds for the K steps [max over ranks], pair kernel ms per launch [max over ranks], last outputs)."""
+        (seconds for the K steps [max over ranks], pair kernel ms per launch [max over ranks; None without `profile`],
+        outputs of the last timed step, prewarm record or None).  `prewarm_seconds` > 0: before the warm-up, each rank
+        launches its own shard without collectives until that much wall time has passed."""
         P_ = S.shape[0] * (S.shape[0] - 1) // 2
         weight = -1.0 / P_
 
@@ -581,6 +595,19 @@ def main():
                 graph["g"] = None
             graphs_used.append(graph["g"] is not None)
             fence()
+        prewarm = None
+        if prewarm_seconds > 0:
+            local = launch_shard if world > 1 else step   # no collectives: each rank stops on its own clock
+            t_pre, launches = time.perf_counter(), 0
+            while time.perf_counter() - t_pre < prewarm_seconds:
+                for _ in range(10):
+                    local()
+                torch.cuda.synchronize()
+                launches += 10
+            prewarm = {"what": "the headline's own pair kernel runs for PREWARM_SECONDS BEFORE the --warmup steps, so the "
+                               "headline is measured at the chip's sustained clock, not on the ramp from idle",
+                       "launches": launches, "seconds": time.perf_counter() - t_pre}
+            fence()
         for _ in range(warmup):
             res = step()
         fence()
@@ -589,22 +616,26 @@ def main():
             res = step()
         fence()
         seconds = time.perf_counter() - t0
-        # kernel duration: a SEPARATE short pass with HIP events around the pair kernel on its launch stream
-        # (asynchronous records; plain launches: a graph replay does not repeat them), right after the timed
-        # region -- same inputs, same clock state
-        lib.sqfa_airm_profile(1)
-        for _ in range(max(5, min(30, steps))):
-            step(True)
-        fence()
-        lib.sqfa_airm_profile(0)
-        ms_total, launches = ctypes.c_double(0), ctypes.c_int(0)
-        lib.sqfa_airm_profile_read(ctypes.byref(ms_total), ctypes.byref(launches))
-        k_ms = ms_total.value / max(launches.value, 1)
+        res = tuple(t.clone() for t in res)   # N > 1: views into the fused buffer, which later launches overwrite
+        k_ms = None
+        if profile:
+            # kernel duration: a SEPARATE short pass with HIP events around the pair kernel on its launch stream
+            # (asynchronous records; plain launches: a graph replay does not repeat them), right after the timed
+            # region -- same inputs, same clock state
+            lib.sqfa_airm_profile(1)
+            for _ in range(max(5, min(30, steps))):
+                step(True)
+            fence()
+            lib.sqfa_airm_profile(0)
+            ms_total, launches = ctypes.c_double(0), ctypes.c_int(0)
+            lib.sqfa_airm_profile_read(ctypes.byref(ms_total), ctypes.byref(launches))
+            k_ms = ms_total.value / max(launches.value, 1)
         if world > 1:
-            both = torch.tensor([seconds, k_ms], dtype=torch.float64, device=device)
+            both = torch.tensor([seconds, k_ms or 0.0], dtype=torch.float64, device=device)
             dist.all_reduce(both, op=dist.ReduceOp.MAX)
-            seconds, k_ms = both.tolist()
-        return seconds, k_ms, res
+            seconds = both[0].item()
+            k_ms = both[1].item() if profile else None
+        return seconds, k_ms, res, prewarm
 
     # second pair workload for the scaling curve (measured FIRST: half a second of the heavier kernel also
     # brings the chip to its sustained clock before the headline's own warm-up): BASELINE config 4's pair stage
@@ -614,12 +645,12 @@ def main():
     c4_pairs = None
     prewarm = None
     S, scale = make_feature_scatters(C, D, K, model, device, dtype)   # both inputs first: no idle gap between the legs
-    if args.workload != "c4" and not args.no_c4_pairs and dtype == torch.float32:
+    if args.full and args.workload != "c4" and not args.no_c4_pairs and dtype == torch.float32:
         C4, D4, K4, model4 = WORKLOADS["c4"]
         S4, scale4 = make_feature_scatters(C4, D4, K4, model4, device, dtype)
         steps4, warm4 = max(5, min(40, args.steps)), max(2, min(10, args.warmup))
         t_pre = time.perf_counter()
-        sec4, kms4, (loss4, flags4, _g4) = time_pair_workload(S4, scale4, warm4, steps4)
+        sec4, kms4, (loss4, flags4, _g4), _ = time_pair_workload(S4, scale4, warm4, steps4)
         prewarm = {
             "what": "the scaling_c4_pairs leg (C=1000, m=32 pair kernel) runs BEFORE the headline's own --warmup steps, so "
                     "the headline is measured at the chip's sustained clock (what a fit sees), not on the ramp from idle",
@@ -636,16 +667,23 @@ def main():
 
     m = S.shape[1]
     P = C * (C - 1) // 2
-    elapsed, kernel_ms, (loss, flags, grad) = time_pair_workload(S, scale, args.warmup, args.steps)
+    elapsed, kernel_ms, (loss, flags, grad), own_prewarm = time_pair_workload(
+        S, scale, args.warmup, args.steps, profile=args.full, prewarm_seconds=0.0 if args.full else PREWARM_SECONDS)
+    prewarm = prewarm if args.full else own_prewarm
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("loss", loss), ("nonfinite", flags), ("grad", grad)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().to(dtype).cpu().numpy())
     assert flags.tolist() == [0, 0], f"non-finite distances: {flags.tolist()}"
 
     # the reference's DEFAULT model (sqfa.model.SQFA, README flow: Calvo-Oller embedding, m = K+1) on the same configuration,
     # same step, same sharding -- its own roofline next to the headline's
     c3_sqfa = None
-    if args.workload == "c3" and not args.no_c3_sqfa:
+    if args.full and args.workload == "c3" and not args.no_c3_sqfa:
         S17, scale17 = make_feature_scatters(C, D, K, "sqfa", device, dtype)
         steps17, warm17 = max(5, min(100, args.steps)), max(2, min(20, args.warmup))
-        sec17, kms17, (loss17, flags17, _g17) = time_pair_workload(S17, scale17, warm17, steps17)
+        sec17, kms17, (loss17, flags17, _g17), _ = time_pair_workload(S17, scale17, warm17, steps17)
         assert flags17.tolist() == [0, 0]
         m17 = S17.shape[1]
         fl17 = 8.0 * C * (C - 1) * m17 ** 3 / world
@@ -661,10 +699,10 @@ def main():
         }
         del S17, _g17
 
-    S_cpu = S.detach().cpu() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    S_cpu = S.detach().cpu() if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     # BASELINE config 4 end to end (class-sharded projection + pair shard + collectives), every rank takes part
     c4_closure = None
-    if not args.no_c4_closure and dtype == torch.float32:
+    if args.full and not args.no_c4_closure and dtype == torch.float32:
         del S, grad
         torch.cuda.empty_cache()
         c4_closure = c4_closure_leg(world, rank, device, shard, max(5, min(20, args.steps // 4)), lib, fence, dist)
@@ -672,12 +710,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         evals_per_s = args.steps / elapsed
-        flops_eval = 8.0 * C * (C - 1) * m ** 3          # 16 m^3 per unordered pair
-        flops_launch = flops_eval / world                # each rank's launch covers 1/world of the tiles
-        achieved_tf = flops_launch / (kernel_ms * 1e-3) / 1e12
-        peak_tf = FP32_PEAK_TFLOPS if dtype == torch.float32 else FP64_PEAK_TFLOPS
-        esz = 4 if dtype == torch.float32 else 8
-        bytes_eval = esz * (2 * C * m * m + 1)
         result = {
             "metric": "SPD pairwise-distance loss+grad evals/sec",
             "value": evals_per_s,
@@ -700,7 +732,15 @@ def main():
             "loss": loss.item(),
             "rccl_ranks": dist.get_world_size() if (world > 1 and dist.get_backend() == "nccl") else (1 if world == 1 else 0),
             "shard_launches_from_hip_graph": bool(graphs_used and all(graphs_used)),
-            "roofline": {
+        }
+        if args.full:
+            flops_eval = 8.0 * C * (C - 1) * m ** 3          # 16 m^3 per unordered pair
+            flops_launch = flops_eval / world                # each rank's launch covers 1/world of the tiles
+            achieved_tf = flops_launch / (kernel_ms * 1e-3) / 1e12
+            peak_tf = FP32_PEAK_TFLOPS if dtype == torch.float32 else FP64_PEAK_TFLOPS
+            esz = 4 if dtype == torch.float32 else 8
+            bytes_eval = esz * (2 * C * m * m + 1)
+            result["roofline"] = {
                 "bound": "valu",
                 "achieved": achieved_tf,
                 "peak": peak_tf,
@@ -716,8 +756,7 @@ def main():
                         "algorithmic flops = 16*m^3 per unordered pair (SURVEY.md 8d). Algorithmic HBM traffic is "
                         f"{bytes_eval / 1e6:.2f} MB per eval = {bytes_eval / (kernel_ms * 1e-3) / 1e9:.1f} GB/s, "
                         f"{bytes_eval / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS * 100:.3f}% of the 8 TB/s HBM roofline",
-            },
-        }
+            }
         result["prewarm"] = prewarm
         if c3_sqfa is not None:
             result["c3_sqfa"] = c3_sqfa
@@ -725,11 +764,11 @@ def main():
             result["scaling_c4_pairs"] = c4_pairs
         if c4_closure is not None:
             result["scaling_c4_closure"] = c4_closure
-        if not args.no_closure and world == 1 and dtype == torch.float32:
+        if args.full and not args.no_closure and world == 1 and dtype == torch.float32:
             result["closure"] = closure_benchmark(C, D, K, model, device, max(10, min(100, args.steps // 2)), lib, with_fit=args.fit)
             result["closure"]["roofline"]["traffic"] = pmc_traffic(result["closure"]["roofline"]["kernel"], args.workload, args.dtype)
             result["closure"]["roofline"]["traffic_unit"] = f"bytes per launch (profiles/{PMC_FILE})"
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(S_cpu, scale, C)
             result["speedup_vs_cpu_baseline"] = evals_per_s / result["cpu_baseline"]["value"]
         print(json.dumps(result))

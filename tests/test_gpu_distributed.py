@@ -298,7 +298,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SQFA_BENCH_REHEARSAL"] = "1"
     env["SQFA_BENCH_C4_CLASSES"] = "60"        # the c4 closure leg (D=2048, K=32) on 60 instead of 1000 classes
-    args = ["--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--workload", "c2"]
+    args = ["--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--workload", "c2"]
     two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, env=env,
                          capture_output=True, text=True, timeout=500)
     assert two.returncode == 0, two.stderr[-2000:]
@@ -321,3 +321,28 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     assert c1_["n_gpus"] == 1 and c1_["collectives_per_closure"] == 0
     assert c2_["value"] > 0 and c2_["projection"]["kernel_ms"] > 0 and 0 < c2_["projection"]["frac"] < 1
     assert abs(c2_["loss"] - c1_["loss"]) < 2e-5 * abs(c1_["loss"])
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py` times the headline only (no roofline or secondary legs) and --dump-outputs writes what
+    its last timed step returned: the loss of the line, no non-finite distances, a finite dL/dS of the input's shape."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--workload", "c2", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True,
+                         timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "evals/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["value"] > 0 and abs(r["ms_per_step"] * r["value"] - 1e3) < 1e-6 * 1e3
+    assert r["prewarm"]["launches"] > 0
+    assert not {"roofline", "closure", "cpu_baseline", "c3_sqfa", "scaling_c4_pairs", "scaling_c4_closure"} & set(r)
+    loss, nonfinite, grad = (np.load(os.path.join(tmp_path, n + ".npy")) for n in ("loss", "nonfinite", "grad"))
+    assert loss.dtype == nonfinite.dtype == grad.dtype == np.float32
+    assert loss.shape == () and abs(float(loss) - r["loss"]) <= 1e-6 * abs(r["loss"])
+    assert nonfinite.tolist() == [0.0, 0.0]
+    assert grad.shape == (100, 8, 8) and np.isfinite(grad).all() and np.linalg.norm(grad) > 0

@@ -10,12 +10,12 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 P=gpurun_out/r3/prof; mkdir -p $P
 echo "[1] default bench"; date
-python3 bench.py > $P/c3_bench.json 2> $P/c3_bench.err
-rocprofv3 --kernel-trace --stats -d $P/c3_stats -o b --output-format csv -- python3 bench.py > $P/c3_bench_profiled.json 2> $P/c3_bench_profiled.err
+python3 bench.py --full > $P/c3_bench.json 2> $P/c3_bench.err
+rocprofv3 --kernel-trace --stats -d $P/c3_stats -o b --output-format csv -- python3 bench.py --full > $P/c3_bench_profiled.json 2> $P/c3_bench_profiled.err
 echo "[2] other workloads"; date
 for w in c2 c3-sqfa c4 c5; do
-  python3 bench.py --workload $w --no-cpu-baseline --no-c4-pairs --no-c4-closure > $P/${w}_bench.json 2> $P/${w}_bench.err
-  rocprofv3 --kernel-trace --stats -d $P/${w}_stats -o b --output-format csv -- python3 bench.py --workload $w --no-cpu-baseline --no-c4-pairs --no-c4-closure > $P/${w}_bench_profiled.json 2> $P/${w}_bench_profiled.err
+  python3 bench.py --full --workload $w --no-cpu-baseline --no-c4-pairs --no-c4-closure > $P/${w}_bench.json 2> $P/${w}_bench.err
+  rocprofv3 --kernel-trace --stats -d $P/${w}_stats -o b --output-format csv -- python3 bench.py --full --workload $w --no-cpu-baseline --no-c4-pairs --no-c4-closure > $P/${w}_bench_profiled.json 2> $P/${w}_bench_profiled.err
 done
 echo "[3] HBM traffic"; date
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $P/pmc_w -o w --output-format csv -- python3 tools/run_closure_once.py > $P/pmc_w.log 2>&1

@@ -7,11 +7,11 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r4/prof
 mkdir -p $O
 # 1. the default bench line, plain and under rocprofv3 --kernel-trace --stats
-python3 bench.py > $O/c3_bench.json 2> $O/c3_bench.err
-rocprofv3 --kernel-trace --stats -d $O/c3_stats -o c3 --output-format csv -- python3 bench.py --no-cpu-baseline > $O/c3_bench_profiled.json 2> $O/c3_prof.err
+python3 bench.py --full > $O/c3_bench.json 2> $O/c3_bench.err
+rocprofv3 --kernel-trace --stats -d $O/c3_stats -o c3 --output-format csv -- python3 bench.py --full --no-cpu-baseline > $O/c3_bench_profiled.json 2> $O/c3_prof.err
 # 2. float64 line and the other workloads (pair stage + closure), plain
-python3 bench.py --dtype f64 --no-cpu-baseline --steps 60 --warmup 10 > $O/c3_f64_bench.json 2> $O/c3_f64.err
-for w in c2 c5; do python3 bench.py --workload $w --no-cpu-baseline --no-c4-pairs --no-c4-closure > $O/${w}_bench.json 2> $O/${w}.err; done
+python3 bench.py --full --dtype f64 --no-cpu-baseline --steps 60 --warmup 10 > $O/c3_f64_bench.json 2> $O/c3_f64.err
+for w in c2 c5; do python3 bench.py --full --workload $w --no-cpu-baseline --no-c4-pairs --no-c4-closure > $O/${w}_bench.json 2> $O/${w}.err; done
 # 3. HBM traffic of the closure's kernels: two --pmc passes (FETCH_SIZE, WRITE_SIZE), as MI355X_MICROARCH.md prescribes
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o f --output-format csv -- python3 tools/run_closure_once.py > $O/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o w --output-format csv -- python3 tools/run_closure_once.py > $O/pmc_write.log 2>&1

@@ -39,14 +39,26 @@ extern "C" {
 /* status codes (return values) */
 #define SQFA_OK                 0
 #define SQFA_ERR_BAD_ARGUMENT  -1   /* null pointer, negative size, bad dtype, bad shard ... */
-#define SQFA_ERR_UNSUPPORTED_M -2   /* m outside [1, sqfa_hip_max_dim()] */
+#define SQFA_ERR_UNSUPPORTED_M -2   /* m outside [1, sqfa_hip_max_dim()] (or the smaller limit of a function) */
 #define SQFA_ERR_WORKSPACE     -3   /* workspace_bytes smaller than sqfa_airm_workspace_bytes() */
 #define SQFA_ERR_LAUNCH        -4   /* a HIP launch failed; see sqfa_hip_last_error() */
 
 /* Library / build identification. */
 int sqfa_hip_version(void);            /* 1000*major + minor */
 const char *sqfa_hip_arch(void);       /* "gfx950" */
-int sqfa_hip_max_dim(void);            /* largest matrix size m handled natively */
+int sqfa_hip_max_dim(void);            /* largest matrix size m of the pair functions sqfa_airm_* (128) */
+
+/*
+ * Matrix sizes.  The sqfa_airm_* functions take 1 <= m <= 128:
+ *   m <= 64       register-resident lane-group kernels (pair_kernel.hpp, pair_kernel_2d.hpp), geometry table configs.hpp
+ *   64 < m <= 128 the LDS pair kernel (pair_kernel_lds.hip): one workgroup per pair at a time, the matrix in LDS, padded
+ *                 size round_up(m, 8); tiles of TI x TJ pairs from 16 x 16 down to 2 x 2 chosen from (nA, nB, m) only
+ *                 (every shard of a job uses the same tiling).  Of sqfa_airm_options only sweep_counter applies there (it
+ *                 then counts pairs, not wave rounds); geometry_policy, class_factor_policy and mean_metric_policy are
+ *                 ignored (no small-launch rows, no class factor pass).  Workspace: the factors (nA m^2 + nB m^2 / 2 values)
+ *                 and a slab of P (1/TI + 1/TJ) lower triangles for P pairs: 2.1 GB at C = 1000, m = 128, float32.
+ * The per-class SPD functions (sqfa_spd_function*) and the Gaussian pair terms keep m <= 64, the projection K <= 64.
+ */
 const char *sqfa_hip_last_error(void); /* text of the last HIP error seen by this library (host thread local) */
 
 /*
@@ -285,7 +297,7 @@ int sqfa_gauss_pair_terms(const void *muA, const void *covA, int nA, const void 
  *   S (n,m,m) dtype, F_out (n,m,m) dtype or NULL; U_out (n,m,m) and lam_out (n,m): FLOAT64, eigenvectors as columns,
  *   eigenvalues unsorted -- what sqfa_spd_function_backward needs (a non-SPD class yields NaN there and in F_out)
  *   kind: SQFA_SPD_LOG, SQFA_SPD_SQRT, SQFA_SPD_INV_SQRT (the symmetric inverse root)
- *   workspace: sqfa_spd_function_workspace_bytes(n, m, dtype) bytes; m <= sqfa_hip_max_dim()
+ *   workspace: sqfa_spd_function_workspace_bytes(n, m, dtype) bytes; m <= 64 (0 bytes / SQFA_ERR_UNSUPPORTED_M above)
  * sqfa_spd_function_backward: gradS_out (n,m,m) dtype = Q [(Q^T sym(G) Q) o Gamma] Q^T for the upstream gradient
  *   G (n,m,m) dtype wrt F (Daleckii-Krein; Gamma = divided differences of f, evaluated in forms that stay finite for
  *   repeated eigenvalues, where torch's eigh backward -- the reference's autograd -- returns inf / NaN).

@@ -90,7 +90,8 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
     code = _dtype_code(A)
     if m > lib.sqfa_hip_max_dim():
         raise NotImplementedError(
-            f"matrix size {m} exceeds the largest size the native kernels handle ({lib.sqfa_hip_max_dim()})"
+            f"matrix size {m} exceeds the largest size the native pair kernels handle ({lib.sqfa_hip_max_dim()}: "
+            "register kernels up to 64, the LDS kernel from 65 to 128)"
         )
     opts = _options()
     nbytes = lib.sqfa_airm_workspace_bytes_sharded(nA, nB, m, code, int(shard[1]), opts.geometry_policy)
@@ -331,11 +332,14 @@ class GaussPairTerms(torch.autograd.Function):
 # per-class matrix functions (spd_log / spd_sqrt: log_euclidean's building block)
 
 SPD_LOG, SPD_SQRT, SPD_INV_SQRT = 0, 1, 2
+# the per-class SPD functions have their own size limit (the pair kernels go to sqfa_hip_max_dim() = 128); larger
+# matrices keep the eigh path of linalg.py
+SPD_FUNCTION_MAX_DIM = 64
 
 
 def spd_function_supported(M):
     return (M.is_cuda and M.dtype in (torch.float32, torch.float64) and M.dim() >= 2 and M.shape[-1] == M.shape[-2]
-            and 1 <= M.shape[-1] <= max_dim() and M.numel() > 0)
+            and 1 <= M.shape[-1] <= SPD_FUNCTION_MAX_DIM and M.numel() > 0)
 
 
 class SpdFunction(torch.autograd.Function):

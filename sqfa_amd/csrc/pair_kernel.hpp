@@ -102,6 +102,35 @@ __host__ __device__ inline int shard_tiles_in_row(int bi, int len, int shard_ind
   return len > o ? (len - 1 - o) / shard_count + 1 : 0;
 }
 
+// Slab slot table for K2 (PairParams::row_start), written by block 0 of a 256-thread prologue launch: owned tiles before
+// each block-row, in the compact grid's order.  The per-row counts (integer divisions) are evaluated by 256 threads at
+// once, thread 0 only adds them up: a serial loop here put 9 us on the critical path of the whole prologue (block 0
+// finished last).
+__device__ inline void write_row_start_table(const PairParams& pp, int TI, int* row_start) {
+  __shared__ int s_cnt[256];
+  int base = 0;
+  for (int b0 = 0; b0 < pp.nbi; b0 += 256) {
+    const int bi = b0 + (int)threadIdx.x;
+    int cnt = 0, first;
+    if (bi < pp.nbi)
+      cnt = shard_tiles_in_row(bi, tiles_in_row(bi, pp.nbj, TI, pp.tj, pp.self_mode), pp.shard_index, pp.shard_count, &first);
+    s_cnt[threadIdx.x] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int acc = base;
+      for (int k = 0; k < 256 && b0 + k < pp.nbi; ++k) {
+        row_start[b0 + k] = acc;
+        acc += s_cnt[k];
+      }
+      s_cnt[0] = acc;
+    }
+    __syncthreads();
+    base = s_cnt[0];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) row_start[pp.nbi] = base;
+}
+
 __host__ __device__ constexpr int ilog2(int v);
 __host__ __device__ constexpr int pow2ceil(int v) {
   int p = 1;

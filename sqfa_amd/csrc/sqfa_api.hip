@@ -13,6 +13,7 @@
 #include "configs.hpp"
 #include "pair_kernel.hpp"
 #include "pair_kernel_2d.hpp"
+#include "pair_kernel_lds.hpp"
 
 namespace sqfa {
 
@@ -99,14 +100,8 @@ static long pair_count(int nA, int nB, int shard_count) {  // pairs per shard of
   return p / (shard_count > 0 ? shard_count : 1);
 }
 
-static int max_dim() {
-  int mx = 0;
-#define SQFA_MAX(T, MR_, G_, CPL_, TJ_, WV_) if (MR_ > mx) mx = MR_;
-#define SQFA_MAX2D(T, MR_, GC_, CPL_, TJ_, WV_, RS_) if (MR_ > mx) mx = MR_;
-  SQFA_CONFIGS_F32(SQFA_MAX)
-  SQFA_CONFIGS2D_F32(SQFA_MAX2D)
-  return mx;
-}
+// The per-class SPD functions (Cholesky + class_eig_kernel) exist for the register geometries only.
+constexpr int kSpdMaxDim = kRegMaxDim;
 
 static thread_local char g_last_error[256] = "";
 
@@ -220,6 +215,52 @@ static WorkspaceLayout layout(int nA, int nBeff, const Geometry& g, size_t esz, 
   return w;
 }
 
+// ---- 64 < m <= 128: tiling and workspace of the LDS pair path (pair_kernel_lds.hip) ------------------------------------
+// One workgroup per tile of TI x TJ pairs, the pairs one after the other.  Tiles start at 16 x 16 (the slab holds
+// P (1/TI + 1/TJ) lower triangles for P pairs: 2.1 GB at C = 1000, m = 128, float32) and are halved, TJ first, while the
+// job has fewer than kLdsMinTiles tiles, down to 2 x 2 (C = 100: 1 275 tiles).  The tiling depends on (nA, nB, m) only:
+// every shard of a job uses the same one.  Nothing of Geometry / find_geometry is involved.
+constexpr long kLdsMinTiles = 1024;  // 4 x the 256 CUs
+struct LdsTiling {
+  int MR, TI, TJ;
+};
+static long lds_tiles(int nA, int nBeff, int TI, int TJ, int self_mode, int shard_index, int shard_count) {
+  const int nbi = (nA + TI - 1) / TI, nbj = (nBeff + TJ - 1) / TJ;
+  long n = 0;
+  for (int bi = 0; bi < nbi; ++bi) {
+    int first;
+    n += shard_tiles_in_row(bi, tiles_in_row(bi, nbj, TI, TJ, self_mode), shard_index, shard_count, &first);
+  }
+  return n;
+}
+static LdsTiling lds_tiling(int nA, int nBeff, int m, int self_mode) {
+  LdsTiling t{lds_padded_size(m), 16, 16};
+  while (t.TI * t.TJ > 4 && lds_tiles(nA, nBeff, t.TI, t.TJ, self_mode, 0, 1) < kLdsMinTiles) {
+    if (t.TJ >= t.TI) t.TJ /= 2;
+    else t.TI /= 2;
+  }
+  return t;
+}
+// shard_count: the slab holds the tiles of the largest shard (1: every tile, enough for any shard count)
+static WorkspaceLayout layout_lds(int nA, int nBeff, const LdsTiling& t, size_t esz, int self_mode, int shard_count) {
+  WorkspaceLayout w;
+  size_t owned = 0;
+  for (int r = 0; r < shard_count; ++r)
+    owned = std::max(owned, (size_t)lds_tiles(nA, nBeff, t.TI, t.TJ, self_mode, r, shard_count));
+  const size_t tri = (size_t)t.MR * (t.MR + 1) / 2;
+  const size_t nbi = (nA + t.TI - 1) / t.TI;
+  size_t o = 0;
+  w.off_lt = o;   o = align_up(o + (size_t)nA * t.MR * t.MR * esz);
+  w.off_linv = o; o = align_up(o + (size_t)nBeff * tri * esz);  // packed lower triangles
+  w.off_slab = o; o = align_up(o + owned * (size_t)(t.TI + t.TJ) * tri * esz);
+  w.off_loss = o; o = align_up(o + owned * esz);
+  w.off_flag = o; o = align_up(o + owned * 2 * sizeof(int));
+  w.off_rows = o; o = align_up(o + (nbi + 1) * sizeof(int));
+  w.off_mean = o;  // no class factor pass above 64
+  w.total = o;
+  return w;
+}
+
 // ---- K0: per-class Cholesky factor and its inverse (always evaluated in double) ----------
 // One 256-thread workgroup per class, matrix in LDS.  LT[c][col*MR + k] = L[k][col];
 // Linv[c][r*MR + k] = (L^-1)[r][k] (MR < 32) or packed Linv[c][r(r+1)/2 + k], k <= r (MR >= 32).
@@ -263,33 +304,7 @@ __global__ __launch_bounds__(256) void cholesky_kernel(const T* __restrict__ S, 
                                                        int* __restrict__ row_start, PairParams pp, int TI,
                                                        int n_classes = 0, const double* __restrict__ mean_parts = nullptr,
                                                        int n_parts = 0, double* __restrict__ mean_linv = nullptr) {
-  if (row_start != nullptr && blockIdx.x == 0) {
-    // slab slot table for K2: owned tiles before each block-row, in the compact grid's order.  The per-row
-    // counts (integer divisions) are evaluated by 256 threads at once, thread 0 only adds them up: a serial
-    // loop here put 9 us on the critical path of the whole prologue (block 0 finished last).
-    __shared__ int s_cnt[256];
-    int base = 0;
-    for (int b0 = 0; b0 < pp.nbi; b0 += 256) {
-      const int bi = b0 + (int)threadIdx.x;
-      int cnt = 0, first;
-      if (bi < pp.nbi)
-        cnt = shard_tiles_in_row(bi, tiles_in_row(bi, pp.nbj, TI, pp.tj, pp.self_mode), pp.shard_index, pp.shard_count, &first);
-      s_cnt[threadIdx.x] = cnt;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        int acc = base;
-        for (int k = 0; k < 256 && b0 + k < pp.nbi; ++k) {
-          row_start[b0 + k] = acc;
-          acc += s_cnt[k];
-        }
-        s_cnt[0] = acc;
-      }
-      __syncthreads();
-      base = s_cnt[0];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) row_start[pp.nbi] = base;
-  }
+  if (row_start != nullptr && blockIdx.x == 0) write_row_start_table(pp, TI, row_start);
   // LDS sized for the padded size class (MAXM >= m) so that small problems keep many
   // workgroups per CU resident
   __shared__ double a[MAXM][MAXM + 1];
@@ -664,7 +679,7 @@ extern "C" {
 
 int sqfa_hip_version(void) { return 1000; }
 const char* sqfa_hip_arch(void) { return "gfx950"; }
-int sqfa_hip_max_dim(void) { return max_dim(); }
+int sqfa_hip_max_dim(void) { return kLdsMaxDim; }
 const char* sqfa_hip_last_error(void) { return g_last_error; }
 
 int sqfa_airm_profile(int enable) {
@@ -713,6 +728,17 @@ int sqfa_project_profile_read(double* kernel_ms_total, int* launches) {
 int sqfa_airm_tiling(int nA, int nB, int m, int dtype, int* tile_i, int* tile_j, int* n_tiles_i,
                      int* n_tiles_j, int* padded_m) {
   if (nA < 1 || nB < 0 || m < 1 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return SQFA_ERR_BAD_ARGUMENT;
+  if (m > kRegMaxDim) {
+    if (m > kLdsMaxDim) return SQFA_ERR_UNSUPPORTED_M;
+    const int nBeff = nB == 0 ? nA : nB;
+    const LdsTiling t = lds_tiling(nA, nBeff, m, nB == 0 ? 1 : 0);
+    if (tile_i) *tile_i = t.TI;
+    if (tile_j) *tile_j = t.TJ;
+    if (n_tiles_i) *n_tiles_i = (nA + t.TI - 1) / t.TI;
+    if (n_tiles_j) *n_tiles_j = (nBeff + t.TJ - 1) / t.TJ;
+    if (padded_m) *padded_m = t.MR;
+    return SQFA_OK;
+  }
   Geometry g;
   if (!find_geometry(m, dtype, pair_count(nA, nB, 1), &g)) return SQFA_ERR_UNSUPPORTED_M;  // the geometry of an unsharded call
   const int nBeff = nB == 0 ? nA : nB;
@@ -728,6 +754,8 @@ size_t sqfa_airm_workspace_bytes(int nA, int nB, int m, int dtype) {
   int ti, tj, nbi, nbj, mr;
   if (sqfa_airm_tiling(nA, nB, m, dtype, &ti, &tj, &nbi, &nbj, &mr) != SQFA_OK) return 0;
   const int nBeff = nB == 0 ? nA : nB;
+  if (m > kRegMaxDim)
+    return layout_lds(nA, nBeff, lds_tiling(nA, nBeff, m, nB == 0 ? 1 : 0), dtype == SQFA_F32 ? 4 : 8, nB == 0 ? 1 : 0, 1).total;
   // enough for any shard count: the regular row's and the small-launch row's layouts both fit
   Geometry g;
   find_geometry(m, dtype, -1, &g, -1);   // the regular row ...
@@ -735,6 +763,102 @@ size_t sqfa_airm_workspace_bytes(int nA, int nB, int m, int dtype) {
   find_geometry(m, dtype, 0, &g, 1);     // ... and the small-launch row of the size, whatever policy a call will carry
   need = std::max(need, layout(nA, nBeff, g, dtype == SQFA_F32 ? 4 : 8, nB == 0 ? 1 : 0).total);
   return need;
+}
+
+// 64 < m <= 128 (arguments already checked): K0L, K1L (pair_kernel_lds.hip), K2 unchanged.  The class factor pass and
+// the geometry / class factor / mean metric policies do not apply here.
+static int pairwise_lds(const void* A, int nA, const void* B, int nB, int m, int dtype, double scale, double eps,
+                        int sqrt_mode, const void* pair_weights, double uniform_weight, int shard_index, int shard_count,
+                        void* loss_out, void* gradA_out, void* gradB_out, void* dist_out, void* eig_out,
+                        int* nonfinite_out, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                        const void* eig_weights, unsigned long long* sweep_counter) {
+  const bool self_mode = (B == nullptr);
+  const int nBeff = self_mode ? nA : nB;
+  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
+  const int f64 = dtype == SQFA_F64 ? 1 : 0;
+  const LdsTiling t = lds_tiling(nA, nBeff, m, self_mode ? 1 : 0);
+  const WorkspaceLayout w = layout_lds(nA, nBeff, t, esz, self_mode ? 1 : 0, shard_count);
+  if (workspace_bytes < w.total) return fail(SQFA_ERR_WORKSPACE, "workspace too small", hipSuccess);
+  char* ws = static_cast<char*>(workspace);
+
+  PairParams p;
+  memset(&p, 0, sizeof(p));
+  p.LT = ws + w.off_lt;
+  p.Linv = ws + w.off_linv;
+  p.W = pair_weights;
+  p.EW = eig_weights;
+  p.slab_grad = ws + w.off_slab;
+  p.slab_loss = ws + w.off_loss;
+  p.slab_flag = reinterpret_cast<int*>(ws + w.off_flag);
+  p.row_start = reinterpret_cast<int*>(ws + w.off_rows);
+  p.dist_out = dist_out;
+  p.eig_out = eig_out;
+  p.sweep_counter = sweep_counter;
+  p.nA = nA;
+  p.nB = nBeff;
+  p.m = m;
+  p.self_mode = self_mode ? 1 : 0;
+  p.sqrt_mode = sqrt_mode ? 1 : 0;
+  p.want_grad = gradA_out != nullptr ? 1 : 0;
+  p.shard_index = shard_index;
+  p.shard_count = shard_count;
+  p.nbi = (nA + t.TI - 1) / t.TI;
+  p.nbj = (nBeff + t.TJ - 1) / t.TJ;
+  p.tj = t.TJ;
+  p.factor_mode = -1;
+  p.scale = scale;
+  p.eps = eps;
+  p.uniform_weight = uniform_weight;
+  p.scale_f = (float)scale;
+  p.eps_f = (float)eps;
+  p.uniform_weight_f = (float)uniform_weight;
+
+  // K0L: factors (the first launch also writes the slab slot table)
+  hipError_t e;
+  if (self_mode) {
+    e = launch_lds_prologue(f64, A, nA, m, t.MR, ws + w.off_lt, ws + w.off_linv, p.row_start, p, t.TI, stream);
+  } else {
+    e = launch_lds_prologue(f64, A, nA, m, t.MR, ws + w.off_lt, nullptr, p.row_start, p, t.TI, stream);
+    if (e == hipSuccess) e = launch_lds_prologue(f64, B, nB, m, t.MR, nullptr, ws + w.off_linv, nullptr, p, t.TI, stream);
+  }
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "cholesky_lds_kernel", e);
+
+  // K1L: pair tiles
+  EventPair ev{};
+  bool prof = g_profile.load();
+  if (prof) {  // event records do not belong in a captured graph: profile eager launches only
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) prof = false;
+  }
+  if (prof) {
+    (void)hipEventCreate(&ev.a);
+    (void)hipEventCreate(&ev.b);
+    (void)hipEventRecord(ev.a, stream);
+  }
+  e = launch_pair_lds(f64, p, t.TI, t.MR, stream);
+  if (prof) {
+    (void)hipEventRecord(ev.b, stream);
+    std::lock_guard<std::mutex> lock(g_events_mutex);
+    g_events.push_back(ev);
+  }
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "pair_lds_kernel", e);
+
+  // K2: slab reduction (finalize_kernel, unchanged)
+  const int n_cls = nA + (self_mode ? 0 : nB);
+  const int k2_tri = t.MR * (t.MR + 1) / 2;
+  const int k2_bpc = (k2_tri + 127) / 128;  // workgroups per class (finalize_kernel's EPB; TRI > 256 here)
+  if (dtype == SQFA_F32) {
+    hipLaunchKernelGGL(finalize_kernel<float>, dim3(n_cls * k2_bpc + 1), dim3(SQFA_K2_THREADS), 0, stream, p, t.TI, t.TJ, t.MR,
+                       static_cast<float*>(gradA_out), static_cast<float*>(gradB_out),
+                       static_cast<float*>(loss_out), nonfinite_out);
+  } else {
+    hipLaunchKernelGGL(finalize_kernel<double>, dim3(n_cls * k2_bpc + 1), dim3(SQFA_K2_THREADS), 0, stream, p, t.TI, t.TJ, t.MR,
+                       static_cast<double*>(gradA_out), static_cast<double*>(gradB_out),
+                       static_cast<double*>(loss_out), nonfinite_out);
+  }
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_kernel", e);
+  return SQFA_OK;
 }
 
 static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, int dtype, double scale,
@@ -755,6 +879,12 @@ static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, in
   if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail(SQFA_ERR_BAD_ARGUMENT, "shard", hipSuccess);
   const bool self_mode = (B == nullptr);
   if (self_mode && nA < 2) return fail(SQFA_ERR_BAD_ARGUMENT, "self mode needs at least two classes", hipSuccess);
+  if (m > kRegMaxDim) {
+    if (m > kLdsMaxDim) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+    return pairwise_lds(A, nA, B, nB, m, dtype, scale, eps, sqrt_mode, pair_weights, uniform_weight, shard_index,
+                        shard_count, loss_out, gradA_out, gradB_out, dist_out, eig_out, nonfinite_out, workspace,
+                        workspace_bytes, stream, eig_weights, options ? options->sweep_counter : nullptr);
+  }
   Geometry g;
   if (!find_geometry(m, dtype, pair_count(nA, nB, shard_count), &g, geometry_mode)) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
   const size_t esz = dtype == SQFA_F32 ? 4 : 8;
@@ -894,6 +1024,10 @@ static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, in
 size_t sqfa_airm_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy) {
   int ti, tj, nbi, nbj, mr;
   if (shard_count < 1 || sqfa_airm_tiling(nA, nB, m, dtype, &ti, &tj, &nbi, &nbj, &mr) != SQFA_OK) return 0;
+  if (m > kRegMaxDim) {
+    const int nBeff = nB == 0 ? nA : nB, self_mode = nB == 0 ? 1 : 0;
+    return layout_lds(nA, nBeff, lds_tiling(nA, nBeff, m, self_mode), dtype == SQFA_F32 ? 4 : 8, self_mode, shard_count).total;
+  }
   Geometry g;
   find_geometry(m, dtype, pair_count(nA, nB, shard_count), &g, geometry_policy > 0 ? 1 : (geometry_policy < 0 ? -1 : 0));
   const int nBeff = nB == 0 ? nA : nB, self_mode = nB == 0 ? 1 : 0;
@@ -984,7 +1118,7 @@ int sqfa_spd_function_backward(const double* U, const double* lam, const void* G
     return fail(SQFA_ERR_BAD_ARGUMENT, "null/size argument", hipSuccess);
   if (dtype != SQFA_F32 && dtype != SQFA_F64) return fail(SQFA_ERR_BAD_ARGUMENT, "dtype", hipSuccess);
   if (kind != SQFA_SPD_LOG && kind != SQFA_SPD_SQRT && kind != SQFA_SPD_INV_SQRT) return fail(SQFA_ERR_BAD_ARGUMENT, "kind", hipSuccess);
-  if (m > max_dim()) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+  if (m > kSpdMaxDim) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
   const size_t lds = ((size_t)3 * m * m + m) * sizeof(double);   // 96.5 KB at m = 64
   if (dtype == SQFA_F32) {
     if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spd_function_backward_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

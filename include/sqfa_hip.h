@@ -153,6 +153,31 @@ int sqfa_airm_pairwise_opt(const void *A, int nA, const void *B, int nB, int m, 
                            const sqfa_airm_options *options);
 
 /*
+ * Pairwise Bures-Wasserstein distances between SPD matrices (the distance_fun the reference's tutorial builds,
+ * docs/source/tutorials/distances.md:127-178: bw_distance_sq / bw_distance), their weighted sum and its gradient:
+ *     bw2(A, B) = tr A + tr B - 2 sum_k sqrt(lambda_k(A B)),   D = sqrt(|bw2| + eps) when sqrt_mode != 0, else D = bw2
+ * Same kernels as sqfa_airm_pairwise with a second spectral function: the B-side factor is R_j (R_j^T R_j = B_j, lower
+ * triangular) in place of L_j^-1, and sum_k sigma_k of X = R_j F_i replaces sum_k log^2 lambda_k.
+ * Arguments, modes (self / cross), pair weights, shards, outputs and guarantees as sqfa_airm_pairwise_opt, without scale and
+ * eig_out: no sync, no allocation, no float atomics; bitwise reproducible for fixed inputs and sharding; the shards of one
+ * shard_count sum to the whole; a non-SPD class counts as a NaN / inf distance.  1 <= m <= 128 (SQFA_ERR_UNSUPPORTED_M).
+ * options: geometry_policy, class_factor_policy and sweep_counter as for sqfa_airm_pairwise_opt; mean_metric_policy does not
+ * apply (the factor pass, where it runs, uses the plain inner product).
+ * Workspace: sqfa_bw_workspace_bytes[_sharded] (the affine-invariant queries are NOT enough: the B-side gradient needs
+ * R_j^-1 and two more m x m double buffers per class).
+ */
+size_t sqfa_bw_workspace_bytes(int nA, int nB, int m, int dtype);
+size_t sqfa_bw_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy);
+int sqfa_bw_pairwise(const void *A, int nA, const void *B, int nB, int m, int dtype,
+                     double eps, int sqrt_mode,
+                     const void *pair_weights, double uniform_weight,
+                     int shard_index, int shard_count,
+                     void *loss_out, void *gradA_out, void *gradB_out,
+                     void *dist_out, int *nonfinite_out,
+                     void *workspace, size_t workspace_bytes, void *stream,
+                     const sqfa_airm_options *options);
+
+/*
  * Backward of the generalized eigenvalues themselves (the reference's generalized_eigenvalues,
  * src/sqfa/linalg.py:48-70, is autograd-transparent and its tutorial builds custom distance_funs
  * on it, docs/source/tutorials/distances.md:127-178): gradient of

@@ -46,6 +46,15 @@ PROTOTYPES = {
     "sqfa_airm_workspace_bytes_sharded": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "sqfa_airm_pairwise": (ctypes.c_int, list(_PAIRWISE_ARGS)),
     "sqfa_airm_pairwise_opt": (ctypes.c_int, list(_PAIRWISE_ARGS) + [ctypes.POINTER(AirmOptions)]),
+    "sqfa_bw_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "sqfa_bw_workspace_bytes_sharded": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "sqfa_bw_pairwise": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+         ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(AirmOptions)],
+    ),
     "sqfa_airm_eigenvalues_backward": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -68,10 +68,15 @@ def _options():
 
 
 def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, shard,
-                     want_loss, want_grad, want_dist, want_eig, out_loss=None, out_gradA=None):
-    """Run sqfa_airm_pairwise on the current stream.  A (nA,m,m); B (nB,m,m) or None (self).
+                     want_loss, want_grad, want_dist, want_eig, out_loss=None, out_gradA=None, metric="airm"):
+    """Run sqfa_airm_pairwise (metric "airm") or sqfa_bw_pairwise (metric "bw": Bures-Wasserstein, `scale` unused, no
+    eigenvalues) on the current stream.  A (nA,m,m); B (nB,m,m) or None (self).
     Returns dict(loss, gradA, gradB, dist, eig, nonfinite) of freshly allocated tensors
     (None where not requested)."""
+    if metric not in ("airm", "bw"):
+        raise ValueError(f"unknown pair metric {metric!r}")
+    if metric == "bw" and want_eig:
+        raise ValueError("the Bures-Wasserstein pair path has no eigenvalue output")
     lib = _lib.load()
     if not A.is_cuda:
         raise RuntimeError(
@@ -94,9 +99,10 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
             "register kernels up to 64, the LDS kernel from 65 to 128)"
         )
     opts = _options()
-    nbytes = lib.sqfa_airm_workspace_bytes_sharded(nA, nB, m, code, int(shard[1]), opts.geometry_policy)
+    ws_query = lib.sqfa_bw_workspace_bytes_sharded if metric == "bw" else lib.sqfa_airm_workspace_bytes_sharded
+    nbytes = ws_query(nA, nB, m, code, int(shard[1]), opts.geometry_policy)
     if nbytes == 0:
-        raise _lib.NativeLibraryError("sqfa_airm_workspace_bytes rejected the problem shape")
+        raise _lib.NativeLibraryError(f"{ws_query.__name__} rejected the problem shape")
     dev = A.device
     nBe = nA if B is None else nB
     with torch.cuda.device(dev):
@@ -117,6 +123,15 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
             if tuple(weights.shape) != (nA, nBe):
                 raise ValueError("pair weights must have shape (nA, nB)")
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if metric == "bw":
+            status = lib.sqfa_bw_pairwise(
+                _ptr(A), nA, _ptr(B), nB, m, code, float(eps), int(bool(sqrt_mode)),
+                _ptr(weights), float(uniform_weight), int(shard[0]), int(shard[1]),
+                _ptr(loss), _ptr(gradA), _ptr(gradB), _ptr(dist), _ptr(nonfinite),
+                _ptr(ws), nbytes, ctypes.c_void_p(stream), ctypes.byref(opts),
+            )
+            _lib.check(status, "sqfa_bw_pairwise")
+            return {"loss": loss, "gradA": gradA, "gradB": gradB, "dist": dist, "eig": None, "nonfinite": nonfinite}
         status = lib.sqfa_airm_pairwise_opt(
             _ptr(A), nA, _ptr(B), nB, m, code,
             float(scale), float(eps), int(bool(sqrt_mode)),
@@ -142,13 +157,15 @@ class PairDistanceMatrix(torch.autograd.Function):
     size nA*nB*m*m is ever stored)."""
 
     @staticmethod
-    def forward(ctx, A, B, scale, eps, sqrt_mode):
+    def forward(ctx, A, B, scale, eps, sqrt_mode, metric="airm"):
+        kw = {"metric": metric} if metric != "airm" else {}
         out = _pair_backend(A, B, scale=scale, eps=eps, sqrt_mode=sqrt_mode, weights=None,
                             uniform_weight=0.0, shard=(0, 1), want_loss=False, want_grad=False,
-                            want_dist=True, want_eig=False)
+                            want_dist=True, want_eig=False, **kw)
         ctx.save_for_backward(A, B if B is not None else A.new_empty(0))
         ctx.self_mode = B is None
         ctx.cfg = (scale, eps, sqrt_mode)
+        ctx.kw = kw
         ctx.mark_non_differentiable(out["nonfinite"])
         return out["dist"], out["nonfinite"]
 
@@ -159,8 +176,8 @@ class PairDistanceMatrix(torch.autograd.Function):
         scale, eps, sqrt_mode = ctx.cfg
         out = _pair_backend(A, B, scale=scale, eps=eps, sqrt_mode=sqrt_mode, weights=gD,
                             uniform_weight=0.0, shard=(0, 1), want_loss=False, want_grad=True,
-                            want_dist=False, want_eig=False)
-        return out["gradA"], out["gradB"], None, None, None
+                            want_dist=False, want_eig=False, **ctx.kw)
+        return out["gradA"], out["gradB"], None, None, None, None
 
 
 class PairwiseLoss(torch.autograd.Function):
@@ -169,8 +186,8 @@ class PairwiseLoss(torch.autograd.Function):
     gradient, in one pass.  `reducer(loss, nonfinite, grad)` combines shards (all-reduce)."""
 
     @staticmethod
-    def forward(ctx, S, scale, eps, sqrt_mode, weight, shard, reducer):
-        extra = {}
+    def forward(ctx, S, scale, eps, sqrt_mode, weight, shard, reducer, metric="airm"):
+        extra = {"metric": metric} if metric != "airm" else {}
         fused = None
         owner = getattr(reducer, "__self__", None)
         if (reducer is not None and shard[1] > 1 and _pair_backend is hip_pair_backend
@@ -178,7 +195,7 @@ class PairwiseLoss(torch.autograd.Function):
             # the kernel writes loss and gradient straight into the all-reduce buffer
             # [loss, nan, inf, grad...]: no packing copies
             fused = torch.empty(S.numel() + 3, dtype=S.dtype, device=S.device)
-            extra = {"out_loss": fused[0], "out_gradA": fused[3:].view(S.shape)}
+            extra.update({"out_loss": fused[0], "out_gradA": fused[3:].view(S.shape)})
         out = _pair_backend(S, None, scale=scale, eps=eps, sqrt_mode=sqrt_mode, weights=None,
                             uniform_weight=weight, shard=shard, want_loss=True, want_grad=True,
                             want_dist=False, want_eig=False, **extra)
@@ -194,7 +211,7 @@ class PairwiseLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gflag):
         (grad,) = ctx.saved_tensors
-        return grad * gloss, None, None, None, None, None, None
+        return grad * gloss, None, None, None, None, None, None, None
 
 
 def hip_eigenvalues_backward(A, B, eig_weights):
@@ -663,12 +680,12 @@ def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
             "S": S, "S_shape": tuple(S.shape), "sphere": sphere}
 
 
-def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None):
+def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None, metric="airm"):
     """Second half: K0 / K1 / K2 on the (C,m,m) batch.  `fused` (S.numel() + 3 elements), when given, receives
     [loss, nan, inf, dL/dS...] in place (the all-reduce buffer of a sharded evaluation)."""
-    extra = {}
+    extra = {"metric": metric} if metric != "airm" else {}
     if fused is not None:
-        extra = {"out_loss": fused[0], "out_gradA": fused[3:].view(S.shape)}
+        extra.update({"out_loss": fused[0], "out_gradA": fused[3:].view(S.shape)})
     out = _pair_backend(S, None, scale=scale, eps=EPSILON, sqrt_mode=sqrt_mode, weights=None,
                         uniform_weight=weight, shard=shard, want_loss=True, want_grad=True,
                         want_dist=False, want_eig=False, **extra)
@@ -677,10 +694,10 @@ def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None):
     return out["loss"], out["nonfinite"], out["gradA"]
 
 
-def closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, sphere, fused=None):
+def closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, sphere, fused=None, metric="airm"):
     """Both halves (closure_stage_project + closure_stage_pairs) for statistics that are not class-sharded."""
     st = closure_stage_project(raw, scatters, means, noise, sphere)
-    st["loss"], st["nonfinite"], st["gS"] = closure_stage_pairs(st["S"], scale, sqrt_mode, weight, shard, fused)
+    st["loss"], st["nonfinite"], st["gS"] = closure_stage_pairs(st["S"], scale, sqrt_mode, weight, shard, fused, metric)
     return st
 
 
@@ -729,14 +746,14 @@ class FusedClosure(torch.autograd.Function):
     BACKWARD_GROUPS = 64
 
     @staticmethod
-    def forward(ctx, raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere):
+    def forward(ctx, raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere, metric="airm"):
         fused = None
         owner = getattr(reducer, "__self__", None)
         if reducer is not None and shard[1] > 1 and _pair_backend is hip_pair_backend and hasattr(owner, "reduce_fused"):
             C, K = scatters.shape[0], raw.shape[0]
             m = K + 1 if means is not None else K
             fused = torch.empty(C * m * m + 3, dtype=scatters.dtype, device=scatters.device)
-        st = closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, sphere, fused)
+        st = closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, sphere, fused, metric)
         loss, nonfinite, gS = st["loss"], st["nonfinite"], st["gS"]
         if fused is not None:
             loss, nonfinite, gS = owner.reduce_fused(fused, nonfinite, st["S_shape"])
@@ -750,4 +767,4 @@ class FusedClosure(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gflag):
         grad = closure_stage_backward(ctx.st, ctx.gS, gloss)
-        return grad, None, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None, None

@@ -149,10 +149,13 @@ class ShardedClosure:
 
     @staticmethod
     def supported(model, prepared):
+        from . import distances
         params = list(model.parameters())
         return bool(GRAPH_CLOSURE and len(params) == 1 and params[0].is_cuda
                     and getattr(model, "pair_shard", None) is not None and model.pair_shard.world_size > 1
                     and hasattr(model, "_has_fused_closure") and model._has_fused_closure()
+                    # the staged graphs evaluate the affine-invariant family only: other pair metrics stay eager
+                    and distances.fused_spec(model.distance_fun)[3] == "airm"
                     and hasattr(model, "_single_node_inputs")
                     and model._single_node_inputs(prepared, allow_class_shard=True) is not None
                     and model._noise_scalar() is not None)
@@ -167,7 +170,8 @@ class ShardedClosure:
         from . import _native, distances
         import torch.distributed as dist
         raw, scatters, means, sphere = model._single_node_inputs(prepared, allow_class_shard=True)
-        _, scale, sqrt_mode = distances.fused_spec(model.distance_fun)
+        spec = distances.fused_spec(model.distance_fun)
+        scale, sqrt_mode = spec[1], spec[2]
         noise = model._noise_scalar()
         shard = model.pair_shard
         cshard = getattr(model, "class_shard", None)

@@ -36,6 +36,14 @@
 // v_rsq/v_rcp/v_sqrt = 3.2 slots, v_pk_fma_f32 = 1.7 slots for 2 flops, v_permlane16/32_swap 3.2,
 // ds_swizzle ~2.3 cycles per CU (LDS pipe, off the VALU), ds_bpermute ~6; LDS float atomics: unusable.
 //
+// Bures-Wasserstein (template flag BW, sqfa_bw_pairwise): the B-side factor staged where L_j^-1 is, is R_j (lower triangular,
+// R_j^T R_j = B_j, bw_prologue_kernel in sqfa_api.hip), so X = R_j F_i has singular values sigma_k = sqrt(lambda_k(A_i B_j));
+// step 3 becomes d2 = tr A_i + tr B_j - 2 sum sigma_k, step 4 the optimal-transport coefficients with u~ = R_j^T y:
+//   dL/dA += h (I - sum_k sigma_k^-3 u~ u~^T),   dL/dB += h (I - R_j^-1 [sum_k sigma_k^-1 y y^T] R_j^-T),  h = w dD/dd2;
+// the B-side bracket (in y coordinates, summed before the back-transform) goes to the slab, the R_j^-1 sandwich and the
+// identity term follow its reduction (finalize_bw_kernel, bw_sandwich_kernel).  With BW = false every instantiation is the
+// affine-invariant kernel above.
+//
 // Replaces: src/sqfa/linalg.py:19-70,144-162, src/sqfa/distances.py:46-89,177-237,
 // src/sqfa/_optim.py:16-30,88-96 of the reference and the autograd backward of that chain.
 #pragma once
@@ -68,6 +76,10 @@ struct PairParams {
   const double* mean_linv;  // Lbar^-1 of the mean A class (MR x MR doubles, identity padded) for the mean-metric factor pass, or nullptr
   double scale, eps, uniform_weight;
   float scale_f, eps_f, uniform_weight_f;  // the same three, pre-rounded for the float32 kernels (stay in SGPRs)
+  // Bures-Wasserstein kernels only (sqfa_bw_pairwise; the Linv slot then holds R_j, R_j^T R_j = B_j, see bw_prologue_kernel):
+  const double* trA;  // [nA] traces of the A classes
+  const double* trB;  // [nB] traces of the B classes (self mode: trA)
+  void* slab_h;       // [tiles of this shard][tj]  sum over the pairs of a B-side slab row of h = w dD/dbw2 (identity term)
 };
 
 template <typename T> __device__ __forceinline__ T param_scale(const PairParams& p) {
@@ -1222,7 +1234,10 @@ struct PairCfg {
 // EIG_BWD selects the backward of the eigenvalues themselves (per-eigenvalue weights EWt) at COMPILE time:
 // as a run-time branch it kept six more values alive across the backward phase of the hot instantiation
 // (7 spilled VGPRs instead of 1 at m=16, +20 MB of scratch traffic per launch).
-template <typename Cfg, bool EIG_BWD>
+// BW selects the Bures-Wasserstein distance (sqfa_bw_pairwise) instead of the affine-invariant one, also at compile time:
+// steps 1, 2 and the back-transform are the same code with R_j staged where L_j^-1 is (X = R_j F_i, u~ = R_j^T y); step 3
+// sums sigma_k = |y_k| instead of log^2 lambda_k, step 4 uses the optimal-transport coefficients ("Bures-Wasserstein").
+template <typename Cfg, bool EIG_BWD, bool BW = false>
 __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel(
     const PairParams p, const typename Cfg::type* __restrict__ LT,
     const typename Cfg::type* __restrict__ LinvAll, const typename Cfg::type* __restrict__ Wt,
@@ -1311,6 +1326,9 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
       if (p.want_grad) {  // nothing to add for this B class, but the slab entry must be defined
         T* gbz = static_cast<T*>(p.slab_grad) + ((size_t)tile * (TI + tj) + TI + jj) * TRI;
         for (int k = lane; k < TRI; k += 64) gbz[k] = T(0);
+        if constexpr (BW) {
+          if (lane == 0) static_cast<T*>(p.slab_h)[(size_t)tile * tj + jj] = T(0);
+        }
       }
       continue;
     }
@@ -1472,12 +1490,24 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
 #pragma unroll
       for (int r = 0; r < MR; ++r) a = R::fma_(x[c][r], x[c][r], a);
       const bool real_col = col < p.m;  // identity-padded and empty slots carry no signal
+      if constexpr (BW) {
+        lam[c] = real_col ? R::sqrt_(a) : T(0);  // sigma_k
+        part += lam[c];
+      } else {
       lam[c] = real_col ? a : T(1);
       loglam[c] = real_col ? R::log_(a) : T(0);
       part = R::fma_(loglam[c], loglam[c], part);
+      }
     }
-    const T d2 = scale * group_sum<G>(part);
-    const T dist = p.sqrt_mode ? R::sqrt_(d2 + eps) : d2;
+    T d2, dist;
+    if constexpr (BW) {  // bw2 = tr A_i + tr B_j - 2 sum sigma_k;  D = sqrt(|bw2| + eps) | bw2
+      const double tr = p.trA[i < p.nA ? i : p.nA - 1] + p.trB[jc];
+      d2 = T(tr) - T(2) * group_sum<G>(part);
+      dist = p.sqrt_mode ? R::sqrt_(R::abs_(d2) + eps) : d2;
+    } else {
+      d2 = scale * group_sum<G>(part);
+      dist = p.sqrt_mode ? R::sqrt_(d2 + eps) : d2;
+    }
     const int io = i;
     T w = T(0);
     if (valid) {
@@ -1516,11 +1546,28 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
       const T dd = p.sqrt_mode ? T(0.5) / dist : T(1);
       const T coef = valid ? w * dd * scale * T(2) : T(0);
       T coefA[CPL], coefB[CPL];
+      if constexpr (!BW) {
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
         const T q = coef * loglam[c] / lam[c];
         coefB[c] = -q;
         coefA[c] = q / lam[c];
+      }
+      }
+      T hc = T(0);  // BW: h = w dD/dbw2, the coefficient of the identity terms
+      if constexpr (BW) {
+        // dbw2/dA_i = I - sum_k sigma_k^-3 u~ u~^T  (the OT map T from N(0,A_i) to N(0,B_j)), u~ = R_j^T y_k;
+        // dbw2/dB_j = I - R_j^-1 (sum_k sigma_k^-1 y y^T) R_j^-T  (T^-1): the B side accumulates the bracket, the sandwich and
+        // the identity term follow the slab reduction (finalize_bw_kernel, bw_sandwich_kernel)
+        const T sg = d2 > T(0) ? T(1) : (d2 < T(0) ? T(-1) : T(0));
+        hc = valid ? (p.sqrt_mode ? w * sg * (T(0.5) / dist) : w) : T(0);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          const bool real_col = c * G + g < p.m;
+          const T rs = real_col ? T(1) / lam[c] : T(0);
+          coefB[c] = -(hc * rs);
+          coefA[c] = coefB[c] * (rs * rs);
+        }
       }
       if constexpr (EIG_BWD) {
         // backward of the eigenvalues themselves: d lambda_k/dA = u u^T = u~ u~^T / lambda_k,
@@ -1537,6 +1584,15 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
           coefB[c] = -wk;
           coefA[c] = wk / lam[c];
         }
+      }
+      if constexpr (BW) {
+        // B side on y itself, before the back-transform: the slab row accumulates -h sum sigma^-1 y y^T, i.e. -h (R A R^T)^1/2,
+        // and finalize_bw_kernel / bw_sandwich_kernel apply R_j^-1 (.) R_j^-T once per class (z = R_j^-1 y; a bracket in u~
+        // coordinates would need B_j^-1 on both sides and amplify its float32 rounding by kappa(B)^2 instead of kappa(B))
+        const int lo = lane;
+        T* gb = static_cast<T*>(p.slab_grad) + ((size_t)tile * (TI + tj) + TI + jj) * TRI;
+        const OuterProduct<T, MR, CPL> prodB{x, coefB};
+        tree_reduce_blocks<6, 0, (TRI + 63) / 64, TRI, T>(prodB, lo, [&](int idx, T v) { gb[idx] = v; });
       }
       // u~ = L_j^-T y in place: u~[r] = sum_{q>=r} Linv[q][r] y[q], rows in ascending order
       if (BWD_PRIO & 2) __builtin_amdgcn_s_setprio(1);
@@ -1573,9 +1629,21 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
         const OuterProduct<T, MR, CPL> prodA{x, coefA};
         constexpr int LG = ilog2(G);
         tree_reduce_blocks<LG, 0, (TRI + G - 1) / G, TRI, T>(prodA, lo, [&](int idx, T v) { ga[idx] += v; });
+        if constexpr (!BW) {
         T* gb = static_cast<T*>(p.slab_grad) + ((size_t)tile * (TI + tj) + TI + jj) * TRI;
         const OuterProduct<T, MR, CPL> prodB{x, coefB};
         tree_reduce_blocks<6, 0, (TRI + 63) / 64, TRI, T>(prodB, lo, [&](int idx, T v) { gb[idx] = v; });
+        }
+        if constexpr (BW) {
+          // identity terms: h on the m real diagonal entries of the pair's A-side accumulator (lane g: rows g, g + G, ...).
+          // Those entries were just written by OTHER lanes of the group (the tree reduction's owners): make their LDS
+          // writes visible to the whole wave before the read-modify-write.  Then the wave's sum of h for the B side.
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          for (int r = lo % G; r < p.m; r += G) ga[tri_index(r, r)] += hc;
+          const T hs = wave_sum((lo % G) == 0 ? hc : T(0));
+          if (lo == 0) static_cast<T*>(p.slab_h)[(size_t)tile * tj + jj] = hs;
+        }
       }
 #else
       {  // keep u~ alive so that the back-transform is not optimised away
@@ -1626,6 +1694,22 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
 }
 
 // host-side launcher, instantiated once per configuration in its own translation unit
+template <typename Cfg>
+hipError_t launch_pair_tiles_bw(const PairParams& p, hipStream_t stream) {
+  long n_tiles = 0;
+  for (int bi = 0; bi < p.nbi; ++bi) {
+    int first;
+    n_tiles += shard_tiles_in_row(bi, tiles_in_row(bi, p.nbj, Cfg::TI, p.tj, p.self_mode), p.shard_index,
+                                  p.shard_count, &first);
+  }
+  if (n_tiles == 0) return hipSuccess;
+  using T = typename Cfg::type;
+  hipLaunchKernelGGL((pair_tile_kernel<Cfg, false, true>), dim3((unsigned)n_tiles), dim3(Cfg::THREADS), 0, stream, p,
+                     static_cast<const T*>(p.LT), static_cast<const T*>(p.Linv), static_cast<const T*>(p.W),
+                     static_cast<const T*>(nullptr));
+  return hipGetLastError();
+}
+
 template <typename Cfg>
 hipError_t launch_pair_tiles(const PairParams& p, hipStream_t stream) {
   long n_tiles = 0;

@@ -140,7 +140,7 @@ template <int RS> __device__ __forceinline__ void row_swap_pair(double a, double
   rb = __hiloint2double(ohi, olo);
 }
 
-template <typename Cfg, bool EIG_BWD>
+template <typename Cfg, bool EIG_BWD, bool BW = false>   // BW: as pair_tile_kernel (pair_kernel.hpp)
 __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel_2d(
     const PairParams p, const typename Cfg::type* __restrict__ LT,
     const typename Cfg::type* __restrict__ LinvAll, const typename Cfg::type* __restrict__ Wt,
@@ -207,6 +207,9 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
       if (p.want_grad) {
         T* gbz = static_cast<T*>(p.slab_grad) + ((size_t)tile * (TI + tj) + TI + jj) * TRI;
         for (int k = lane; k < TRI; k += 64) gbz[k] = T(0);
+        if constexpr (BW) {
+          if (lane == 0) static_cast<T*>(p.slab_h)[(size_t)tile * tj + jj] = T(0);
+        }
       }
       continue;
     }
@@ -350,12 +353,13 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
       for (int r = 0; r < MRL; ++r) a = R::fma_(x[c][r], x[c][r], a);
       a = row_total<RS>(a);
       const bool real_col = col < p.m;
-      lam[c] = real_col ? a : T(1);
+      lam[c] = real_col ? (BW ? R::sqrt_(a) : a) : (BW ? T(0) : T(1));  // BW: sigma_k
       loglam[c] = real_col ? R::log_(a) : T(0);
-      part = R::fma_(loglam[c], loglam[c], part);
+      part = BW ? part + lam[c] : R::fma_(loglam[c], loglam[c], part);
     }
-    const T d2 = scale * group_sum<GC>(part);
-    const T dist = p.sqrt_mode ? R::sqrt_(d2 + eps) : d2;
+    // BW: d2 = tr A_i + tr B_j - 2 sum sigma_k (constant conditions: the affine-invariant instantiations are unchanged)
+    const T d2 = BW ? T(p.trA[i < p.nA ? i : p.nA - 1] + p.trB[jc]) - T(2) * group_sum<GC>(part) : scale * group_sum<GC>(part);
+    const T dist = p.sqrt_mode ? R::sqrt_((BW ? R::abs_(d2) : d2) + eps) : d2;
     const int io = i;
     T w = T(0);
     if (valid) {
@@ -398,6 +402,18 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
         coefB[c] = -qq;
         coefA[c] = qq / lam[c];
       }
+      T hc = T(0);
+      if constexpr (BW) {  // coefficients as pair_tile_kernel's
+        const T sg = d2 > T(0) ? T(1) : (d2 < T(0) ? T(-1) : T(0));
+        hc = valid ? (p.sqrt_mode ? w * sg * (T(0.5) / dist) : w) : T(0);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          const bool real_col = c * GC + g < p.m;
+          const T rs = real_col ? T(1) / lam[c] : T(0);
+          coefB[c] = -(hc * rs);
+          coefA[c] = coefB[c] * (rs * rs);
+        }
+      }
       if constexpr (EIG_BWD) {
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
@@ -426,6 +442,13 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
           if (2 * q + 1 < MR) xf[c2][(2 * q + 1 < MR) ? 2 * q + 1 : 0] = rb;
         }
       }
+      if constexpr (BW) {  // B side on y before the back-transform, as pair_tile_kernel
+        const int lo = lane;
+        T* gb = static_cast<T*>(p.slab_grad) + ((size_t)tile * (TI + tj) + TI + jj) * TRI;
+        const OuterProduct<T, MR, CF> prodB{xf, cBf};
+        const int posB = Map::pos(lo, 6);
+        tree_reduce_blocks_mapped<6, 0, (TRI + 63) / 64, TRI, Map, T>(prodB, lo, posB, [&](int idx, T v) { gb[idx] = v; });
+      }
       // u~ = L_j^-T y in place, rows in ascending order
 #pragma unroll
       for (int r = 0; r < MR; ++r) {
@@ -447,10 +470,20 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
         const OuterProduct<T, MR, CF> prodA{xf, cAf};
         const int posA = Map::pos(lo, LG);
         tree_reduce_blocks_mapped<LG, 0, (TRI + G - 1) / G, TRI, Map, T>(prodA, lo, posA, [&](int idx, T v) { ga[idx] += v; });
+        if constexpr (!BW) {
         T* gb = static_cast<T*>(p.slab_grad) + ((size_t)tile * (TI + tj) + TI + jj) * TRI;
         const OuterProduct<T, MR, CF> prodB{xf, cBf};
         const int posB = Map::pos(lo, 6);
         tree_reduce_blocks_mapped<6, 0, (TRI + 63) / 64, TRI, Map, T>(prodB, lo, posB, [&](int idx, T v) { gb[idx] = v; });
+        }
+        if constexpr (BW) {  // identity terms, as pair_tile_kernel (row lane 0 of the pair only; same wave-wide fence)
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          if (lane_h(lo) == 0)
+            for (int r = lane_g(lo); r < p.m; r += GC) ga[tri_index(r, r)] += hc;
+          const T hs = wave_sum((lane_g(lo) == 0 && lane_h(lo) == 0) ? hc : T(0));
+          if (lo == 0) static_cast<T*>(p.slab_h)[(size_t)tile * tj + jj] = hs;
+        }
       }
     }
   }
@@ -485,6 +518,21 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void pair_tile_kernel
       slab[k] = acc;
     }
   }
+}
+
+template <typename Cfg>
+hipError_t launch_pair_tiles_2d_bw(const PairParams& p, hipStream_t stream) {
+  long n_tiles = 0;
+  for (int bi = 0; bi < p.nbi; ++bi) {
+    int first;
+    n_tiles += shard_tiles_in_row(bi, tiles_in_row(bi, p.nbj, Cfg::TI, p.tj, p.self_mode), p.shard_index, p.shard_count, &first);
+  }
+  if (n_tiles == 0) return hipSuccess;
+  using T = typename Cfg::type;
+  hipLaunchKernelGGL((pair_tile_kernel_2d<Cfg, false, true>), dim3((unsigned)n_tiles), dim3(Cfg::THREADS), 0, stream, p,
+                     static_cast<const T*>(p.LT), static_cast<const T*>(p.Linv), static_cast<const T*>(p.W),
+                     static_cast<const T*>(nullptr));
+  return hipGetLastError();
 }
 
 template <typename Cfg>

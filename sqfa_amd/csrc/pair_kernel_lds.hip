@@ -128,7 +128,8 @@ __global__ __launch_bounds__(256) void cholesky_lds_kernel(const T* __restrict__
 }
 
 // ---- K1L ------------------------------------------------------------------------------------------------------------
-template <typename T, bool EIG_BWD>
+// BW: the Bures-Wasserstein distance (sqfa_bw_pairwise), as pair_tile_kernel's BW (pair_kernel.hpp); LinvAll then holds R_j
+template <typename T, bool EIG_BWD, bool BW = false>
 __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int TI, int MR, const T* __restrict__ LT,
                                                        const T* __restrict__ LinvAll, const T* __restrict__ Wt,
                                                        const T* __restrict__ EWt) {
@@ -164,6 +165,10 @@ __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int T
   if (p.want_grad) {  // every slab row of the tile is defined; entry idx is always handled by thread idx % nt
     for (int row = 0; row < TI + tj; ++row)
       for (int idx = tid; idx < TRI; idx += nt) slab[(size_t)row * TRI + idx] = T(0);
+    if constexpr (BW) {
+      if (tid == 0)
+        for (int jj = 0; jj < tj; ++jj) static_cast<T*>(p.slab_h)[(size_t)tile * tj + jj] = T(0);
+    }
   }
 
   const T tol2 = R::kEps * R::kEps * T(MR);
@@ -190,12 +195,42 @@ __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int T
         for (int k = 0; k < MR; ++k) xc[k] = lt[k];
         for (int r = MR - 1; r >= 0; --r) {
           const T* __restrict__ lr = li + tri_index(r, 0);  // same address in every lane
+          if constexpr (BW && sizeof(T) == 4) {
+            // BW float32: X = R_j F_i accumulated in double -- its rounding enters sum sigma_k directly (at m = 128 the
+            // float32 sum put the distance at 1.3e-5 of the float64 value)
+            double accd = 0.0;
+            for (int k = 0; k <= r; ++k) accd = fma((double)lr[k], (double)xc[k], accd);
+            xc[r] = (T)accd;
+            continue;
+          }
           T acc = T(0);
           for (int k = 0; k <= r; ++k) acc = R::fma_(lr[k], xc[k], acc);
           xc[r] = acc;
         }
       }
       __syncthreads();
+      // BW: |X|_F^2 before the sweeps, in double (s_cA as reduction slots: not written before step 4).  The rotations preserve
+      // it exactly in exact arithmetic; their float32 rounding drifts every column norm alike by ~1e-5 over ~10 sweeps of
+      // MR - 1 steps, which the BW distance (sum sigma_k, not a log) would show directly -- step 3 rescales by the ratio.
+      // The real columns are also scaled by a power of two (exact) to |X|_F^2 ~ m: the rotation test compares squared inner
+      // products with eps^2 MR |x|^2 |y|^2, which underflows float32 for classes of size 1e-6 and stopped the sweeps early.
+      double fro0 = 0.0, xs = 1.0;
+      if constexpr (BW && sizeof(T) == 4) {
+        double v = 0.0;
+        if (tid < m) {
+          const T* xc = X + tid * P;
+          for (int r = 0; r < MR; ++r) v = fma((double)xc[r], (double)xc[r], v);
+        }
+        fro0 = block_sum(v, reinterpret_cast<double*>(s_cA));
+        xs = exp2(rint(-0.5 * log2(fro0 / (double)m)));
+        if (!(xs > 0.0 && xs < 1e30)) xs = 1.0;  // zero / non-finite classes: leave as they are
+        fro0 *= xs * xs;
+        if (tid < m) {
+          T* xc = X + tid * P;
+          for (int r = 0; r < MR; ++r) xc[r] *= (T)xs;
+        }
+        __syncthreads();
+      }
 
       // ---- 2. one-sided Jacobi, round-robin ordering --------------------------------------------------------------
       int sweeps = 0;
@@ -264,13 +299,32 @@ __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int T
         T a = T(0);
         for (int r = 0; r < MR; ++r) a = R::fma_(xc[r], xc[r], a);
         const bool real_col = tid < m;  // identity-padded columns carry no signal
-        const T lam = real_col ? a : T(1);
+        const T lam = real_col ? (BW ? R::sqrt_(a) : a) : (BW ? T(0) : T(1));  // BW: sigma_k
         s_lam[tid] = lam;
         const T ll = real_col ? R::log_(lam) : T(0);
-        part = ll * ll;
+        part = BW ? lam : ll * ll;
       }
-      const T d2 = scale * block_sum(part, s_red);
-      const T dist = p.sqrt_mode ? R::sqrt_(d2 + eps) : d2;
+      double bw_sum = 0.0;  // BW: sum sigma_k in double (s_cA, not yet written for this pair, as the reduction slots)
+      if constexpr (BW) {
+        if constexpr (sizeof(T) == 4) {
+          // the column norms in double, rescaled so that sum |y_k|^2 = |X|_F^2 of the unrotated X (see fro0)
+          double ad = 0.0;
+          if (tid < m) {
+            T* xc = X + tid * P;
+            for (int r = 0; r < MR; ++r) ad = fma((double)xc[r], (double)xc[r], ad);
+            for (int r = 0; r < MR; ++r) xc[r] *= (T)(1.0 / xs);  // back to the true scale (exact) for step 4
+          }
+          const double corr = sqrt(fro0 / block_sum(ad, reinterpret_cast<double*>(s_cA))) / xs;
+          const double sg = tid < m ? sqrt(ad) * corr : 0.0;
+          if (tid < m) s_lam[tid] = (T)sg;
+          bw_sum = block_sum(sg, reinterpret_cast<double*>(s_cA));
+        } else {
+          bw_sum = block_sum((double)part, reinterpret_cast<double*>(s_cA));
+        }
+      }
+      const T d2 = BW ? T(p.trA[i] + p.trB[j] - 2.0 * bw_sum) : scale * block_sum(part, s_red);
+      const T dist = p.sqrt_mode ? R::sqrt_((BW ? R::abs_(d2) : d2) + eps) : d2;
+      if constexpr (BW) __syncthreads();  // every thread has read the reduction slots before step 4 writes s_cA
       T w;
       if (Wt != nullptr) {
         w = Wt[(size_t)i * p.nB + j];
@@ -296,6 +350,28 @@ __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int T
 
       // ---- 4. backward --------------------------------------------------------------------------------------------
       if (!p.want_grad) continue;
+      T hc = T(0);  // BW: h = w dD/dbw2 (the same value in every thread)
+      if constexpr (BW) {
+        const T sg = d2 > T(0) ? T(1) : (d2 < T(0) ? T(-1) : T(0));
+        hc = p.sqrt_mode ? w * sg * (T(0.5) / dist) : w;
+        if (tid == 0) static_cast<T*>(p.slab_h)[(size_t)tile * tj + jj] += hc;
+        // B side on y itself, before the back-transform (pair_tile_kernel): -h sum sigma^-1 y y^T, sandwiched by R_j^-1 after
+        // the slab reduction
+        if (tid < m) s_cB[tid] = -(hc / s_lam[tid]);
+        __syncthreads();
+        T* gbw = slab + (size_t)(TI + jj) * TRI;
+        for (int idx = tid; idx < TRI; idx += nt) {
+          int r = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
+          while (tri_index(r, 0) > idx) --r;
+          while (tri_index(r + 1, 0) <= idx) ++r;
+          const int c = idx - tri_index(r, 0);
+          if (r >= m) continue;
+          T sb = T(0);
+          for (int k = 0; k < m; ++k) sb = R::fma_(X[k * P + r] * X[k * P + c], s_cB[k], sb);
+          gbw[idx] += sb;
+        }
+        __syncthreads();  // y is read before the back-transform overwrites it
+      }
       if (tid < m) {
         const T lam = s_lam[tid];
         T cA, cB;
@@ -310,6 +386,12 @@ __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int T
           const T q = w * dd * scale * T(2) * R::log_(lam) / lam;
           cB = -q;
           cA = q / lam;
+        }
+        if constexpr (BW) {
+          // sigma_k^-3 on u~ u~^T (pair_tile_kernel's BW coefficients); the B side is already in the slab
+          const T rs = T(1) / lam;
+          cB = T(0);
+          cA = -(hc * rs) * (rs * rs);
         }
         s_cA[tid] = cA;
         s_cB[tid] = cB;
@@ -336,8 +418,11 @@ __global__ __launch_bounds__(256) void pair_lds_kernel(const PairParams p, int T
           sa = R::fma_(zz, s_cA[k], sa);
           sb = R::fma_(zz, s_cB[k], sb);
         }
+        if constexpr (BW) {
+          if (r == c) sa += hc;  // identity term of the A side
+        }
         ga[idx] += sa;
-        gb[idx] += sb;
+        if constexpr (!BW) gb[idx] += sb;
       }
     }
   }
@@ -363,6 +448,24 @@ hipError_t launch_prologue_t(const void* S, int n, int m, int MR, void* LT, void
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(cholesky_lds_kernel<T>, dim3(n), dim3(256), lds, stream, static_cast<const T*>(S), m, MR,
                      static_cast<T*>(LT), static_cast<T*>(Linv), row_start, p, TI);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_pair_bw_t(const PairParams& p, int TI, int MR, hipStream_t stream) {
+  long n_tiles = 0;
+  for (int bi = 0; bi < p.nbi; ++bi) {
+    int first;
+    n_tiles += shard_tiles_in_row(bi, tiles_in_row(bi, p.nbj, TI, p.tj, p.self_mode), p.shard_index, p.shard_count, &first);
+  }
+  if (n_tiles == 0) return hipSuccess;
+  const int threads = lds_pair_threads(MR);
+  const size_t lds = lds_pair_shared_bytes(MR, sizeof(T));
+  hipError_t e = allow_lds(pair_lds_kernel<T, false, true>, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((pair_lds_kernel<T, false, true>), dim3((unsigned)n_tiles), dim3(threads), lds, stream, p, TI, MR,
+                     static_cast<const T*>(p.LT), static_cast<const T*>(p.Linv), static_cast<const T*>(p.W),
+                     static_cast<const T*>(nullptr));
   return hipGetLastError();
 }
 
@@ -399,6 +502,10 @@ hipError_t launch_lds_prologue(int dtype_f64, const void* S, int n, int m, int M
 
 hipError_t launch_pair_lds(int dtype_f64, const PairParams& p, int TI, int MR, hipStream_t stream) {
   return dtype_f64 ? launch_pair_t<double>(p, TI, MR, stream) : launch_pair_t<float>(p, TI, MR, stream);
+}
+
+hipError_t launch_pair_lds_bw(int dtype_f64, const PairParams& p, int TI, int MR, hipStream_t stream) {
+  return dtype_f64 ? launch_pair_bw_t<double>(p, TI, MR, stream) : launch_pair_bw_t<float>(p, TI, MR, stream);
 }
 
 }  // namespace sqfa

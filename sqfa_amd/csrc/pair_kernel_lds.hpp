@@ -25,5 +25,7 @@ hipError_t launch_lds_prologue(int dtype_f64, const void* S, int n, int m, int M
                                const PairParams& p, int TI, hipStream_t stream);
 // K1L: the pair tiles of this shard (p.tj B classes per tile, TI A classes per tile)
 hipError_t launch_pair_lds(int dtype_f64, const PairParams& p, int TI, int MR, hipStream_t stream);
+// the same tiles for the Bures-Wasserstein distance (sqfa_bw_pairwise: p.Linv holds R_j, p.trA / trB / slab_h set)
+hipError_t launch_pair_lds_bw(int dtype_f64, const PairParams& p, int TI, int MR, hipStream_t stream);
 
 }  // namespace sqfa

@@ -20,29 +20,35 @@ namespace sqfa {
 // ---- per-configuration launchers (defined in pair_inst.hip translation units) -----------
 #define SQFA_DECL_F32(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f32_##MR(const PairParams&, hipStream_t);   \
+  hipError_t launch_pair_bw_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_classeig_f32_##MR(const void*, int, int, double*, double*, hipStream_t);
 #define SQFA_DECL_F64(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f64_##MR(const PairParams&, hipStream_t);   \
+  hipError_t launch_pair_bw_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_classeig_f64_##MR(const void*, int, int, double*, double*, hipStream_t);
 SQFA_CONFIGS_F32(SQFA_DECL_F32)
 SQFA_CONFIGS_F64(SQFA_DECL_F64)
 #define SQFA_DECL_F32S(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f32s_##MR(const PairParams&, hipStream_t);  \
+  hipError_t launch_pair_bw_f32s_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor_f32s_##MR(const PairParams&, hipStream_t);
 SQFA_CONFIGS_F32_SMALL(SQFA_DECL_F32S)
 #define SQFA_DECL_F64S(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f64s_##MR(const PairParams&, hipStream_t);  \
+  hipError_t launch_pair_bw_f64s_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor_f64s_##MR(const PairParams&, hipStream_t);
 SQFA_CONFIGS_F64_SMALL(SQFA_DECL_F64S)
 
 #define SQFA_DECL2D_F32(T, MR, GC, CPL, TJ, WV, RS) \
   hipError_t launch_pair2d_f32_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_pair2d_bw_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor2d_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_classeig2d_f32_##MR(const void*, int, int, double*, double*, hipStream_t);
 #define SQFA_DECL2D_F64(T, MR, GC, CPL, TJ, WV, RS) \
   hipError_t launch_pair2d_f64_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_pair2d_bw_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor2d_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_classeig2d_f64_##MR(const void*, int, int, double*, double*, hipStream_t);
 SQFA_CONFIGS2D_F32(SQFA_DECL2D_F32)
@@ -55,6 +61,7 @@ struct Geometry {
   hipError_t (*eig)(const void*, int, int, double*, double*, hipStream_t) = nullptr;  // per-class eigen-decomposition (regular rows)
   bool mean_metric = false;     // the row's factor pass runs in the metric of the mean class (Cfg::MEAN_METRIC)
   long factor_min_pairs = 0;    // Cfg::FACTOR_MIN_PAIRS: launches with fewer pairs per shard skip the factor pass
+  hipError_t (*launch_bw)(const PairParams&, hipStream_t) = nullptr;  // the row's Bures-Wasserstein tile kernel
 };
 
 // The geometry table: every whole-column row (pair_kernel.hpp) and every 2-D row (pair_kernel_2d.hpp: GC column lanes x 2
@@ -71,12 +78,12 @@ static bool find_geometry(int m, int dtype, long pairs, Geometry* out, int geome
       found = true;
     }
   };
-#define SQFA_ROW_F32(T, MR_, G_, CPL_, TJ_, WV_) consider(SQFA_F32, Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f32_##MR_, launch_factor_f32_##MR_, launch_classeig_f32_##MR_, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS});
-#define SQFA_ROW_F64(T, MR_, G_, CPL_, TJ_, WV_) consider(SQFA_F64, Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f64_##MR_, launch_factor_f64_##MR_, launch_classeig_f64_##MR_, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS});
+#define SQFA_ROW_F32(T, MR_, G_, CPL_, TJ_, WV_) consider(SQFA_F32, Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f32_##MR_, launch_factor_f32_##MR_, launch_classeig_f32_##MR_, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f32_##MR_});
+#define SQFA_ROW_F64(T, MR_, G_, CPL_, TJ_, WV_) consider(SQFA_F64, Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f64_##MR_, launch_factor_f64_##MR_, launch_classeig_f64_##MR_, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f64_##MR_});
 #define SQFA_ROW2D_F32(T, MR_, GC_, CPL_, TJ_, WV_, RS_) \
-  consider(SQFA_F32, Geometry{MR_, 2 * GC_, CPL_, TJ_, 64 / (2 * GC_), WV_, launch_pair2d_f32_##MR_, launch_factor2d_f32_##MR_, launch_classeig2d_f32_##MR_, PairCfg2D<float, MR_, GC_, CPL_, TJ_, WV_, RS_>::MEAN_METRIC, PairCfg2D<float, MR_, GC_, CPL_, TJ_, WV_, RS_>::FACTOR_MIN_PAIRS});
+  consider(SQFA_F32, Geometry{MR_, 2 * GC_, CPL_, TJ_, 64 / (2 * GC_), WV_, launch_pair2d_f32_##MR_, launch_factor2d_f32_##MR_, launch_classeig2d_f32_##MR_, PairCfg2D<float, MR_, GC_, CPL_, TJ_, WV_, RS_>::MEAN_METRIC, PairCfg2D<float, MR_, GC_, CPL_, TJ_, WV_, RS_>::FACTOR_MIN_PAIRS, launch_pair2d_bw_f32_##MR_});
 #define SQFA_ROW2D_F64(T, MR_, GC_, CPL_, TJ_, WV_, RS_) \
-  consider(SQFA_F64, Geometry{MR_, 2 * GC_, CPL_, TJ_, 64 / (2 * GC_), WV_, launch_pair2d_f64_##MR_, launch_factor2d_f64_##MR_, launch_classeig2d_f64_##MR_, PairCfg2D<double, MR_, GC_, CPL_, TJ_, WV_, RS_>::MEAN_METRIC, PairCfg2D<double, MR_, GC_, CPL_, TJ_, WV_, RS_>::FACTOR_MIN_PAIRS});
+  consider(SQFA_F64, Geometry{MR_, 2 * GC_, CPL_, TJ_, 64 / (2 * GC_), WV_, launch_pair2d_f64_##MR_, launch_factor2d_f64_##MR_, launch_classeig2d_f64_##MR_, PairCfg2D<double, MR_, GC_, CPL_, TJ_, WV_, RS_>::MEAN_METRIC, PairCfg2D<double, MR_, GC_, CPL_, TJ_, WV_, RS_>::FACTOR_MIN_PAIRS, launch_pair2d_bw_f64_##MR_});
   SQFA_CONFIGS_F32(SQFA_ROW_F32)
   SQFA_CONFIGS_F64(SQFA_ROW_F64)
   SQFA_CONFIGS2D_F32(SQFA_ROW2D_F32)
@@ -85,11 +92,11 @@ static bool find_geometry(int m, int dtype, long pairs, Geometry* out, int geome
     // same padded size, more lanes per pair
 #define SQFA_ROW_F32S(T, MR_, G_, CPL_, TJ_, WV_)                                                                        \
     if (dtype == SQFA_F32 && best.MR == MR_ && (geometry_mode > 0 || pairs < small_launch_max_pairs(MR_)))                \
-      best = Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f32s_##MR_, launch_factor_f32s_##MR_, best.eig, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS};
+      best = Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f32s_##MR_, launch_factor_f32s_##MR_, best.eig, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f32s_##MR_};
     SQFA_CONFIGS_F32_SMALL(SQFA_ROW_F32S)
 #define SQFA_ROW_F64S(T, MR_, G_, CPL_, TJ_, WV_)                                                                        \
     if (dtype == SQFA_F64 && best.MR == MR_ && (geometry_mode > 0 || pairs < small_launch_max_pairs_f64(MR_)))              \
-      best = Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f64s_##MR_, launch_factor_f64s_##MR_, best.eig, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS};
+      best = Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f64s_##MR_, launch_factor_f64s_##MR_, best.eig, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f64s_##MR_};
     SQFA_CONFIGS_F64_SMALL(SQFA_ROW_F64S)
   }
   if (found) *out = best;
@@ -578,6 +585,179 @@ __global__ __launch_bounds__(SQFA_K2_THREADS) void finalize_kernel(const PairPar
   }
 }
 
+// ---- Bures-Wasserstein kernels (sqfa_bw_pairwise) -------------------------------------------------------------------
+// K0 (B side): per class, in double, the LOWER triangular R with R^T R = S: R = J chol(J S J)^T J (J reverses the index
+// order), written where the affine-invariant path keeps L^-1 (identity padded, packed lower triangle for MR >= 32 as
+// PairCfg::PACK_LINV and the LDS path), R^-1 = J L^-T J (L = chol(J S J)) as m x m doubles (the sandwich of the B-side
+// gradient) and the trace.  trace_only: the trace alone (the A side, whose factor comes from the unchanged Cholesky prologue).
+// One 256-thread workgroup per class; a[m][m+1] + rd[m] doubles of dynamic LDS.  A non-SPD class yields NaN, never a fault.
+template <typename T>
+__global__ __launch_bounds__(256) void bw_prologue_kernel(const T* __restrict__ S, int m, int MR, T* __restrict__ Rout,
+                                                          double* __restrict__ Sinv, double* __restrict__ trace) {
+  extern __shared__ double lds_bw[];
+  const int P = m + 1, c = blockIdx.x, t = threadIdx.x;
+  double* a = lds_bw;           // a[r * P + k]
+  double* rd = lds_bw + m * P;  // 1 / L[k][k], then scratch
+  const T* s = S + (size_t)c * m * m;
+  if (trace != nullptr) {
+    if (t < 64) {  // one wave, fixed order: reproducible
+      double v = 0.0;
+      for (int k = t; k < m; k += 64) v += (double)s[(size_t)k * m + k];
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (t == 0) trace[c] = v;
+    }
+  }
+  if (Rout == nullptr && Sinv == nullptr) return;
+  for (int idx = t; idx < m * m; idx += 256) {
+    const int r = idx / m, k = idx % m;
+    a[r * P + k] = (double)s[(size_t)(m - 1 - r) * m + (m - 1 - k)];
+  }
+  __syncthreads();
+  for (int k = 0; k < m; ++k) {  // right-looking elimination on the unscaled columns (cholesky_kernel)
+    const double akk = a[k * P + k];
+    double rk = __builtin_amdgcn_rcp(akk);
+    rk = rk * (2.0 - akk * rk);
+    rk = rk * (2.0 - akk * rk);
+    if (!(akk > 0.0)) rk = __builtin_nan("");
+    const int n = m - k - 1;
+    for (int e = t; e < n * n; e += 256) {
+      const int r = k + 1 + e / n, c2 = k + 1 + e % n;
+      if (c2 <= r) a[r * P + c2] -= a[r * P + k] * a[c2 * P + k] * rk;
+    }
+    __syncthreads();
+  }
+  for (int k = t; k < m; k += 256) rd[k] = fast_rsqrt(a[k * P + k]);
+  __syncthreads();
+  for (int e = t; e < m * m; e += 256) {
+    const int r = e / m, k = e % m;
+    if (k <= r) a[r * P + k] *= rd[k];  // a: L = chol(J S J), lower
+  }
+  __syncthreads();
+  if (Rout != nullptr) {  // R[r][k] = L[m-1-k][m-1-r], k <= r
+    const bool packed = MR >= 32;
+    T* R = Rout + (size_t)c * (packed ? MR * (MR + 1) / 2 : MR * MR);
+    for (int idx = t; idx < MR * MR; idx += 256) {
+      const int r = idx / MR, k = idx % MR;
+      if (packed && k > r) continue;
+      const double v = (r < m && k < m) ? (k <= r ? a[(m - 1 - k) * P + (m - 1 - r)] : 0.0) : (r == k ? 1.0 : 0.0);
+      R[packed ? tri_index(r, k) : idx] = (T)v;
+    }
+  }
+  if (Sinv == nullptr) return;
+  // X = L^-1 in place: strict lower triangle stored transposed in the upper triangle (X[r][q] at a[q][r]), diagonal in rd
+  {
+    const int col = t >> 1, part = t & 1;
+    for (int r = 1; r < m; ++r) {
+      double acc = 0.0;
+      if (col < r) {
+        for (int k = col + part; k < r; k += 2) acc += a[r * P + k] * (k == col ? rd[col] : a[col * P + k]);
+      }
+      acc += __shfl_xor(acc, 1, 64);
+      if (part == 0 && col < r) a[col * P + r] = -acc * rd[r];
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  __syncthreads();
+  // R^-1 = J X^T J: R^-1[r][q] = X[m-1-q][m-1-r] (lower triangular, q <= r)
+  double* si = Sinv + (size_t)c * m * m;
+  for (int idx = t; idx < m * m; idx += 256) {
+    const int r = idx / m, q = idx % m;
+    const int u = m - 1 - q, v = m - 1 - r;  // X[u][v], u >= v
+    si[idx] = q > r ? 0.0 : (u == v ? rd[u] : a[v * P + u]);
+  }
+}
+
+// K2 of the gradient (BW): the A-side slab rows of every class (identity terms included) -> gradA, and the B-side rows
+// -> G (m x m doubles, the bracket of the B-side gradient) with the sums of slab_h -> hsum.  Self mode: A side and B side of
+// one class are reduced SEPARATELY (only the B side is sandwiched).  Workgroup b: class b / BPC (A classes first, then the
+// nBeff B classes), 256 consecutive lower-triangle entries; every thread sums its entry over the owned tiles in the
+// enumeration order of finalize_kernel, four partial sums: fixed order, bitwise reproducible.
+template <typename T>
+__global__ __launch_bounds__(256) void finalize_bw_kernel(const PairParams p, int TI, int TJ, int MR, T* __restrict__ gradA,
+                                                          double* __restrict__ G, double* __restrict__ hsum) {
+  const int TRI = MR * (MR + 1) / 2, BPC = (TRI + 255) / 256;
+  const int b = blockIdx.x, cls = b / BPC, idx = (b % BPC) * 256 + threadIdx.x;
+  const bool a_side = cls < p.nA;
+  const int c = a_side ? cls : cls - p.nA;
+  const T* slab = static_cast<const T*>(p.slab_grad);
+  const size_t tile_stride = (size_t)(TI + TJ) * TRI;
+  const int N = p.shard_count;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double hacc = 0.0;
+  const bool h_thread = !a_side && b % BPC == 0 && threadIdx.x == 0;
+  if (a_side) {
+    const int bi_a = c / TI, pi = c % TI;
+    int first;
+    const int n_a = shard_tiles_in_row(bi_a, tiles_in_row(bi_a, p.nbj, TI, TJ, p.self_mode), p.shard_index, N, &first);
+    if (idx < TRI)
+      for (int q = 0; q < n_a; ++q) acc[q & 3] += (double)slab[(size_t)(p.row_start[bi_a] + q) * tile_stride + (size_t)pi * TRI + idx];
+  } else {
+    const int bj_b = c / TJ, pj = c % TJ;
+    const int first_b = ((p.shard_index - bj_b) % N + N) % N;
+    const int n_b = p.nbi > first_b ? (p.nbi - 1 - first_b) / N + 1 : 0;
+    for (int k = 0; k < n_b; ++k) {
+      const int bi = first_b + k * N;
+      if (p.self_mode && (bi * TI + TI - 1 <= bj_b * TJ)) continue;  // tile_processed
+      int slot = p.row_start[bi] + bj_b;
+      if (N > 1) slot = p.row_start[bi] + (bj_b - ((p.shard_index - bi) % N + N) % N) / N;
+      if (idx < TRI) acc[k & 3] += (double)slab[(size_t)slot * tile_stride + (size_t)(TI + pj) * TRI + idx];
+      if (h_thread) hacc += (double)static_cast<const T*>(p.slab_h)[(size_t)slot * TJ + pj];
+    }
+    if (h_thread) hsum[c] = hacc;
+  }
+  if (idx >= TRI) return;
+  int r = 0;
+  while ((r + 1) * (r + 2) / 2 <= idx) ++r;
+  const int cc = idx - r * (r + 1) / 2;
+  if (r >= p.m) return;
+  const double tot = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  const int m = p.m;
+  if (a_side) {
+    if (gradA != nullptr) {
+      gradA[(size_t)c * m * m + (size_t)r * m + cc] = (T)tot;
+      gradA[(size_t)c * m * m + (size_t)cc * m + r] = (T)tot;
+    }
+  } else {
+    G[(size_t)c * m * m + (size_t)r * m + cc] = tot;
+    G[(size_t)c * m * m + (size_t)cc * m + r] = tot;
+  }
+}
+
+// B-side gradient: grad_j = hsum_j I + R_j^-1 G_j R_j^-T (G_j = -sum h sigma^-1 y y^T reduced), in double; one workgroup
+// per class, W = R^-1 G through the workspace.  accumulate: self mode adds it to the A-side gradient of the same class.
+template <typename T>
+__global__ __launch_bounds__(256) void bw_sandwich_kernel(int m, const double* __restrict__ Sinv, const double* __restrict__ G,
+                                                          double* __restrict__ W, const double* __restrict__ hsum,
+                                                          T* __restrict__ out, int accumulate) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  const double* si = Sinv + (size_t)c * m * m;
+  const double* g = G + (size_t)c * m * m;
+  double* w = W + (size_t)c * m * m;
+  for (int idx = t; idx < m * m; idx += 256) {
+    const int r = idx / m, q = idx % m;
+    double acc = 0.0;
+    for (int k = 0; k < m; ++k) acc += si[r * m + k] * g[k * m + q];
+    w[idx] = acc;
+  }
+  __syncthreads();
+  const double hs = hsum[c];
+  T* o = out + (size_t)c * m * m;
+  for (int idx = t; idx < m * m; idx += 256) {
+    const int r = idx / m, q = idx % m;
+    if (q > r) continue;
+    double acc = r == q ? hs : 0.0;
+    for (int k = 0; k < m; ++k) acc += w[r * m + k] * si[q * m + k];
+    if (accumulate) {
+      o[r * m + q] = (T)((double)o[r * m + q] + acc);
+      if (q != r) o[q * m + r] = (T)((double)o[q * m + r] + acc);
+    } else {
+      o[r * m + q] = (T)acc;
+      o[q * m + r] = (T)acc;
+    }
+  }
+}
+
 // ---- per-class matrix functions f(S) = Q f(Lambda) Q^T and their backward -----------------------------------------------
 // (spd_log / spd_sqrt of the reference, src/sqfa/linalg.py:121-141, 165-183: torch.linalg.eigh + einsum there.)
 // One 256-thread workgroup per class; Q (m x m, eigenvectors as columns) and the small intermediates live in LDS as
@@ -1021,6 +1201,227 @@ static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, in
   return SQFA_OK;
 }
 
+// ---- sqfa_bw_pairwise ------------------------------------------------------------------------------------------------
+// Workspace: the affine-invariant layout of the same problem (factors, slab, slot table), then
+//   traces (nA + nB doubles) | slab_h (one value per B-side slab row: at most nbi (nB + TJ)) | hsum (nB doubles) |
+//   R_j^-1, G_j, W_j (3 nB m^2 doubles)
+struct BwExtra {
+  size_t off_tr, off_h, off_hsum, off_sinv, off_g, off_w, total;
+};
+static BwExtra bw_extra(size_t base, int nA, int nBeff, int m, int nbi, int TJ) {
+  BwExtra x;
+  size_t o = base;
+  x.off_tr = o;   o = align_up(o + (size_t)(nA + nBeff) * sizeof(double));
+  x.off_h = o;    o = align_up(o + (size_t)nbi * (nBeff + TJ) * sizeof(double));
+  x.off_hsum = o; o = align_up(o + (size_t)nBeff * sizeof(double));
+  x.off_sinv = o; o = align_up(o + (size_t)nBeff * m * m * sizeof(double));
+  x.off_g = o;    o = align_up(o + (size_t)nBeff * m * m * sizeof(double));
+  x.off_w = o;    o = align_up(o + (size_t)nBeff * m * m * sizeof(double));
+  x.total = o;
+  return x;
+}
+// widest tiling of a problem: (tile rows, widest tile width); slab_h needs nbi (nB + TJ) entries for any narrower width
+static void bw_tiles(int nA, int nBeff, int m, int dtype, int self_mode, int* nbi, int* TJ) {
+  if (m > kRegMaxDim) {
+    const LdsTiling t = lds_tiling(nA, nBeff, m, self_mode);
+    *nbi = (nA + t.TI - 1) / t.TI;
+    *TJ = t.TJ;
+    return;
+  }
+  // the rows of any geometry policy: the smallest TI and the largest TJ among them
+  Geometry g1, g2;
+  find_geometry(m, dtype, -1, &g1, -1);
+  find_geometry(m, dtype, 0, &g2, 1);
+  const int TI = std::min(g1.TI, g2.TI);
+  *nbi = (nA + TI - 1) / TI;
+  *TJ = std::max(g1.TJ, g2.TJ);
+}
+
+static int bw_impl(const void* A, int nA, const void* B, int nB, int m, int dtype, double eps, int sqrt_mode,
+                   const void* pair_weights, double uniform_weight, int shard_index, int shard_count, void* loss_out,
+                   void* gradA_out, void* gradB_out, void* dist_out, int* nonfinite_out, void* workspace,
+                   size_t workspace_bytes, void* stream_, const sqfa_airm_options* options) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  auto clamp = [](int v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); };
+  const int geometry_mode = options ? clamp(options->geometry_policy) : 0;
+  const int factor_mode = options ? clamp(options->class_factor_policy) : 0;
+  g_last_error[0] = 0;
+  if (A == nullptr || nA < 1 || m < 1 || nB < 0 || workspace == nullptr) return fail(SQFA_ERR_BAD_ARGUMENT, "null/size argument", hipSuccess);
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return fail(SQFA_ERR_BAD_ARGUMENT, "dtype", hipSuccess);
+  if ((B == nullptr) != (nB == 0)) return fail(SQFA_ERR_BAD_ARGUMENT, "B and nB disagree", hipSuccess);
+  if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail(SQFA_ERR_BAD_ARGUMENT, "shard", hipSuccess);
+  const bool self_mode = (B == nullptr);
+  if (self_mode && nA < 2) return fail(SQFA_ERR_BAD_ARGUMENT, "self mode needs at least two classes", hipSuccess);
+  if (m > kLdsMaxDim) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
+  const int nBeff = self_mode ? nA : nB;
+  const int f64 = dtype == SQFA_F64 ? 1 : 0;
+  const bool lds = m > kRegMaxDim;
+
+  Geometry g;
+  LdsTiling lt{};
+  int TI, tj, MR;
+  WorkspaceLayout w;
+  if (lds) {
+    lt = lds_tiling(nA, nBeff, m, self_mode ? 1 : 0);
+    TI = lt.TI;
+    tj = lt.TJ;
+    MR = lt.MR;
+    w = layout_lds(nA, nBeff, lt, esz, self_mode ? 1 : 0, shard_count);
+  } else {
+    if (!find_geometry(m, dtype, pair_count(nA, nB, shard_count), &g, geometry_mode) || g.launch_bw == nullptr)
+      return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+    TI = g.TI;
+    MR = g.MR;
+    tj = choose_tile_width(nA, nBeff, g, self_mode ? 1 : 0, shard_count);
+    w = layout(nA, nBeff, g, esz, self_mode ? 1 : 0, tj, shard_count);
+  }
+  int nbi_max, TJ_max;
+  bw_tiles(nA, nBeff, m, dtype, self_mode ? 1 : 0, &nbi_max, &TJ_max);
+  const BwExtra x = bw_extra(w.total, nA, nBeff, m, nbi_max, TJ_max);
+  if (workspace_bytes < x.total) return fail(SQFA_ERR_WORKSPACE, "workspace too small", hipSuccess);
+  char* ws = static_cast<char*>(workspace);
+  double* tr = reinterpret_cast<double*>(ws + x.off_tr);
+
+  PairParams p;
+  memset(&p, 0, sizeof(p));
+  p.LT = ws + w.off_lt;
+  p.Linv = ws + w.off_linv;
+  p.W = pair_weights;
+  p.slab_grad = ws + w.off_slab;
+  p.slab_loss = ws + w.off_loss;
+  p.slab_flag = reinterpret_cast<int*>(ws + w.off_flag);
+  p.row_start = reinterpret_cast<int*>(ws + w.off_rows);
+  p.dist_out = dist_out;
+  p.sweep_counter = options ? options->sweep_counter : nullptr;
+  p.nA = nA;
+  p.nB = nBeff;
+  p.m = m;
+  p.self_mode = self_mode ? 1 : 0;
+  p.sqrt_mode = sqrt_mode ? 1 : 0;
+  p.want_grad = gradA_out != nullptr ? 1 : 0;
+  p.shard_index = shard_index;
+  p.shard_count = shard_count;
+  p.nbi = (nA + TI - 1) / TI;
+  p.nbj = (nBeff + tj - 1) / tj;
+  p.tj = tj;
+  p.factor_mode = lds ? -1 : factor_mode;
+  p.scale = 1.0;
+  p.eps = eps;
+  p.uniform_weight = uniform_weight;
+  p.scale_f = 1.0f;
+  p.eps_f = (float)eps;
+  p.uniform_weight_f = (float)uniform_weight;
+  p.trA = tr;
+  p.trB = self_mode ? tr : tr + nA;
+  p.slab_h = ws + x.off_h;
+
+  // K0: A-side factors (the affine-invariant prologue; its first launch writes the slab slot table) ...
+  hipError_t e = hipSuccess;
+  if (lds) {
+    e = launch_lds_prologue(f64, A, nA, m, MR, ws + w.off_lt, nullptr, p.row_start, p, TI, stream);
+  } else {
+    auto chol = [&](auto zero) {
+      using T = decltype(zero);
+      const T* sp = static_cast<const T*>(A);
+      T* ltp = static_cast<T*>(const_cast<void*>(p.LT));
+      if (m <= 16) hipLaunchKernelGGL((cholesky_kernel<T, 16>), dim3(nA), dim3(256), 0, stream, sp, m, MR, ltp, (T*)nullptr, p.row_start, p, TI);
+      else if (m <= 32) hipLaunchKernelGGL((cholesky_kernel<T, 32>), dim3(nA), dim3(256), 0, stream, sp, m, MR, ltp, (T*)nullptr, p.row_start, p, TI);
+      else hipLaunchKernelGGL((cholesky_kernel<T, 64>), dim3(nA), dim3(256), 0, stream, sp, m, MR, ltp, (T*)nullptr, p.row_start, p, TI);
+    };
+    if (dtype == SQFA_F32) chol(0.0f); else chol(0.0);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "cholesky_kernel", e);
+  // ... and the BW prologue: R_j, R_j^-1 and traces of the B classes, traces of the A classes
+  {
+    const size_t lds_bytes = ((size_t)m * (m + 1) + m) * sizeof(double);
+    double* sinv = reinterpret_cast<double*>(ws + x.off_sinv);
+    auto launch = [&](auto zero, const void* S, int n, void* R, double* si, double* trace) {
+      using T = decltype(zero);
+      if (lds_bytes > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bw_prologue_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      hipLaunchKernelGGL(bw_prologue_kernel<T>, dim3(n), dim3(256), lds_bytes, stream, static_cast<const T*>(S), m, MR,
+                         static_cast<T*>(R), si, trace);
+    };
+    void* rslot = ws + w.off_linv;
+    if (dtype == SQFA_F32) {
+      if (self_mode) launch(0.0f, A, nA, rslot, sinv, tr);
+      else { launch(0.0f, A, nA, nullptr, nullptr, tr); launch(0.0f, B, nB, rslot, sinv, tr + nA); }
+    } else {
+      if (self_mode) launch(0.0, A, nA, rslot, sinv, tr);
+      else { launch(0.0, A, nA, nullptr, nullptr, tr); launch(0.0, B, nB, rslot, sinv, tr + nA); }
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "bw_prologue_kernel", e);
+  }
+  if (!lds && g.factor != nullptr) {  // K0b on the A-side factors (plain metric: mean_metric_policy does not apply here)
+    e = g.factor(p, stream);
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "class_factor_kernel", e);
+  }
+
+  // K1: pair tiles
+  EventPair ev{};
+  bool prof = g_profile.load();
+  if (prof) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) prof = false;
+  }
+  if (prof) {
+    (void)hipEventCreate(&ev.a);
+    (void)hipEventCreate(&ev.b);
+    (void)hipEventRecord(ev.a, stream);
+  }
+  e = lds ? launch_pair_lds_bw(f64, p, TI, MR, stream) : g.launch_bw(p, stream);
+  if (prof) {
+    (void)hipEventRecord(ev.b, stream);
+    std::lock_guard<std::mutex> lock(g_events_mutex);
+    g_events.push_back(ev);
+  }
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "pair_tile_kernel (Bures-Wasserstein)", e);
+
+  // K2: loss, flags and the diagonal of dist_out through finalize_kernel (its class blocks return at once without
+  // want_grad), then the gradient reduction and the B-side sandwich
+  {
+    PairParams q = p;
+    q.want_grad = 0;
+    const int k2_tri = MR * (MR + 1) / 2;
+    const int k2_blocks = (nA + (self_mode ? 0 : nB)) * (!lds && k2_tri <= 256 ? 1 : (k2_tri + 127) / 128) + 1;  // the last one works
+    if (dtype == SQFA_F32)
+      hipLaunchKernelGGL(finalize_kernel<float>, dim3(k2_blocks), dim3(SQFA_K2_THREADS), 0, stream, q, TI, tj, MR, (float*)nullptr,
+                         (float*)nullptr, static_cast<float*>(loss_out), nonfinite_out);
+    else
+      hipLaunchKernelGGL(finalize_kernel<double>, dim3(k2_blocks), dim3(SQFA_K2_THREADS), 0, stream, q, TI, tj, MR, (double*)nullptr,
+                         (double*)nullptr, static_cast<double*>(loss_out), nonfinite_out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_kernel", e);
+  }
+  if (p.want_grad) {
+    const int TRI = MR * (MR + 1) / 2, BPC = (TRI + 255) / 256;
+    double* G = reinterpret_cast<double*>(ws + x.off_g);
+    double* W = reinterpret_cast<double*>(ws + x.off_w);
+    double* hs = reinterpret_cast<double*>(ws + x.off_hsum);
+    const double* sinv = reinterpret_cast<const double*>(ws + x.off_sinv);
+    void* outB = self_mode ? gradA_out : gradB_out;
+    if (dtype == SQFA_F32) {
+      hipLaunchKernelGGL(finalize_bw_kernel<float>, dim3((nA + nBeff) * BPC), dim3(256), 0, stream, p, TI, tj, MR,
+                         static_cast<float*>(gradA_out), G, hs);
+      if (outB != nullptr)
+        hipLaunchKernelGGL(bw_sandwich_kernel<float>, dim3(nBeff), dim3(256), 0, stream, m, sinv, G, W, hs,
+                           static_cast<float*>(outB), self_mode ? 1 : 0);
+    } else {
+      hipLaunchKernelGGL(finalize_bw_kernel<double>, dim3((nA + nBeff) * BPC), dim3(256), 0, stream, p, TI, tj, MR,
+                         static_cast<double*>(gradA_out), G, hs);
+      if (outB != nullptr)
+        hipLaunchKernelGGL(bw_sandwich_kernel<double>, dim3(nBeff), dim3(256), 0, stream, m, sinv, G, W, hs,
+                           static_cast<double*>(outB), self_mode ? 1 : 0);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_bw_kernel", e);
+  }
+  return SQFA_OK;
+}
+
 size_t sqfa_airm_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy) {
   int ti, tj, nbi, nbj, mr;
   if (shard_count < 1 || sqfa_airm_tiling(nA, nB, m, dtype, &ti, &tj, &nbi, &nbj, &mr) != SQFA_OK) return 0;
@@ -1065,6 +1466,32 @@ int sqfa_airm_eigenvalues_backward(const void* A, int nA, const void* B, int nB,
   }
   return pairwise_impl(A, nA, B, nB, m, dtype, 1.0, 0.0, 0, nullptr, 0.0, 0, 1, nullptr, gradA_out, gradB_out,
                        nullptr, nullptr, nullptr, workspace, workspace_bytes, stream_, eig_weights, options);
+}
+
+size_t sqfa_bw_workspace_bytes(int nA, int nB, int m, int dtype) {
+  const size_t base = sqfa_airm_workspace_bytes(nA, nB, m, dtype);
+  if (base == 0) return 0;
+  const int nBeff = nB == 0 ? nA : nB;
+  int nbi, TJ;
+  bw_tiles(nA, nBeff, m, dtype, nB == 0 ? 1 : 0, &nbi, &TJ);
+  return bw_extra(align_up(base), nA, nBeff, m, nbi, TJ).total;
+}
+
+size_t sqfa_bw_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy) {
+  const size_t base = sqfa_airm_workspace_bytes_sharded(nA, nB, m, dtype, shard_count, geometry_policy);
+  if (base == 0) return 0;
+  const int nBeff = nB == 0 ? nA : nB;
+  int nbi, TJ;
+  bw_tiles(nA, nBeff, m, dtype, nB == 0 ? 1 : 0, &nbi, &TJ);
+  return bw_extra(align_up(base), nA, nBeff, m, nbi, TJ).total;
+}
+
+int sqfa_bw_pairwise(const void* A, int nA, const void* B, int nB, int m, int dtype, double eps, int sqrt_mode,
+                     const void* pair_weights, double uniform_weight, int shard_index, int shard_count, void* loss_out,
+                     void* gradA_out, void* gradB_out, void* dist_out, int* nonfinite_out, void* workspace,
+                     size_t workspace_bytes, void* stream_, const sqfa_airm_options* options) {
+  return bw_impl(A, nA, B, nB, m, dtype, eps, sqrt_mode, pair_weights, uniform_weight, shard_index, shard_count, loss_out,
+                 gradA_out, gradB_out, dist_out, nonfinite_out, workspace, workspace_bytes, stream_, options);
 }
 
 size_t sqfa_spd_function_workspace_bytes(int n, int m, int dtype) {

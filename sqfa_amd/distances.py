@@ -64,19 +64,20 @@ def _pair_matrix(A, B, scale, sqrt_mode):
 
 
 # marks the callables the fused closure path may replace by a single loss+grad launch:
-# name -> (input kind, scale, sqrt_mode)
+# name -> (input kind, scale, sqrt_mode, pair metric)   metric: "airm" (sqfa_airm_pairwise) | "bw" (sqfa_bw_pairwise,
+# registered by sqfa_amd.transport)
 _FUSED = {}
 
 
-def _fusable(kind, scale, sqrt_mode):
+def _fusable(kind, scale, sqrt_mode, metric="airm"):
     def deco(fn):
-        _FUSED[fn] = (kind, scale, sqrt_mode)
+        _FUSED[fn] = (kind, scale, sqrt_mode, metric)
         return fn
     return deco
 
 
 def fused_spec(fn):
-    """(kind, scale, sqrt_mode) if `fn` is one of the native affine-invariant operators."""
+    """(kind, scale, sqrt_mode, metric) if `fn` is one of the native pair operators the fused closure evaluates."""
     return _FUSED.get(fn)
 
 

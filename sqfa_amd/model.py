@@ -180,7 +180,7 @@ class SecondMomentsSQFA(nn.Module):
         if not self._has_fused_closure():
             return None
         spec = distances.fused_spec(self.distance_fun)
-        _, scale, sqrt_mode = spec
+        scale, sqrt_mode, metric = spec[1], spec[2], spec[3]
         single = self._single_node_inputs(prepared)
         if single is not None:
             raw, scatters, means, sphere = single
@@ -191,9 +191,10 @@ class SecondMomentsSQFA(nn.Module):
                 shard, reducer = self.pair_shard.shard, self.pair_shard.reduce
             noise = self._noise_scalar()
             if noise is None:
-                return self._fused_closure_loss_chain(prepared, scale, sqrt_mode)
-            return _native.FusedClosure.apply(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere)
-        return self._fused_closure_loss_chain(prepared, scale, sqrt_mode)
+                return self._fused_closure_loss_chain(prepared, scale, sqrt_mode, metric)
+            return _native.FusedClosure.apply(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere,
+                                              metric)
+        return self._fused_closure_loss_chain(prepared, scale, sqrt_mode, metric)
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once
@@ -211,7 +212,7 @@ class SecondMomentsSQFA(nn.Module):
         self._noise_cache = (key, value)
         return value
 
-    def _fused_closure_loss_chain(self, prepared, scale, sqrt_mode):
+    def _fused_closure_loss_chain(self, prepared, scale, sqrt_mode, metric="airm"):
         """The same loss as a chain of autograd nodes (parametrization -> projection -> noise ->
         [embedding] -> PairwiseLoss): any parametrization, class-sharded statistics, odd filter counts."""
         S = self._fused_input(prepared)
@@ -222,7 +223,7 @@ class SecondMomentsSQFA(nn.Module):
         shard, reducer = (0, 1), None
         if self.pair_shard is not None:
             shard, reducer = self.pair_shard.shard, self.pair_shard.reduce
-        return _native.PairwiseLoss.apply(S, scale, distances.EPSILON, sqrt_mode, weight, shard, reducer)
+        return _native.PairwiseLoss.apply(S, scale, distances.EPSILON, sqrt_mode, weight, shard, reducer, metric)
 
     def _sync_gradients(self):
         """Called by the fitting loop after backward: sums the filter gradient over class shards."""

@@ -314,6 +314,38 @@ int sqfa_gauss_pair_terms(const void *muA, const void *covA, int nA, const void 
                           void *gmuA_out, void *gcovA_out, void *stream);
 
 /*
+ * Fused closure loss of the Gaussian pair distances: for the n classes N(mu_c, Sigma_c), with Q_ij and LD_ij as above,
+ * ld_c = log det Sigma_c and Bh_ij = Q_ij/8 + (LD_ij - (ld_i + ld_j)/2)/2,
+ *     kind SQFA_GAUSS_BHATTACHARYYA   D_ij = Bh_ij
+ *          SQFA_GAUSS_HELLINGER       D_ij = sqrt(1 - exp(-Bh_ij) + eps)
+ *          SQFA_GAUSS_MAHALANOBIS_SQ  D_ij = Q_ij
+ *          SQFA_GAUSS_MAHALANOBIS     D_ij = sqrt(Q_ij + eps)
+ *     loss = uniform_weight * sum_{i>j} D_ij      (uniform_weight = -1/P, P = n(n-1)/2: the reference's -mean)
+ * together with its gradient wrt mu and Sigma, in one pass over the pairs: the same pair kernels as
+ * sqfa_gauss_pair_terms in their fused mode (the distance and its partial derivatives are formed the moment a pair is
+ * factorised; no (n,n) matrix is stored unless dist_out is given, no pair is factorised twice), after a per-class
+ * pre-pass for ld_c (Bhattacharyya / Hellinger only) and before a one-workgroup reduction of the per-class partial
+ * losses and counters.  No float atomics anywhere: results are bitwise reproducible.
+ *   mu (n,m), cov (n,m,m): row-major, dtype; n >= 2, m <= 64
+ *   loss_out (1) dtype or NULL; gmu_out (n,m) and gcov_out (n,m,m, full symmetric matrices): both or neither (NULL, NULL =
+ *   forward only); dist_out (n,n) or NULL: D_ij, both triangles, the diagonal as the reference gives it (0, or
+ *   sqrt(eps) for the two square-root kinds); nonfinite_out (2) int32 or NULL: {#NaN, #inf} among the pairs i > j
+ *   (a mean covariance that is not positive definite yields NaN and is counted, never a fault)
+ *   workspace: sqfa_gauss_pairwise_workspace_bytes(n, m, dtype) bytes (0 = shape or dtype not supported)
+ * Returns SQFA_ERR_BAD_ARGUMENT (null mu / cov, n < 2, dtype, kind, exactly one of gmu_out / gcov_out),
+ * SQFA_ERR_UNSUPPORTED_M (m > 64), SQFA_ERR_WORKSPACE.
+ */
+#define SQFA_GAUSS_BHATTACHARYYA  0
+#define SQFA_GAUSS_HELLINGER      1
+#define SQFA_GAUSS_MAHALANOBIS_SQ 2
+#define SQFA_GAUSS_MAHALANOBIS    3
+size_t sqfa_gauss_pairwise_workspace_bytes(int n, int m, int dtype);
+int sqfa_gauss_pairwise_loss(const void *mu, const void *cov, int n, int m, int dtype, int kind,
+                             double eps, double uniform_weight,
+                             void *loss_out, void *gmu_out, void *gcov_out, void *dist_out, int *nonfinite_out,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the
  * reference (src/sqfa/linalg.py:165-183, 121-141: torch.linalg.eigh + einsum), as used by log_euclidean[_sq]
  * (src/sqfa/distances.py:92-138).  The eigen-decomposition is one-sided Jacobi, run to convergence, on the Cholesky

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SQFA_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libsqfa_hip.so")
 
 SQFA_F32, SQFA_F64 = 0, 1
+SQFA_GAUSS_BHATTACHARYYA, SQFA_GAUSS_HELLINGER, SQFA_GAUSS_MAHALANOBIS_SQ, SQFA_GAUSS_MAHALANOBIS = 0, 1, 2, 3
 SQFA_OK = 0
 STATUS_TEXT = {
     -1: "bad argument",
@@ -66,6 +67,13 @@ PROTOTYPES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "sqfa_gauss_pairwise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sqfa_gauss_pairwise_loss": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+         ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
     ),
     "sqfa_project_scatters": (
         ctypes.c_int,

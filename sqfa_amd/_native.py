@@ -345,6 +345,73 @@ class GaussPairTerms(torch.autograd.Function):
         return gmuA, gcovA, gmuB, gcovB, None
 
 
+def _pad_gauss(mu, cov, M):
+    """Identity padding of (n,m) means / (n,m,m) covariances to size M: exact for Q, logdet and the distances built on
+    them (log 1 = 0; the padded coordinates have delta = 0)."""
+    m = cov.shape[-1]
+    cov_p = torch.eye(M, dtype=cov.dtype, device=cov.device).repeat(cov.shape[0], 1, 1)
+    cov_p[:, :m, :m] = cov
+    return torch.nn.functional.pad(mu, (0, M - m)), cov_p
+
+
+def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dist=False):
+    """sqfa_gauss_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe inside
+    a graph capture).  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested)."""
+    lib = _lib.load()
+    if not cov.is_cuda:
+        raise RuntimeError("sqfa_amd's fused Gaussian pair loss runs on the GPU only (no CPU fallback)")
+    if mu.device != cov.device or mu.dtype != cov.dtype:
+        raise ValueError("means and covariances must share device and dtype")
+    mu, cov = mu.detach().contiguous(), cov.detach().contiguous()
+    n, m = cov.shape[0], cov.shape[-1]
+    if m > GAUSS_MAX_DIM:
+        raise NotImplementedError(f"feature dimension {m} exceeds the native Gaussian pair kernels' limit ({GAUSS_MAX_DIM})")
+    m_true = m
+    if m < 16 and m % 4 != 0 and n * n >= 20000:
+        # same rule as hip_gauss_terms: the one-pair-per-lane kernel reads whole 16-byte rows at its own sizes
+        m = (m + 3) // 4 * 4
+        mu, cov = _pad_gauss(mu, cov, m)
+    code = _dtype_code(cov)
+    nbytes = lib.sqfa_gauss_pairwise_workspace_bytes(n, m, code)
+    if nbytes == 0:
+        raise _lib.NativeLibraryError("sqfa_gauss_pairwise_workspace_bytes rejected the problem shape")
+    dev, dt = cov.device, cov.dtype
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=dt, device=dev)
+        nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
+        gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad else None
+        gcov = torch.empty((n, m, m), dtype=dt, device=dev) if want_grad else None
+        dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        status = lib.sqfa_gauss_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), float(weight),
+                                              _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist), _ptr(nonfinite),
+                                              _ptr(ws), nbytes, stream)
+    _lib.check(status, "sqfa_gauss_pairwise_loss")
+    if m != m_true and want_grad:
+        gmu, gcov = gmu[:, :m_true].contiguous(), gcov[:, :m_true, :m_true].contiguous()
+    return {"loss": loss, "gmu": gmu, "gcov": gcov, "dist": dist, "nonfinite": nonfinite}
+
+
+class GaussPairwiseLoss(torch.autograd.Function):
+    """Fused closure loss of the Gaussian pair distances (kind: _lib.SQFA_GAUSS_*): weight * sum over the unordered
+    class pairs of bhattacharyya / hellinger / mahalanobis[_sq], with its gradient wrt means (C,K) and covariances
+    (C,K,K), from ONE pass over the pairs (sqfa_gauss_pairwise_loss) -- in place of GaussPairTerms forward + the
+    element-wise chain + its backward + GaussPairTerms backward.  Returns (loss, flags {#NaN, #inf})."""
+
+    @staticmethod
+    def forward(ctx, means, covariances, kind, eps, weight):
+        out = hip_gauss_pairwise_loss(means, covariances, kind, eps, weight)
+        ctx.save_for_backward(out["gmu"], out["gcov"])
+        ctx.mark_non_differentiable(out["nonfinite"])
+        return out["loss"], out["nonfinite"]
+
+    @staticmethod
+    def backward(ctx, gloss, _gflag):
+        gmu, gcov = ctx.saved_tensors
+        return gmu * gloss, gcov * gloss, None, None, None
+
+
 # ------------------------------------------------------------------------------------------
 # per-class matrix functions (spd_log / spd_sqrt: log_euclidean's building block)
 

@@ -17,6 +17,14 @@
 // keeps its own gradient accumulator in LDS; groups are combined in a fixed order at the end
 // (bitwise reproducible, no atomics).  The B-side gradient is the same launch with the roles
 // swapped (the caller transposes gQ / gLD).
+//
+// Fused mode (sqfa_gauss_pairwise_loss, template parameter MODE = GAUSS_FUSED of both kernels, self case only): the pair's
+// distance D (bhattacharyya / hellinger / mahalanobis[_sq]) and its partial derivatives are formed from q and ld the
+// moment the pair is finished, so gQ / gLD are never read and no (C,C) matrix exists unless dist_out is asked for.
+// Class row i accumulates  w D_ij (i > j)  and the gradient of every pair it belongs to from its own side; the term
+// of the per-class log-determinants, -(1/4) (sum_j w dD/dBh_ij) Sigma_i^-1, uses the j == i step of the walk (Sbar_ii is
+// Sigma_i exactly), which parks Sigma_i^-1 in the workspace until the row's sum is known.  MODE = GAUSS_PRE is the
+// per-class pre-pass: the same Cholesky arithmetic on the pairs (c, c), writing logdet Sigma_c only.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
@@ -50,10 +58,55 @@ struct GaussParams {
   void *Q, *LD;              // (nA,nB) or nullptr
   void *gmuA, *gcovA;        // (nA,m), (nA,m,m) or nullptr
   int nA, nB, m, ng;         // ng: lane groups per workgroup
+  // fused mode only (B is A)
+  int kind;                  // SQFA_GAUSS_*
+  double eps, weight;
+  float epsf, weightf;       // the same two, rounded once on the host (scalar kernel arguments, no conversion per wave)
+  void *ldc;                 // (n) logdet Sigma_c: written by the pre-pass, read by the fused pass
+  void *sinv;                // (n,m,m) lower triangle of Sigma_i^-1, or nullptr (forward only / mahalanobis)
+  void *dist;                // (n,n) or nullptr
+  double *loss_part;         // (n) per-class partial losses
+  int *cnt_part;             // (n,2) per-class {#NaN, #inf}
 };
 
-template <typename T, int G>
+enum { GAUSS_PLAIN = 0, GAUSS_FUSED = 1, GAUSS_PRE = 2 };
+
+template <typename T> __device__ __forceinline__ T fused_weight(const GaussParams& p);
+template <> __device__ __forceinline__ float fused_weight<float>(const GaussParams& p) { return p.weightf; }
+template <> __device__ __forceinline__ double fused_weight<double>(const GaussParams& p) { return p.weight; }
+template <typename T> __device__ __forceinline__ T fused_eps(const GaussParams& p);
+template <> __device__ __forceinline__ float fused_eps<float>(const GaussParams& p) { return p.epsf; }
+template <> __device__ __forceinline__ double fused_eps<double>(const GaussParams& p) { return p.eps; }
+
+__device__ __forceinline__ float g_exp(float x) { return expf(x); }
+__device__ __forceinline__ double g_exp(double x) { return exp(x); }
+__device__ __forceinline__ float g_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double g_sqrt(double x) { return sqrt(x); }
+
+// D and its partial derivatives from the pair terms: dQ = dD/dQ in total (through Bh too), dBh = dD/dBh (dD/dLD = dBh / 2,
+// dD/dld_c = -dBh / 4).  On the diagonal the log-determinant term is exactly zero, as in the reference.
+template <typename T>
+__device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi, T ldj, bool diagonal, T& D, T& dQ, T& dBh) {
+  if (kind == SQFA_GAUSS_MAHALANOBIS_SQ) {
+    D = q; dQ = T(1); dBh = T(0);
+  } else if (kind == SQFA_GAUSS_MAHALANOBIS) {
+    D = g_sqrt(q + eps); dQ = T(0.5) / D; dBh = T(0);
+  } else {
+    const T bh = diagonal ? q * T(0.125) : q * T(0.125) + T(0.5) * (ld - T(0.5) * (ldi + ldj));
+    if (kind == SQFA_GAUSS_BHATTACHARYYA) {
+      D = bh; dBh = T(1);
+    } else {
+      const T e = g_exp(-bh);
+      D = g_sqrt(T(1) - e + eps);
+      dBh = T(0.5) * e / D;
+    }
+    dQ = T(0.125) * dBh;
+  }
+}
+
+template <typename T, int G, int MODE = GAUSS_PLAIN>
 __global__ void gauss_pair_kernel(const GaussParams p) {
+  constexpr bool FUSED = MODE == GAUSS_FUSED, PRE = MODE == GAUSS_PRE;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   constexpr int LD_ = G + 1;                 // row pitch
@@ -78,6 +131,12 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
   const T* gLD = static_cast<const T*>(p.gLD);
   const bool want_grad = p.gcovA != nullptr;
   const int lane_base = (tid & 63) & ~(G - 1);  // first lane of my group inside the wave
+  // Sbar^-1 is needed where logdet Sbar has a gradient
+  const bool with_inv = FUSED ? p.kind <= SQFA_GAUSS_HELLINGER : gLD != nullptr;
+  const T* ldc = static_cast<const T*>(p.ldc);
+  const T fw = fused_weight<T>(p), feps = fused_eps<T>(p);
+  T loss_acc = T(0), csum = T(0);   // fused: lane 0 of the group keeps the group's partial sums
+  int n_nan = 0, n_inf = 0;
 
   if (want_grad && live) {
     for (int c = 0; c < G; ++c) acc[r * LD_ + c] = T(0);
@@ -86,7 +145,8 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
   const T mu_i = active ? muA[(size_t)i * m + r] : T(0);
   const T* ci = covA + (size_t)i * m * m;
 
-  for (int j = live ? grp : p.nB; j < p.nB; j += p.ng) {
+  // pre-pass: the single "pair" (i, i), on group 0
+  for (int j = PRE ? (grp == 0 ? i : p.nB) : (live ? grp : p.nB); j < p.nB; j += PRE ? p.nB : p.ng) {
     const T* cj = covB + (size_t)j * m * m;
     if (active) {
       for (int c = 0; c <= r; ++c) a[r * LD_ + c] = T(0.5) * (ci[r * m + c] + cj[r * m + c]);
@@ -118,17 +178,40 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
       if (r == k) z = zk;
       if (active && r > k) d -= a[r * LD_ + k] * zk;
     }
+    if constexpr (PRE) {
+      if (r == 0) static_cast<T*>(p.ldc)[i] = ld;
+      return;
+    }
     const T q = group_total<G>(z * z);
-    if (r == 0) {
-      if (p.Q != nullptr) static_cast<T*>(p.Q)[(size_t)i * p.nB + j] = q;
-      if (p.LD != nullptr) static_cast<T*>(p.LD)[(size_t)i * p.nB + j] = ld;
+    T gq, gl;
+    if constexpr (FUSED) {
+      T D, dQ, dBh;
+      gauss_distance<T>(p.kind, feps, q, ld, with_inv ? ldc[i] : T(0), with_inv ? ldc[j] : T(0), j == i, D, dQ, dBh);
+      gq = j != i ? fw * dQ : T(0);
+      gl = j != i ? T(0.5) * fw * dBh : T(0);
+      if (r == 0) {
+        if (j != i) csum += fw * dBh;
+        if (j < i) {   // each unordered pair counted once
+          loss_acc += fw * D;
+          n_nan += D != D;
+          n_inf += D == D && __builtin_isinf(D);
+        }
+        if (p.dist != nullptr) static_cast<T*>(p.dist)[(size_t)i * p.nB + j] = D;
+      }
+    } else {
+      if (r == 0) {
+        if (p.Q != nullptr) static_cast<T*>(p.Q)[(size_t)i * p.nB + j] = q;
+        if (p.LD != nullptr) static_cast<T*>(p.LD)[(size_t)i * p.nB + j] = ld;
+      }
     }
     if (!want_grad) {
       group_sync();
       continue;
     }
-    const T gq = gQ != nullptr ? gQ[(size_t)i * p.nB + j] : T(0);
-    const T gl = gLD != nullptr ? gLD[(size_t)i * p.nB + j] : T(0);
+    if constexpr (!FUSED) {
+      gq = gQ != nullptr ? gQ[(size_t)i * p.nB + j] : T(0);
+      gl = gLD != nullptr ? gLD[(size_t)i * p.nB + j] : T(0);
+    }
     // ---- s = R^-T z (column oriented, from the last row up) -----------------------------
     T t = z, s = T(0);
     for (int k = m - 1; k >= 0; --k) {
@@ -139,7 +222,7 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
     sv[r] = s;
     mu_acc += T(2) * gq * s;
     // ---- W = R^-1: lane c owns column c ---------------------------------------------------
-    if (gLD != nullptr) {
+    if (with_inv) {
       if (active) {
         w[r * LD_ + r] = rdiag;
         for (int rr = r + 1; rr < m; ++rr) {
@@ -154,10 +237,13 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
     if (active) {
       for (int c = 0; c <= r; ++c) {
         T v = -gq * s * sv[c];
-        if (gLD != nullptr) {
+        if (with_inv) {
           T inv = T(0);
           for (int k = r; k < m; ++k) inv += w[k * LD_ + r] * w[k * LD_ + c];
           v += gl * inv;
+          if constexpr (FUSED) {
+            if (j == i) static_cast<T*>(p.sinv)[((size_t)i * m + r) * m + c] = inv;   // Sbar_ii = Sigma_i
+          }
         }
         acc[r * LD_ + c] += T(0.5) * v;
       }
@@ -165,9 +251,38 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
     group_sync();
   }
 
-  if (!want_grad) return;
-  if (live) accmu[r] = mu_acc;
-  __syncthreads();
+  T coef = T(0);   // fused: -(1/4) sum_j w dD/dBh_ij, the weight of Sigma_i^-1
+  if constexpr (FUSED) {
+    __shared__ T s_part[64][2];
+    __shared__ int s_cnt[64][2];
+    if (live && r == 0) {
+      s_part[grp][0] = loss_acc;
+      s_part[grp][1] = csum;
+      s_cnt[grp][0] = n_nan;
+      s_cnt[grp][1] = n_inf;
+    }
+    if (want_grad && live) accmu[r] = mu_acc;
+    __syncthreads();
+    T lsum = T(0), cs = T(0);
+    int nn = 0, ni = 0;
+    for (int g2 = 0; g2 < p.ng; ++g2) {
+      lsum += s_part[g2][0];
+      cs += s_part[g2][1];
+      nn += s_cnt[g2][0];
+      ni += s_cnt[g2][1];
+    }
+    if (tid == 0) {
+      p.loss_part[i] = (double)lsum;
+      p.cnt_part[2 * i] = nn;
+      p.cnt_part[2 * i + 1] = ni;
+    }
+    if (!want_grad) return;
+    coef = T(-0.25) * cs;
+  } else {
+    if (!want_grad) return;
+    if (live) accmu[r] = mu_acc;
+    __syncthreads();
+  }
   // combine the groups in a fixed order; write the full symmetric gradient
   T* gcov = static_cast<T*>(p.gcovA) + (size_t)i * m * m;
   for (int e = tid; e < m * m; e += blockDim.x) {
@@ -175,6 +290,9 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
     const int hi = rr > cc ? rr : cc, lo = rr > cc ? cc : rr;
     T sum = T(0);
     for (int g2 = 0; g2 < p.ng; ++g2) sum += smem[(size_t)g2 * PER_GROUP + 2 * MAT + hi * LD_ + lo];
+    if constexpr (FUSED) {
+      if (with_inv) sum += coef * static_cast<const T*>(p.sinv)[((size_t)i * m + hi) * m + lo];
+    }
     gcov[e] = sum;
   }
   if (p.gmuA != nullptr) {
@@ -187,11 +305,11 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
   }
 }
 
-template <typename T, int G>
+template <typename T, int G, int MODE = GAUSS_PLAIN>
 static hipError_t launch_gauss(const GaussParams& p0, hipStream_t stream) {
   GaussParams p = p0;
   const size_t per_group = (size_t)(3 * G * (G + 1) + 2 * G) * sizeof(T);
-  int ng = 256 / G;
+  int ng = MODE == GAUSS_PRE ? 1 : 256 / G;   // the pre-pass has one pair per class
   const size_t budget = 60 * 1024;
   while (ng > 1 && ng * per_group > budget) ng /= 2;
   if (ng > p.nB) {  // fewer pairs per class than groups: do not leave whole waves idle
@@ -203,13 +321,13 @@ static hipError_t launch_gauss(const GaussParams& p0, hipStream_t stream) {
   p.ng = ng;
   const size_t lds = ng * per_group;
   if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gauss_pair_kernel<T, G>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gauss_pair_kernel<T, G, MODE>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
   int threads = ng * G;
   if (threads < 64) threads = 64;  // whole waves (extra lanes form idle groups: grp >= ng never owns a pair)
-  hipLaunchKernelGGL((gauss_pair_kernel<T, G>), dim3(p.nA), dim3(threads), lds, stream, p);
+  hipLaunchKernelGGL((gauss_pair_kernel<T, G, MODE>), dim3(p.nA), dim3(threads), lds, stream, p);
   return hipGetLastError();
 }
 
@@ -249,9 +367,14 @@ template <typename T, int M> struct GradEntries {
 // the arithmetic and takes 313 registers at M=16)
 // EXACT: m == M (no identity padding: no selects, rows of M elements, 16-byte row loads when M % 4 == 0 (float32) / M % 2
 // == 0 (float64) and the matrices are 16-byte aligned, which the launcher checks)
-template <typename T, int M, bool EXACT>
-__global__ __launch_bounds__(256, (M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 40 ? 4 : ((M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 140 ? 2 : 1))
+// (fused mode with identity padding in the kernel, MODE = GAUSS_FUSED && !EXACT: the selects of the padding plus the
+// epilogue's scalars do not fit the budget of the twin; half the workgroups per CU instead of spills -- this variant only
+// runs small problems, the host pads large ones to an EXACT size)
+template <typename T, int M, bool EXACT, int MODE = GAUSS_PLAIN>
+__global__ __launch_bounds__(256, ((M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 40 ? 4 : ((M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 140 ? 2 : 1))
+                                   >> ((MODE == GAUSS_FUSED && !EXACT && (M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 140) ? 1 : 0))
 void gauss_pair_reg_kernel(const GaussParams p) {
+  constexpr bool FUSED = MODE == GAUSS_FUSED, PRE = MODE == GAUSS_PRE;
   constexpr int TRI = M * (M + 1) / 2, NACC = TRI + M;
   __shared__ T s_acc[4][NACC | 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -268,16 +391,24 @@ void gauss_pair_reg_kernel(const GaussParams p) {
   }
   const T* ci = covA + (size_t)i * m * m;
   auto at = [](int r, int c) constexpr { return r * (r + 1) / 2 + c; };  // c <= r
+  // Sbar^-1 is needed where logdet Sbar has a gradient
+  const bool with_inv = FUSED ? p.kind <= SQFA_GAUSS_HELLINGER : gLD != nullptr;
+  const T* ldc = static_cast<const T*>(p.ldc);
+  const T fw = fused_weight<T>(p), feps = fused_eps<T>(p);
+  T loss_acc = T(0), csum = T(0);   // fused: per-wave partial sums and counts (wave-uniform: scalar registers)
+  int n_nan = 0, n_inf = 0;
 
-  const int rounds = (p.nB + 255) / 256;
+  // pre-pass: one workgroup per 256 classes, lane = class c, the "pair" (c, c)
+  const int rounds = PRE ? 1 : (p.nB + 255) / 256;
   for (int it = 0; it < rounds; ++it) {
-    const int j = it * 256 + tid;
+    const int j = (PRE ? (int)blockIdx.x : it) * 256 + tid;
     const bool valid = j < p.nB;
     const T* cj = covB + (size_t)(valid ? j : 0) * m * m;
     // Sigma_i is the same in every round: hidden from loop-invariant code motion, or its 136 values would be kept in
     // registers across the whole loop (321 VGPRs and spills at M=16 instead of ~200)
     const T* cir = ci;
-    asm volatile("" : "+s"(cir));
+    if constexpr (PRE) cir = cj;
+    else asm volatile("" : "+s"(cir));
     T a[TRI], d[M];
     // ---- Sbar = (Sigma_i + Sigma_j)/2 and its Cholesky factor R (lower, in place), ROW BY ROW: row r needs the finished
     //      rows above it and its own entries only, so the loads of a row sit next to their use (live set: the triangle
@@ -290,7 +421,8 @@ void gauss_pair_reg_kernel(const GaussParams p) {
     for (int r = 0; r < M; ++r) {
       T row[M];
       if constexpr (EXACT) {
-        d[r] = muA[(size_t)i * M + r] - muB[(size_t)(valid ? j : 0) * M + r];
+        if constexpr (PRE) d[r] = T(0);
+        else d[r] = muA[(size_t)i * M + r] - muB[(size_t)(valid ? j : 0) * M + r];
         if constexpr (M % VW == 0) {
 #pragma unroll
           for (int c0 = 0; c0 <= r; c0 += VW) {
@@ -306,7 +438,7 @@ void gauss_pair_reg_kernel(const GaussParams p) {
       } else {
         const bool rr = r < m;
         const int rc = rr ? r : m - 1;   // clamped addresses, selected values: no branches
-        const T dv = muA[(size_t)i * m + rc] - muB[(size_t)(valid ? j : 0) * m + rc];
+        const T dv = PRE ? T(0) : muA[(size_t)i * m + rc] - muB[(size_t)(valid ? j : 0) * m + rc];
         d[r] = rr ? dv : T(0);
 #pragma unroll
         for (int c = 0; c <= r; ++c) {
@@ -335,6 +467,10 @@ void gauss_pair_reg_kernel(const GaussParams p) {
       a[at(r, r)] = dk;
     }
     ld *= T(2);
+    if constexpr (PRE) {
+      if (valid) static_cast<T*>(p.ldc)[j] = ld;
+      return;
+    }
     // ---- z = R^-1 delta, Q = |z|^2 ----
     T q = T(0);
 #pragma unroll
@@ -345,13 +481,29 @@ void gauss_pair_reg_kernel(const GaussParams p) {
       d[k] = t * rdiag[k];   // d becomes z
       q += d[k] * d[k];
     }
-    if (valid) {
-      if (p.Q != nullptr) static_cast<T*>(p.Q)[(size_t)i * p.nB + j] = q;
-      if (p.LD != nullptr) static_cast<T*>(p.LD)[(size_t)i * p.nB + j] = ld;
+    T gq, gl;
+    if constexpr (FUSED) {
+      T D, dQ, dBh;
+      const T ldi = with_inv ? ldc[i] : T(0), ldj = with_inv ? ldc[valid ? j : 0] : T(0);
+      gauss_distance<T>(p.kind, feps, q, ld, ldi, ldj, j == i, D, dQ, dBh);
+      const bool off = valid && j != i, counted = valid && j < i;   // each unordered pair counted once
+      gq = off ? fw * dQ : T(0);
+      gl = off ? T(0.5) * fw * dBh : T(0);
+      csum = wave_uniform(csum + wave_sum(off ? fw * dBh : T(0)));
+      loss_acc = wave_uniform(loss_acc + wave_sum(counted ? fw * D : T(0)));
+      n_nan += __popcll(__ballot(counted && D != D));
+      n_inf += __popcll(__ballot(counted && D == D && __builtin_isinf(D)));
+      if (valid && p.dist != nullptr) static_cast<T*>(p.dist)[(size_t)i * p.nB + j] = D;
+      if (!want_grad) continue;
+    } else {
+      if (valid) {
+        if (p.Q != nullptr) static_cast<T*>(p.Q)[(size_t)i * p.nB + j] = q;
+        if (p.LD != nullptr) static_cast<T*>(p.LD)[(size_t)i * p.nB + j] = ld;
+      }
+      if (!want_grad) continue;
+      gq = (valid && gQ != nullptr) ? gQ[(size_t)i * p.nB + j] : T(0);
+      gl = (valid && gLD != nullptr) ? gLD[(size_t)i * p.nB + j] : T(0);
     }
-    if (!want_grad) continue;
-    const T gq = (valid && gQ != nullptr) ? gQ[(size_t)i * p.nB + j] : T(0);
-    const T gl = (valid && gLD != nullptr) ? gLD[(size_t)i * p.nB + j] : T(0);
     // ---- s = R^-T z (in place, from the last row up) ----
 #pragma unroll
     for (int k = M - 1; k >= 0; --k) {
@@ -360,7 +512,7 @@ void gauss_pair_reg_kernel(const GaussParams p) {
       for (int r = k + 1; r < M; ++r) t -= a[at(r, k)] * d[r];
       d[k] = t * rdiag[k];   // d becomes s
     }
-    if (gLD != nullptr) {
+    if (with_inv) {
       // ---- W = R^-1 in place, column by column: column c of W needs R[r][k] for k >= c only, so it may overwrite
       //      column c of R as soon as it is complete ----
 #pragma unroll
@@ -391,22 +543,57 @@ void gauss_pair_reg_kernel(const GaussParams p) {
 #pragma unroll
         for (int c = 0; c <= r; ++c) a[at(r, c)] = row[c];
       }
+      if constexpr (FUSED) {
+        if (valid && j == i) {   // Sbar_ii = Sigma_i: one lane of one round parks Sigma_i^-1 for the per-class term
+          // (pitch M whatever m is: compile-time offsets; the workspace holds (m rounded up to 4)^2 elements per class)
+          T* si = static_cast<T*>(p.sinv) + (size_t)i * (M * M);
+#pragma unroll
+          for (int r = 0; r < M; ++r) {
+#pragma unroll
+            for (int c = 0; c <= r; ++c) si[r * M + c] = a[at(r, c)];
+          }
+        }
+      }
     }
     // ---- 1/2 (gl Sbar^-1 - gq s s^T) and 2 gq s, summed over the 64 pairs of the wave: lane l finishes entries 64 I + l ----
     {
-      const GradEntries<T, M> prod{a, d, gq, gl, gLD != nullptr};
+      const GradEntries<T, M> prod{a, d, gq, gl, with_inv};
       T* acc = s_acc[wave];
       tree_reduce_blocks<6, 0, (NACC + 63) / 64, NACC, T>(prod, lane, [&](int idx, T v) { acc[idx] += v; });
     }
   }
-  if (!want_grad) return;
-  __syncthreads();
+  T coef = T(0);   // fused: -(1/4) sum_j w dD/dBh_ij, the weight of Sigma_i^-1
+  if constexpr (FUSED) {
+    __shared__ T s_part[4][2];
+    __shared__ int s_cnt[4][2];
+    if (lane == 0) {
+      s_part[wave][0] = loss_acc;
+      s_part[wave][1] = csum;
+      s_cnt[wave][0] = n_nan;
+      s_cnt[wave][1] = n_inf;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      p.loss_part[i] = (double)(((s_part[0][0] + s_part[1][0]) + s_part[2][0]) + s_part[3][0]);
+      p.cnt_part[2 * i] = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
+      p.cnt_part[2 * i + 1] = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
+    }
+    if (!want_grad) return;
+    coef = T(-0.25) * (((s_part[0][1] + s_part[1][1]) + s_part[2][1]) + s_part[3][1]);
+  } else {
+    if (!want_grad) return;
+    __syncthreads();
+  }
   T* gcov = static_cast<T*>(p.gcovA) + (size_t)i * m * m;
   for (int e = tid; e < m * m; e += 256) {
     const int rr = e / m, cc = e % m;
     const int hi = rr > cc ? rr : cc, lo = rr > cc ? cc : rr;
     const int idx = hi * (hi + 1) / 2 + lo;
-    gcov[e] = ((s_acc[0][idx] + s_acc[1][idx]) + s_acc[2][idx]) + s_acc[3][idx];
+    T sum = ((s_acc[0][idx] + s_acc[1][idx]) + s_acc[2][idx]) + s_acc[3][idx];
+    if constexpr (FUSED) {
+      if (with_inv) sum += coef * static_cast<const T*>(p.sinv)[(size_t)i * (M * M) + hi * M + lo];
+    }
+    gcov[e] = sum;
   }
   if (p.gmuA != nullptr) {
     T* gmu = static_cast<T*>(p.gmuA) + (size_t)i * m;
@@ -415,15 +602,73 @@ void gauss_pair_reg_kernel(const GaussParams p) {
   }
 }
 
-template <typename T, int M>
+template <typename T, int M, int MODE = GAUSS_PLAIN>
 static hipError_t launch_gauss_reg(const GaussParams& p, hipStream_t stream) {
   const bool aligned = (reinterpret_cast<size_t>(p.covA) % 16) == 0 && (reinterpret_cast<size_t>(p.covB) % 16) == 0;
+  const dim3 grid(MODE == GAUSS_PRE ? (p.nA + 255) / 256 : p.nA);
   if (p.m == M && aligned)
-    hipLaunchKernelGGL((gauss_pair_reg_kernel<T, M, true>), dim3(p.nA), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gauss_pair_reg_kernel<T, M, true, MODE>), grid, dim3(256), 0, stream, p);
   else
-    hipLaunchKernelGGL((gauss_pair_reg_kernel<T, M, false>), dim3(p.nA), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gauss_pair_reg_kernel<T, M, false, MODE>), grid, dim3(256), 0, stream, p);
   return hipGetLastError();
 }
+
+// the kernel the plain entry point would pick for (dtype, m), in mode MODE
+template <int MODE>
+static hipError_t dispatch_gauss(const GaussParams& p, int dtype, hipStream_t stream) {
+  const int m = p.m;
+  if (dtype == SQFA_F32) {
+    if (m <= 4) return launch_gauss_reg<float, 4, MODE>(p, stream);
+    if (m <= 8) return launch_gauss_reg<float, 8, MODE>(p, stream);
+    if (m <= 12) return launch_gauss_reg<float, 12, MODE>(p, stream);
+    if (m <= 16) return launch_gauss_reg<float, 16, MODE>(p, stream);
+    if (m <= 32) return launch_gauss<float, 32, MODE>(p, stream);
+    return launch_gauss<float, 64, MODE>(p, stream);
+  }
+  if (m <= 4) return launch_gauss_reg<double, 4, MODE>(p, stream);
+  if (m <= 8) return launch_gauss_reg<double, 8, MODE>(p, stream);
+  if (m <= 12) return launch_gauss_reg<double, 12, MODE>(p, stream);
+  if (m <= 16) return launch_gauss_reg<double, 16, MODE>(p, stream);
+  if (m <= 32) return launch_gauss<double, 32, MODE>(p, stream);
+  return launch_gauss<double, 64, MODE>(p, stream);
+}
+
+// loss = sum of the per-class partial losses, {#NaN, #inf} = sums of the per-class counts: one workgroup, fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_finalize_kernel(const double* loss_part, const int* cnt_part, int n,
+                                                              T* loss_out, int* nonfinite_out) {
+  __shared__ double s_loss[256];
+  __shared__ int s_cnt[256][2];
+  const int tid = threadIdx.x;
+  double l = 0.0;
+  int nn = 0, ni = 0;
+  for (int c = tid; c < n; c += 256) {
+    l += loss_part[c];
+    nn += cnt_part[2 * c];
+    ni += cnt_part[2 * c + 1];
+  }
+  s_loss[tid] = l;
+  s_cnt[tid][0] = nn;
+  s_cnt[tid][1] = ni;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (tid < d) {
+      s_loss[tid] += s_loss[tid + d];
+      s_cnt[tid][0] += s_cnt[tid + d][0];
+      s_cnt[tid][1] += s_cnt[tid + d][1];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (loss_out != nullptr) *loss_out = T(s_loss[0]);
+    if (nonfinite_out != nullptr) {
+      nonfinite_out[0] = s_cnt[0][0];
+      nonfinite_out[1] = s_cnt[0][1];
+    }
+  }
+}
+
+static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 }  // namespace sqfa
 
 using namespace sqfa;
@@ -473,4 +718,52 @@ extern "C" int sqfa_gauss_pair_terms(const void* muA, const void* covA, int nA, 
     SQFA_GAUSS_DISPATCH(double)
   }
   return e == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+// workspace of sqfa_gauss_pairwise_loss: [logdet Sigma_c (n)] [partial losses (n) double] [counts (n,2) int] [Sigma_c^-1 (n,m,m)]
+extern "C" size_t sqfa_gauss_pairwise_workspace_bytes(int n, int m, int dtype) {
+  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return 0;
+  const size_t elem = dtype == SQFA_F32 ? 4 : 8;
+  const size_t mp = ((size_t)m + 3) & ~(size_t)3;   // the register kernels park Sigma_c^-1 with their padded pitch
+  return 3 * align256((size_t)n * 8) + align256((size_t)n * mp * mp * elem);
+}
+
+extern "C" int sqfa_gauss_pairwise_loss(const void* mu, const void* cov, int n, int m, int dtype, int kind, double eps,
+                                        double uniform_weight, void* loss_out, void* gmu_out, void* gcov_out,
+                                        void* dist_out, int* nonfinite_out, void* workspace, size_t workspace_bytes,
+                                        void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (mu == nullptr || cov == nullptr || n < 2 || m < 1) return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  if (kind < SQFA_GAUSS_BHATTACHARYYA || kind > SQFA_GAUSS_MAHALANOBIS) return SQFA_ERR_BAD_ARGUMENT;
+  if ((gmu_out != nullptr) != (gcov_out != nullptr)) return SQFA_ERR_BAD_ARGUMENT;
+  if (m > 64) return SQFA_ERR_UNSUPPORTED_M;
+  const size_t need = sqfa_gauss_pairwise_workspace_bytes(n, m, dtype);
+  if (workspace == nullptr || workspace_bytes < need) return SQFA_ERR_WORKSPACE;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const size_t block = align256((size_t)n * 8);
+  GaussParams p{mu, cov, mu, cov, nullptr, nullptr, nullptr, nullptr, gmu_out, gcov_out, n, n, m, 1};
+  p.kind = kind;
+  p.eps = eps;
+  p.weight = uniform_weight;
+  p.epsf = (float)eps;
+  p.weightf = (float)uniform_weight;
+  p.ldc = ws;
+  p.loss_part = reinterpret_cast<double*>(ws + block);
+  p.cnt_part = reinterpret_cast<int*>(ws + 2 * block);
+  p.sinv = ws + 3 * block;
+  p.dist = dist_out;
+  if (kind <= SQFA_GAUSS_HELLINGER) {   // per-class log-determinants first: every pair needs both of its classes'
+    GaussParams pre = p;
+    pre.gmuA = pre.gcovA = nullptr;
+    if (dispatch_gauss<GAUSS_PRE>(pre, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
+  }
+  if (dispatch_gauss<GAUSS_FUSED>(p, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
+  if (dtype == SQFA_F32)
+    hipLaunchKernelGGL((gauss_finalize_kernel<float>), dim3(1), dim3(256), 0, stream, p.loss_part, p.cnt_part, n,
+                       static_cast<float*>(loss_out), nonfinite_out);
+  else
+    hipLaunchKernelGGL((gauss_finalize_kernel<double>), dim3(1), dim3(256), 0, stream, p.loss_part, p.cnt_part, n,
+                       static_cast<double*>(loss_out), nonfinite_out);
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }

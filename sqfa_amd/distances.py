@@ -7,7 +7,8 @@ hand-written HIP kernels (forward and backward).  The other operators (SURVEY.md
 either model; for GPU tensors their pair-dependent terms run on the native Gaussian pair kernel
 (``bhattacharyya`` / ``mahalanobis[_sq]`` / ``hellinger`` / ``fisher_rao_same_cov``: sqfa_gauss_pair_terms) or avoid
 the reference's (nA,nB,m,m) tensor (``log_euclidean[_sq]``: per-class logarithms + exact pairwise distances); CPU
-tensors keep the reference's torch expression.
+tensors keep the reference's torch expression.  As ``SQFA``'s ``distance_fun``, ``bhattacharyya`` / ``hellinger`` /
+``mahalanobis[_sq]`` train through one fused loss+gradient pass per closure (sqfa_gauss_pairwise_loss, GAUSS_FUSED_CLOSURE).
 """
 import torch
 
@@ -65,8 +66,13 @@ def _pair_matrix(A, B, scale, sqrt_mode):
 
 # marks the callables the fused closure path may replace by a single loss+grad launch:
 # name -> (input kind, scale, sqrt_mode, pair metric)   metric: "airm" (sqfa_airm_pairwise) | "bw" (sqfa_bw_pairwise,
-# registered by sqfa_amd.transport)
+# registered by sqfa_amd.transport) | "gauss" (sqfa_gauss_pairwise_loss: `scale` holds the SQFA_GAUSS_* kind code)
 _FUSED = {}
+
+# bhattacharyya / hellinger / mahalanobis[_sq] as SQFA's distance_fun: one fused loss+gradient pass over the class pairs
+# (_native.GaussPairwiseLoss), captured in a HIP graph by the fitting loop.  False restores the generic closure
+# (GaussPairTerms -> element-wise chain -> validity check on the host -> autograd backward, no graph).
+GAUSS_FUSED_CLOSURE = True
 
 
 def _fusable(kind, scale, sqrt_mode, metric="airm"):
@@ -78,7 +84,10 @@ def _fusable(kind, scale, sqrt_mode, metric="airm"):
 
 def fused_spec(fn):
     """(kind, scale, sqrt_mode, metric) if `fn` is one of the native pair operators the fused closure evaluates."""
-    return _FUSED.get(fn)
+    spec = _FUSED.get(fn)
+    if spec is not None and spec[3] == "gauss" and not GAUSS_FUSED_CLOSURE:
+        return None
+    return spec
 
 
 @_fusable("spd", 1.0, False)
@@ -182,6 +191,7 @@ def _gauss_pair_terms(statistics_A, statistics_B):
     return (delta * sol).sum(-1), torch.logdet(mid), torch.logdet(covA), torch.logdet(covB)
 
 
+@_fusable("gaussian", _native._lib.SQFA_GAUSS_BHATTACHARYYA, False, "gauss")
 def bhattacharyya(statistics_A, statistics_B):
     """Bhattacharyya distance between Gaussians (reference: src/sqfa/distances.py:240-280):
     Q/8 + (logdet Sbar - (logdet Sigma_i + logdet Sigma_j)/2)/2."""
@@ -190,17 +200,20 @@ def bhattacharyya(statistics_A, statistics_B):
     return torch.squeeze(Q / 8 + det_term)
 
 
+@_fusable("gaussian", _native._lib.SQFA_GAUSS_MAHALANOBIS_SQ, False, "gauss")
 def mahalanobis_sq(statistics_A, statistics_B):
     """Squared Mahalanobis distance under the pair's mean covariance
     (reference: src/sqfa/distances.py:283-332; like the reference, not squeezed)."""
     return _gauss_pair_terms(statistics_A, statistics_B)[0]
 
 
+@_fusable("gaussian", _native._lib.SQFA_GAUSS_MAHALANOBIS, True, "gauss")
 def mahalanobis(statistics_A, statistics_B):
     """reference: src/sqfa/distances.py:335-361"""
     return torch.sqrt(mahalanobis_sq(statistics_A, statistics_B) + EPSILON)
 
 
+@_fusable("gaussian", _native._lib.SQFA_GAUSS_HELLINGER, True, "gauss")
 def hellinger(statistics_A, statistics_B):
     """reference: src/sqfa/distances.py:364-393"""
     return torch.sqrt(1 - torch.exp(-bhattacharyya(statistics_A, statistics_B)) + EPSILON)

@@ -149,7 +149,12 @@ class SecondMomentsSQFA(nn.Module):
     def _has_fused_closure(self):
         """True when distance_fun is the native operator this model's fused closure evaluates."""
         spec = distances.fused_spec(self.distance_fun)
-        return spec is not None and spec[0] == self._fused_kind
+        if spec is None or spec[0] != self._fused_kind:
+            return False
+        if spec[3] == "gauss":   # the Gaussian pair kernels' own limits: beyond them the generic closure, never captured
+            nm = self.noise_mat   # (K,K), the model's dtype (reading self.filters would run the parametrization)
+            return nm.shape[0] <= _native.GAUSS_MAX_DIM and nm.dtype in (torch.float32, torch.float64)
+        return True
 
     # the whole closure as ONE autograd node (8 / 11 launches instead of ~40): _native.FusedClosure
     SINGLE_NODE_CLOSURE = True
@@ -181,6 +186,8 @@ class SecondMomentsSQFA(nn.Module):
             return None
         spec = distances.fused_spec(self.distance_fun)
         scale, sqrt_mode, metric = spec[1], spec[2], spec[3]
+        if metric == "gauss":
+            return self._gauss_closure_loss(prepared, scale)
         single = self._single_node_inputs(prepared)
         if single is not None:
             raw, scatters, means, sphere = single
@@ -195,6 +202,23 @@ class SecondMomentsSQFA(nn.Module):
             return _native.FusedClosure.apply(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere,
                                               metric)
         return self._fused_closure_loss_chain(prepared, scale, sqrt_mode, metric)
+
+    def _gauss_closure_loss(self, prepared, kind):
+        """(loss, flags) for bhattacharyya / hellinger / mahalanobis[_sq] as the chain parametrization -> projection ->
+        noise -> _native.GaussPairwiseLoss (one fused pass over the class pairs), or None -- the fitting loop's generic
+        closure -- where the native kernels do not apply: CPU or non-float32/64 statistics, more than
+        _native.GAUSS_MAX_DIM filters, sharded fits."""
+        if self.pair_shard is not None or self.class_shard is not None or not isinstance(prepared, dict):
+            return None
+        stats = self._feature_statistics(prepared, True)
+        mu, cov = stats["means"], stats["covariances"]
+        if not (cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[-1] <= _native.GAUSS_MAX_DIM
+                and cov.shape[0] >= 2 and cov.dtype in (torch.float32, torch.float64) and mu.dtype == cov.dtype
+                and mu.device == cov.device):
+            return None
+        C = cov.shape[0]
+        weight = -1.0 / (C * (C - 1) // 2)
+        return _native.GaussPairwiseLoss.apply(mu, cov, int(kind), distances.EPSILON, weight)
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once

@@ -55,48 +55,59 @@ SQFA_CONFIGS2D_F32(SQFA_DECL2D_F32)
 SQFA_CONFIGS2D_F64(SQFA_DECL2D_F64)
 
 struct Geometry {
-  int MR, G, CPL, TJ, TI, WV;  // TJ: widest tile (B classes); a launch may use TJ/2, TJ/4 ... >= WV
+  int dtype, MR, TJ, TI, WV;  // TJ: widest tile (B classes); a launch may use TJ/2, TJ/4 ... >= WV
   hipError_t (*launch)(const PairParams&, hipStream_t);
   hipError_t (*factor)(const PairParams&, hipStream_t);  // K0b, the class factor pass
-  hipError_t (*eig)(const void*, int, int, double*, double*, hipStream_t) = nullptr;  // per-class eigen-decomposition (regular rows)
-  bool mean_metric = false;     // the row's factor pass runs in the metric of the mean class (Cfg::MEAN_METRIC)
-  long factor_min_pairs = 0;    // Cfg::FACTOR_MIN_PAIRS: launches with fewer pairs per shard skip the factor pass
-  hipError_t (*launch_bw)(const PairParams&, hipStream_t) = nullptr;  // the row's Bures-Wasserstein tile kernel
+  hipError_t (*eig)(const void*, int, int, double*, double*, hipStream_t);  // per-class eigen-decomposition (regular rows)
+  hipError_t (*launch_bw)(const PairParams&, hipStream_t);  // the row's Bures-Wasserstein tile kernel
+  bool mean_metric;       // the row's factor pass runs in the metric of the mean class (Cfg::MEAN_METRIC)
+  long factor_min_pairs;  // Cfg::FACTOR_MIN_PAIRS: launches with fewer pairs per shard skip the factor pass
 };
+// One row of the table: the numbers come from the configuration type (PairCfg or PairCfg2D), the launchers by name.
+template <typename Cfg>
+static Geometry make_geometry(decltype(Geometry::launch) launch, decltype(Geometry::factor) factor, decltype(Geometry::eig) eig,
+                              decltype(Geometry::launch_bw) launch_bw) {
+  return Geometry{sizeof(typename Cfg::type) == 4 ? SQFA_F32 : SQFA_F64, Cfg::MR, Cfg::TJ, Cfg::TI, Cfg::WAVES, launch, factor, eig,
+                  launch_bw, Cfg::MEAN_METRIC, Cfg::FACTOR_MIN_PAIRS};
+}
 
 // The geometry table: every whole-column row (pair_kernel.hpp) and every 2-D row (pair_kernel_2d.hpp: GC column lanes x 2
-// row lanes per pair, G = 2 GC lanes per pair) of configs.hpp; a problem of size m runs on the smallest MR >= m.  A launch
-// with few pairs (`pairs` = pairs per shard; < 0: not known, regular rows only) takes the small-launch row of that MR if
-// there is one (configs.hpp, SQFA_CONFIGS_F32_SMALL).  geometry_mode: sqfa_airm_options::geometry_policy of the call (0 by
-// pair count, 1 small-launch rows wherever one exists, -1 never) -- a per-call argument, no process-wide state.
+// row lanes per pair) of configs.hpp; a problem of size m runs on the smallest MR >= m.  A launch with few pairs (`pairs` =
+// pairs per shard; < 0: not known, regular rows only) takes the small-launch row of that MR if there is one (configs.hpp,
+// SQFA_CONFIGS_F32_SMALL).  geometry_mode: sqfa_airm_options::geometry_policy of the call (0 by pair count, 1 small-launch
+// rows wherever one exists, -1 never) -- a per-call argument, no process-wide state.
 static bool find_geometry(int m, int dtype, long pairs, Geometry* out, int geometry_mode = 0) {
   bool found = false;
   Geometry best{};
-  auto consider = [&](int dt, const Geometry& g) {
-    if (dt == dtype && m <= g.MR && (!found || g.MR < best.MR)) {
+  auto consider = [&](const Geometry& g) {
+    if (g.dtype == dtype && m <= g.MR && (!found || g.MR < best.MR)) {
       best = g;
       found = true;
     }
   };
-#define SQFA_ROW_F32(T, MR_, G_, CPL_, TJ_, WV_) consider(SQFA_F32, Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f32_##MR_, launch_factor_f32_##MR_, launch_classeig_f32_##MR_, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f32_##MR_});
-#define SQFA_ROW_F64(T, MR_, G_, CPL_, TJ_, WV_) consider(SQFA_F64, Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f64_##MR_, launch_factor_f64_##MR_, launch_classeig_f64_##MR_, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f64_##MR_});
-#define SQFA_ROW2D_F32(T, MR_, GC_, CPL_, TJ_, WV_, RS_) \
-  consider(SQFA_F32, Geometry{MR_, 2 * GC_, CPL_, TJ_, 64 / (2 * GC_), WV_, launch_pair2d_f32_##MR_, launch_factor2d_f32_##MR_, launch_classeig2d_f32_##MR_, PairCfg2D<float, MR_, GC_, CPL_, TJ_, WV_, RS_>::MEAN_METRIC, PairCfg2D<float, MR_, GC_, CPL_, TJ_, WV_, RS_>::FACTOR_MIN_PAIRS, launch_pair2d_bw_f32_##MR_});
-#define SQFA_ROW2D_F64(T, MR_, GC_, CPL_, TJ_, WV_, RS_) \
-  consider(SQFA_F64, Geometry{MR_, 2 * GC_, CPL_, TJ_, 64 / (2 * GC_), WV_, launch_pair2d_f64_##MR_, launch_factor2d_f64_##MR_, launch_classeig2d_f64_##MR_, PairCfg2D<double, MR_, GC_, CPL_, TJ_, WV_, RS_>::MEAN_METRIC, PairCfg2D<double, MR_, GC_, CPL_, TJ_, WV_, RS_>::FACTOR_MIN_PAIRS, launch_pair2d_bw_f64_##MR_});
+  // same padded size, more lanes per pair; the per-class eigen-decomposition stays the regular row's
+  auto consider_small = [&](Geometry g, long max_pairs) {
+    g.eig = best.eig;
+    if (g.dtype == dtype && g.MR == best.MR && (geometry_mode > 0 || pairs < max_pairs)) best = g;
+  };
+#define SQFA_ROW_F32(T, MR, G, CPL, TJ, WV) \
+  consider(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f32_##MR, launch_factor_f32_##MR, launch_classeig_f32_##MR, launch_pair_bw_f32_##MR));
+#define SQFA_ROW_F64(T, MR, G, CPL, TJ, WV) \
+  consider(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f64_##MR, launch_factor_f64_##MR, launch_classeig_f64_##MR, launch_pair_bw_f64_##MR));
+#define SQFA_ROW2D_F32(T, MR, GC, CPL, TJ, WV, RS) \
+  consider(make_geometry<PairCfg2D<T, MR, GC, CPL, TJ, WV, RS>>(launch_pair2d_f32_##MR, launch_factor2d_f32_##MR, launch_classeig2d_f32_##MR, launch_pair2d_bw_f32_##MR));
+#define SQFA_ROW2D_F64(T, MR, GC, CPL, TJ, WV, RS) \
+  consider(make_geometry<PairCfg2D<T, MR, GC, CPL, TJ, WV, RS>>(launch_pair2d_f64_##MR, launch_factor2d_f64_##MR, launch_classeig2d_f64_##MR, launch_pair2d_bw_f64_##MR));
+#define SQFA_ROW_F32S(T, MR, G, CPL, TJ, WV) \
+  consider_small(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f32s_##MR, launch_factor_f32s_##MR, nullptr, launch_pair_bw_f32s_##MR), small_launch_max_pairs(MR));
+#define SQFA_ROW_F64S(T, MR, G, CPL, TJ, WV) \
+  consider_small(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f64s_##MR, launch_factor_f64s_##MR, nullptr, launch_pair_bw_f64s_##MR), small_launch_max_pairs_f64(MR));
   SQFA_CONFIGS_F32(SQFA_ROW_F32)
   SQFA_CONFIGS_F64(SQFA_ROW_F64)
   SQFA_CONFIGS2D_F32(SQFA_ROW2D_F32)
   SQFA_CONFIGS2D_F64(SQFA_ROW2D_F64)
   if (found && geometry_mode >= 0 && pairs >= 0) {
-    // same padded size, more lanes per pair
-#define SQFA_ROW_F32S(T, MR_, G_, CPL_, TJ_, WV_)                                                                        \
-    if (dtype == SQFA_F32 && best.MR == MR_ && (geometry_mode > 0 || pairs < small_launch_max_pairs(MR_)))                \
-      best = Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f32s_##MR_, launch_factor_f32s_##MR_, best.eig, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<float, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f32s_##MR_};
     SQFA_CONFIGS_F32_SMALL(SQFA_ROW_F32S)
-#define SQFA_ROW_F64S(T, MR_, G_, CPL_, TJ_, WV_)                                                                        \
-    if (dtype == SQFA_F64 && best.MR == MR_ && (geometry_mode > 0 || pairs < small_launch_max_pairs_f64(MR_)))              \
-      best = Geometry{MR_, G_, CPL_, TJ_, 64 / G_, WV_, launch_pair_f64s_##MR_, launch_factor_f64s_##MR_, best.eig, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::MEAN_METRIC, PairCfg<double, MR_, G_, CPL_, TJ_, WV_>::FACTOR_MIN_PAIRS, launch_pair_bw_f64s_##MR_};
     SQFA_CONFIGS_F64_SMALL(SQFA_ROW_F64S)
   }
   if (found) *out = best;
@@ -137,13 +148,13 @@ struct WorkspaceLayout {
 };
 constexpr int kMeanParts = 32;   // class groups of the mean-class partial sums (mean_partial_kernel)
 
-// Tiles of a shard for tile width tj (same enumeration as the kernel's compact grid).
-static long shard_tiles(int nA, int nBeff, const Geometry& g, int tj, int self_mode, int shard_index, int shard_count) {
-  const int nbi = (nA + g.TI - 1) / g.TI, nbj = (nBeff + tj - 1) / tj;
+// Tiles of a shard for tiles of TI x tj classes (same enumeration as the kernels' compact grid).
+static long shard_tiles(int nA, int nBeff, int TI, int tj, int self_mode, int shard_index, int shard_count) {
+  const int nbi = (nA + TI - 1) / TI, nbj = (nBeff + tj - 1) / tj;
   long n = 0;
   for (int bi = 0; bi < nbi; ++bi) {
     int first;
-    n += shard_tiles_in_row(bi, tiles_in_row(bi, nbj, g.TI, tj, self_mode), shard_index, shard_count, &first);
+    n += shard_tiles_in_row(bi, tiles_in_row(bi, nbj, TI, tj, self_mode), shard_index, shard_count, &first);
   }
   return n;
 }
@@ -166,7 +177,7 @@ static int resident_workgroups() {
 static bool width_allowed(int nA, int nBeff, const Geometry& g, int tj, int self_mode) {
   if (tj == g.TJ) return true;
   if (tj < g.WV || tj < 1 || g.TJ % tj != 0) return false;
-  return shard_tiles(nA, nBeff, g, tj, self_mode, 0, 1) <= 16L * resident_workgroups();
+  return shard_tiles(nA, nBeff, g.TI, tj, self_mode, 0, 1) <= 16L * resident_workgroups();
 }
 
 // ... while the launch has fewer than SQFA_TILE_ROUNDS x the resident workgroups in tiles.  2 since round 3: a launch of
@@ -182,90 +193,116 @@ static bool width_allowed(int nA, int nBeff, const Geometry& g, int tj, int self
 static int choose_tile_width(int nA, int nBeff, const Geometry& g, int self_mode, int shard_count) {
   int tj = g.TJ;
   while (tj % 2 == 0 && width_allowed(nA, nBeff, g, tj / 2, self_mode) &&
-         shard_tiles(nA, nBeff, g, tj, self_mode, 0, 1) / shard_count < (long)SQFA_TILE_ROUNDS * resident_workgroups())
+         shard_tiles(nA, nBeff, g.TI, tj, self_mode, 0, 1) / shard_count < (long)SQFA_TILE_ROUNDS * resident_workgroups())
     tj /= 2;
   return tj;
 }
 
-// Workspace for one tiling (only_tj > 0: exactly the tile width a call will use), or for the narrowest
-// tiles any call may choose (only_tj == 0: most tiles, largest slab).
-static WorkspaceLayout layout(int nA, int nBeff, const Geometry& g, size_t esz, int self_mode, int only_tj = 0,
-                              int shard_count = 1) {
+// The tiling and the workspace of one call: what every size query and every pairwise entry point derives, once, from
+// (nA, nB, m, dtype, shard_count, geometry policy).  m <= 64 runs a register row of the geometry table (`g`), 64 < m <= 128
+// the LDS pair path (pair_kernel_lds.hip: nothing of `g` is involved, no class factor pass).
+struct PairPlan {
+  int nA, m, dtype, shard_count;
+  int nBeff, self_mode;  // B classes (self mode, nB == 0: the A classes)
+  size_t esz;
+  bool lds;
+  int MR, TI, TJ, tj;    // padded size; A classes per tile; the widest tile and the width this call uses (B classes)
+  int nbi, nbj;          // tile rows, and tile columns of width tj
+  Geometry g;            // register rows only
   WorkspaceLayout w;
-  const size_t mat = (size_t)g.MR * g.MR * esz;
+};
+
+// Workspace of a register row for exactly the plan's tile width, or (any_width) for the narrowest tiles any call may
+// choose: most tiles, largest slab.
+static WorkspaceLayout layout(const PairPlan& pl, bool any_width) {
+  WorkspaceLayout w;
+  const Geometry& g = pl.g;
+  const size_t mat = (size_t)g.MR * g.MR * pl.esz;
   const size_t tri = (size_t)g.MR * (g.MR + 1) / 2;
-  const size_t nbi = (nA + g.TI - 1) / g.TI;
   size_t slab = 0, tiles = 0;
-  for (int tj = g.TJ; tj >= 1 && width_allowed(nA, nBeff, g, tj, self_mode); tj /= 2) {
-    if (only_tj > 0 && tj != only_tj) {
+  for (int tj = g.TJ; tj >= 1 && width_allowed(pl.nA, pl.nBeff, g, tj, pl.self_mode); tj /= 2) {
+    if (!any_width && tj != pl.tj) {
       if (tj % 2) break;
       continue;
     }
     // the slab holds the tiles one shard owns (compact numbering): the largest shard decides
     size_t owned = 0;
-    for (int r = 0; r < shard_count; ++r)
-      owned = std::max(owned, (size_t)shard_tiles(nA, nBeff, g, tj, self_mode, r, shard_count));
-    slab = std::max(slab, owned * (size_t)(g.TI + tj) * tri * esz);
+    for (int r = 0; r < pl.shard_count; ++r)
+      owned = std::max(owned, (size_t)shard_tiles(pl.nA, pl.nBeff, g.TI, tj, pl.self_mode, r, pl.shard_count));
+    slab = std::max(slab, owned * (size_t)(g.TI + tj) * tri * pl.esz);
     tiles = std::max(tiles, owned);
     if (tj % 2) break;
   }
   size_t o = 0;
-  w.off_lt = o;   o = align_up(o + (size_t)nA * mat);
-  w.off_linv = o; o = align_up(o + (size_t)nBeff * mat);  // (packed for MR >= 32: uses about half)
+  w.off_lt = o;   o = align_up(o + (size_t)pl.nA * mat);
+  w.off_linv = o; o = align_up(o + (size_t)pl.nBeff * mat);  // (packed for MR >= 32: uses about half)
   w.off_slab = o; o = align_up(o + slab);
-  w.off_loss = o; o = align_up(o + tiles * esz);
+  w.off_loss = o; o = align_up(o + tiles * pl.esz);
   w.off_flag = o; o = align_up(o + tiles * 2 * sizeof(int));
-  w.off_rows = o; o = align_up(o + (nbi + 1) * sizeof(int));
+  w.off_rows = o; o = align_up(o + ((size_t)pl.nbi + 1) * sizeof(int));
   // mean-metric factor pass: kMeanParts partial sums of the A classes (MR x MR doubles each), then Lbar^-1 (MR x MR doubles)
   w.off_mean = o; o = align_up(o + (size_t)(kMeanParts + 1) * g.MR * g.MR * sizeof(double));
   w.total = o;
   return w;
 }
-
-// ---- 64 < m <= 128: tiling and workspace of the LDS pair path (pair_kernel_lds.hip) ------------------------------------
-// One workgroup per tile of TI x TJ pairs, the pairs one after the other.  Tiles start at 16 x 16 (the slab holds
-// P (1/TI + 1/TJ) lower triangles for P pairs: 2.1 GB at C = 1000, m = 128, float32) and are halved, TJ first, while the
-// job has fewer than kLdsMinTiles tiles, down to 2 x 2 (C = 100: 1 275 tiles).  The tiling depends on (nA, nB, m) only:
-// every shard of a job uses the same one.  Nothing of Geometry / find_geometry is involved.
-constexpr long kLdsMinTiles = 1024;  // 4 x the 256 CUs
-struct LdsTiling {
-  int MR, TI, TJ;
-};
-static long lds_tiles(int nA, int nBeff, int TI, int TJ, int self_mode, int shard_index, int shard_count) {
-  const int nbi = (nA + TI - 1) / TI, nbj = (nBeff + TJ - 1) / TJ;
-  long n = 0;
-  for (int bi = 0; bi < nbi; ++bi) {
-    int first;
-    n += shard_tiles_in_row(bi, tiles_in_row(bi, nbj, TI, TJ, self_mode), shard_index, shard_count, &first);
-  }
-  return n;
-}
-static LdsTiling lds_tiling(int nA, int nBeff, int m, int self_mode) {
-  LdsTiling t{lds_padded_size(m), 16, 16};
-  while (t.TI * t.TJ > 4 && lds_tiles(nA, nBeff, t.TI, t.TJ, self_mode, 0, 1) < kLdsMinTiles) {
-    if (t.TJ >= t.TI) t.TJ /= 2;
-    else t.TI /= 2;
-  }
-  return t;
-}
-// shard_count: the slab holds the tiles of the largest shard (1: every tile, enough for any shard count)
-static WorkspaceLayout layout_lds(int nA, int nBeff, const LdsTiling& t, size_t esz, int self_mode, int shard_count) {
+// Workspace of the LDS path: the slab holds the tiles of the largest shard (one shard: every tile, enough for any shard count)
+static WorkspaceLayout layout_lds(const PairPlan& pl) {
   WorkspaceLayout w;
   size_t owned = 0;
-  for (int r = 0; r < shard_count; ++r)
-    owned = std::max(owned, (size_t)lds_tiles(nA, nBeff, t.TI, t.TJ, self_mode, r, shard_count));
-  const size_t tri = (size_t)t.MR * (t.MR + 1) / 2;
-  const size_t nbi = (nA + t.TI - 1) / t.TI;
+  for (int r = 0; r < pl.shard_count; ++r)
+    owned = std::max(owned, (size_t)shard_tiles(pl.nA, pl.nBeff, pl.TI, pl.tj, pl.self_mode, r, pl.shard_count));
+  const size_t tri = (size_t)pl.MR * (pl.MR + 1) / 2;
   size_t o = 0;
-  w.off_lt = o;   o = align_up(o + (size_t)nA * t.MR * t.MR * esz);
-  w.off_linv = o; o = align_up(o + (size_t)nBeff * tri * esz);  // packed lower triangles
-  w.off_slab = o; o = align_up(o + owned * (size_t)(t.TI + t.TJ) * tri * esz);
-  w.off_loss = o; o = align_up(o + owned * esz);
+  w.off_lt = o;   o = align_up(o + (size_t)pl.nA * pl.MR * pl.MR * pl.esz);
+  w.off_linv = o; o = align_up(o + (size_t)pl.nBeff * tri * pl.esz);  // packed lower triangles
+  w.off_slab = o; o = align_up(o + owned * (size_t)(pl.TI + pl.tj) * tri * pl.esz);
+  w.off_loss = o; o = align_up(o + owned * pl.esz);
   w.off_flag = o; o = align_up(o + owned * 2 * sizeof(int));
-  w.off_rows = o; o = align_up(o + (nbi + 1) * sizeof(int));
+  w.off_rows = o; o = align_up(o + ((size_t)pl.nbi + 1) * sizeof(int));
   w.off_mean = o;  // no class factor pass above 64
   w.total = o;
   return w;
+}
+
+// LDS path: one workgroup per tile of TI x TJ pairs, the pairs one after the other.  Tiles start at 16 x 16 (the slab holds
+// P (1/TI + 1/TJ) lower triangles for P pairs: 2.1 GB at C = 1000, m = 128, float32) and are halved, TJ first, while the
+// job has fewer than kLdsMinTiles tiles, down to 2 x 2 (C = 100: 1 275 tiles).  The tiling depends on (nA, nB, m) only:
+// every shard of a job uses the same one.
+constexpr long kLdsMinTiles = 1024;  // 4 x the 256 CUs
+
+// false: no kernel for matrices of size m.  nB == 0: self mode.  geometry_mode as find_geometry; any_width: see layout().
+static bool make_plan(int nA, int nB, int m, int dtype, int shard_count, int geometry_mode, PairPlan* out,
+                      bool any_width = false) {
+  PairPlan pl{};
+  pl.nA = nA;
+  pl.m = m;
+  pl.dtype = dtype;
+  pl.shard_count = shard_count;
+  pl.self_mode = nB == 0 ? 1 : 0;
+  pl.nBeff = nB == 0 ? nA : nB;
+  pl.esz = dtype == SQFA_F32 ? 4 : 8;
+  pl.lds = m > kRegMaxDim;
+  if (pl.lds) {
+    if (m > kLdsMaxDim) return false;
+    pl.MR = lds_padded_size(m);
+    pl.TI = pl.TJ = 16;
+    while (pl.TI * pl.TJ > 4 && shard_tiles(nA, pl.nBeff, pl.TI, pl.TJ, pl.self_mode, 0, 1) < kLdsMinTiles) {
+      if (pl.TJ >= pl.TI) pl.TJ /= 2;
+      else pl.TI /= 2;
+    }
+    pl.tj = pl.TJ;
+  } else {
+    if (!find_geometry(m, dtype, pair_count(nA, nB, shard_count), &pl.g, geometry_mode)) return false;
+    pl.MR = pl.g.MR;
+    pl.TI = pl.g.TI;
+    pl.TJ = pl.g.TJ;
+    pl.tj = choose_tile_width(nA, pl.nBeff, pl.g, pl.self_mode, shard_count);
+  }
+  pl.nbi = (nA + pl.TI - 1) / pl.TI;
+  pl.nbj = (pl.nBeff + pl.tj - 1) / pl.tj;
+  pl.w = pl.lds ? layout_lds(pl) : layout(pl, any_width);
+  *out = pl;
+  return true;
 }
 
 // ---- K0: per-class Cholesky factor and its inverse (always evaluated in double) ----------
@@ -335,13 +372,10 @@ __global__ __launch_bounds__(256) void cholesky_kernel(const T* __restrict__ S, 
     }
   }
   __syncthreads();
-#ifndef SQFA_CHOL_ONE_BARRIER
-#define SQFA_CHOL_ONE_BARRIER 1
-#endif
-#if SQFA_CHOL_ONE_BARRIER
   // Right-looking elimination on the UNSCALED columns, one workgroup barrier per pivot (round 3; three before: pivot, scaled
   // column, trailing update): step k only reads column k and the pivot, which no later step writes, and subtracts
   // a[r][k] a[c][k] / a[k][k] from the trailing block; the columns are scaled by 1/sqrt(pivot) once at the end.
+  // (bw_prologue_kernel repeats this loop on its own array: as one shared routine the two kernels compiled to other code.)
   for (int k = 0; k < m; ++k) {
     const double akk = a[k][k];
     // a non-positive or NaN pivot poisons the trailing block: NaN here and everywhere downstream, as with the scaled form
@@ -362,24 +396,6 @@ __global__ __launch_bounds__(256) void cholesky_kernel(const T* __restrict__ S, 
     const int r = e / m, k = e % m;
     if (k <= r) a[r][k] *= rd[k];  // r == k: akk * rs = sqrt(akk)
   }
-#else
-  for (int k = 0; k < m; ++k) {
-    // a non-positive or NaN pivot gives NaN here and everywhere downstream
-    const double rs = fast_rsqrt(a[k][k]);
-    __syncthreads();
-    for (int r = k + t; r < m; r += 256) {
-      a[r][k] *= rs;  // r == k: akk * rs = sqrt(akk)
-      if (r == k) rd[k] = rs;
-    }
-    __syncthreads();
-    // trailing update of the lower triangle: entries (r, c2) with k < c2 <= r < m
-    const int n = m - k - 1;
-    for (int e = t; e < n * n; e += 256) {
-      const int r = k + 1 + e / n, c2 = k + 1 + e % n;
-      if (c2 <= r) a[r][c2] -= a[r][k] * a[c2][k];
-    }
-  }
-#endif
   __syncthreads();
   // inverse X = L^-1, row by row; 4 lanes per column (always inside one wave, so rows only
   // need the wave's own program order, no workgroup barrier)
@@ -433,6 +449,12 @@ __device__ inline bool tile_processed(const PairParams& p, int bi, int bj, int T
 #ifndef SQFA_K2_THREADS
 #define SQFA_K2_THREADS 512  // 1024 threads (7 summation groups per class instead of 3): 29 vs 28 us at c3, no gain
 #endif
+// Lower-triangle entries per workgroup of finalize_kernel, and its workgroups per class: small sizes (TRI <= 256, m <= 22)
+// keep one workgroup per class.  The kernel and its launch (launch_finalize) both take the numbers from here.
+__host__ __device__ constexpr int finalize_epb(int tri) { return tri <= 256 ? tri : 128; }
+__host__ __device__ constexpr int finalize_bpc(int tri) { return (tri + finalize_epb(tri) - 1) / finalize_epb(tri); }
+// the same for finalize_bw_kernel: 256 consecutive entries per workgroup
+__host__ __device__ constexpr int finalize_bw_bpc(int tri) { return (tri + 255) / 256; }
 template <typename T>
 __global__ __launch_bounds__(SQFA_K2_THREADS) void finalize_kernel(const PairParams p, int TI, int TJ, int MR,
                                                        T* __restrict__ gradA, T* __restrict__ gradB,
@@ -459,8 +481,8 @@ __global__ __launch_bounds__(SQFA_K2_THREADS) void finalize_kernel(const PairPar
   // ~190 tiles serially: 275 us at C=1000, m=32.)
   // Small sizes (TRI <= 256, m <= 22) keep one workgroup per class (splitting 136 entries over two
   // workgroups cost 41 vs 30 us at m=16); m=32: 289 -> 199 us.
-  const int EPB = TRI <= 256 ? TRI : 128, NG = SQFA_K2_THREADS / EPB;
-  const int BPC = (TRI + EPB - 1) / EPB;
+  const int EPB = finalize_epb(TRI), NG = SQFA_K2_THREADS / EPB;
+  const int BPC = finalize_bpc(TRI);
   if (b < n_cls * BPC) {
     if (!p.want_grad) return;
     const int cls = b / BPC, e_in = tid % EPB, idx = (b % BPC) * EPB + e_in, grp = tid / EPB;
@@ -676,7 +698,7 @@ __global__ __launch_bounds__(256) void bw_prologue_kernel(const T* __restrict__ 
 template <typename T>
 __global__ __launch_bounds__(256) void finalize_bw_kernel(const PairParams p, int TI, int TJ, int MR, T* __restrict__ gradA,
                                                           double* __restrict__ G, double* __restrict__ hsum) {
-  const int TRI = MR * (MR + 1) / 2, BPC = (TRI + 255) / 256;
+  const int TRI = MR * (MR + 1) / 2, BPC = finalize_bw_bpc(TRI);
   const int b = blockIdx.x, cls = b / BPC, idx = (b % BPC) * 256 + threadIdx.x;
   const bool a_side = cls < p.nA;
   const int c = a_side ? cls : cls - p.nA;
@@ -851,6 +873,125 @@ static int fail(int code, const char* what, hipError_t e) {
   return code;
 }
 
+static int clamp_policy(int v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); }
+static bool known_dtype(int dtype) { return dtype == SQFA_F32 || dtype == SQFA_F64; }
+
+// ---- the stages of a pairwise call, shared by both metrics and both size ranges -------------------------------------------
+// Argument checks: SQFA_OK, or the error code with the message set.
+static int validate_pair_call(const void* A, int nA, const void* B, int nB, int m, int dtype, int shard_index, int shard_count,
+                              const void* workspace) {
+  g_last_error[0] = 0;
+  if (A == nullptr || nA < 1 || m < 1 || nB < 0 || workspace == nullptr) return fail(SQFA_ERR_BAD_ARGUMENT, "null/size argument", hipSuccess);
+  if (!known_dtype(dtype)) return fail(SQFA_ERR_BAD_ARGUMENT, "dtype", hipSuccess);
+  if ((B == nullptr) != (nB == 0)) return fail(SQFA_ERR_BAD_ARGUMENT, "B and nB disagree", hipSuccess);
+  if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail(SQFA_ERR_BAD_ARGUMENT, "shard", hipSuccess);
+  if (B == nullptr && nA < 2) return fail(SQFA_ERR_BAD_ARGUMENT, "self mode needs at least two classes", hipSuccess);
+  if (m > kLdsMaxDim) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+  return SQFA_OK;
+}
+
+// The parameter block of a call on the workspace `ws`; the caller adds what belongs to its metric alone (affine-invariant:
+// EW, eig_out, mean_linv; Bures-Wasserstein: trA, trB, slab_h).
+static PairParams make_pair_params(const PairPlan& pl, char* ws, int shard_index, double scale, double eps, int sqrt_mode,
+                                   const void* pair_weights, double uniform_weight, bool want_grad, void* dist_out,
+                                   const sqfa_airm_options* options) {
+  PairParams p;
+  memset(&p, 0, sizeof(p));
+  p.LT = ws + pl.w.off_lt;
+  p.Linv = ws + pl.w.off_linv;
+  p.W = pair_weights;
+  p.slab_grad = ws + pl.w.off_slab;
+  p.slab_loss = ws + pl.w.off_loss;
+  p.slab_flag = reinterpret_cast<int*>(ws + pl.w.off_flag);
+  p.row_start = reinterpret_cast<int*>(ws + pl.w.off_rows);
+  p.dist_out = dist_out;
+  p.sweep_counter = options ? options->sweep_counter : nullptr;
+  p.nA = pl.nA;
+  p.nB = pl.nBeff;
+  p.m = pl.m;
+  p.self_mode = pl.self_mode;
+  p.sqrt_mode = sqrt_mode ? 1 : 0;
+  p.want_grad = want_grad ? 1 : 0;
+  p.shard_index = shard_index;
+  p.shard_count = pl.shard_count;
+  p.nbi = pl.nbi;
+  p.nbj = pl.nbj;
+  p.tj = pl.tj;
+  p.factor_mode = pl.lds ? -1 : (options ? clamp_policy(options->class_factor_policy) : 0);  // no class factor pass above 64
+  p.scale = scale;
+  p.eps = eps;
+  p.uniform_weight = uniform_weight;
+  p.scale_f = (float)scale;
+  p.eps_f = (float)eps;
+  p.uniform_weight_f = (float)uniform_weight;
+  return p;
+}
+
+// cholesky_kernel for n classes S (n, m, m) of element type `dtype`, LDS sized for the size class of m (m <= 64).
+// mean_parts != NULL: one more block factorises the mean class (see the kernel).
+static void launch_cholesky(int dtype, int m, hipStream_t stream, const void* S, int n, int MR, void* LT, void* Linv,
+                            int* row_start, const PairParams& p, int TI, const double* mean_parts = nullptr, int n_parts = 0,
+                            double* mean_linv = nullptr) {
+  const int blocks = n + (mean_parts != nullptr ? 1 : 0);
+  auto launch = [&](auto zero) {
+    using T = decltype(zero);
+    auto kernel = m <= 16 ? cholesky_kernel<T, 16> : (m <= 32 ? cholesky_kernel<T, 32> : cholesky_kernel<T, 64>);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, static_cast<const T*>(S), m, MR, static_cast<T*>(LT),
+                       static_cast<T*>(Linv), row_start, p, TI, n, mean_parts, n_parts, mean_linv);
+  };
+  if (dtype == SQFA_F32) launch(0.0f);
+  else launch(0.0);
+}
+
+// K0 for one side of a call: the factor (LT, may be NULL) and the inverse factor (Linv, may be NULL) of n classes;
+// row_start != NULL: the launch also writes the slab slot table.
+static hipError_t launch_factors(const PairPlan& pl, const PairParams& p, hipStream_t stream, const void* S, int n, void* LT,
+                                 void* Linv, int* row_start, const double* mean_parts = nullptr, int n_parts = 0,
+                                 double* mean_linv = nullptr) {
+  if (pl.lds) return launch_lds_prologue(pl.dtype == SQFA_F64, S, n, pl.m, pl.MR, LT, Linv, row_start, p, pl.TI, stream);
+  launch_cholesky(pl.dtype, pl.m, stream, S, n, pl.MR, LT, Linv, row_start, p, pl.TI, mean_parts, n_parts, mean_linv);
+  return hipGetLastError();
+}
+
+// Runs `launch` (K1) between two events on the stream when profiling is on (sqfa_airm_profile).  Event records do not
+// belong in a captured graph: eager launches only.
+template <typename F>
+static hipError_t launch_profiled(hipStream_t stream, F launch) {
+  bool prof = g_profile.load();
+  if (prof) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) prof = false;
+  }
+  EventPair ev{};
+  if (prof) {
+    (void)hipEventCreate(&ev.a);
+    (void)hipEventCreate(&ev.b);
+    (void)hipEventRecord(ev.a, stream);
+  }
+  const hipError_t e = launch();
+  if (prof) {
+    (void)hipEventRecord(ev.b, stream);
+    std::lock_guard<std::mutex> lock(g_events_mutex);
+    g_events.push_back(ev);
+  }
+  return e;
+}
+
+// K2: finalize_kernel, finalize_bpc workgroups per class and one for the loss, the flags and the diagonals.
+static hipError_t launch_finalize(const PairPlan& pl, const PairParams& p, void* gradA, void* gradB, void* loss, int* nonfinite,
+                                  hipStream_t stream) {
+  const int n_cls = p.nA + (p.self_mode ? 0 : p.nB);
+  const dim3 grid(n_cls * finalize_bpc(pl.MR * (pl.MR + 1) / 2) + 1);
+  auto launch = [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(finalize_kernel<T>, grid, dim3(SQFA_K2_THREADS), 0, stream, p, pl.TI, pl.tj, pl.MR, static_cast<T*>(gradA),
+                       static_cast<T*>(gradB), static_cast<T*>(loss), nonfinite);
+  };
+  if (pl.dtype == SQFA_F32) launch(0.0f);
+  else launch(0.0);
+  return hipGetLastError();
+}
+
 }  // namespace sqfa
 
 using namespace sqfa;
@@ -907,138 +1048,23 @@ int sqfa_project_profile_read(double* kernel_ms_total, int* launches) {
 
 int sqfa_airm_tiling(int nA, int nB, int m, int dtype, int* tile_i, int* tile_j, int* n_tiles_i,
                      int* n_tiles_j, int* padded_m) {
-  if (nA < 1 || nB < 0 || m < 1 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return SQFA_ERR_BAD_ARGUMENT;
-  if (m > kRegMaxDim) {
-    if (m > kLdsMaxDim) return SQFA_ERR_UNSUPPORTED_M;
-    const int nBeff = nB == 0 ? nA : nB;
-    const LdsTiling t = lds_tiling(nA, nBeff, m, nB == 0 ? 1 : 0);
-    if (tile_i) *tile_i = t.TI;
-    if (tile_j) *tile_j = t.TJ;
-    if (n_tiles_i) *n_tiles_i = (nA + t.TI - 1) / t.TI;
-    if (n_tiles_j) *n_tiles_j = (nBeff + t.TJ - 1) / t.TJ;
-    if (padded_m) *padded_m = t.MR;
-    return SQFA_OK;
-  }
-  Geometry g;
-  if (!find_geometry(m, dtype, pair_count(nA, nB, 1), &g)) return SQFA_ERR_UNSUPPORTED_M;  // the geometry of an unsharded call
-  const int nBeff = nB == 0 ? nA : nB;
-  if (tile_i) *tile_i = g.TI;
-  if (tile_j) *tile_j = g.TJ;
-  if (n_tiles_i) *n_tiles_i = (nA + g.TI - 1) / g.TI;
-  if (n_tiles_j) *n_tiles_j = (nBeff + g.TJ - 1) / g.TJ;
-  if (padded_m) *padded_m = g.MR;
+  if (nA < 1 || nB < 0 || m < 1 || !known_dtype(dtype)) return SQFA_ERR_BAD_ARGUMENT;
+  PairPlan pl;
+  if (!make_plan(nA, nB, m, dtype, 1, 0, &pl)) return SQFA_ERR_UNSUPPORTED_M;  // the widest tiles of an unsharded call
+  if (tile_i) *tile_i = pl.TI;
+  if (tile_j) *tile_j = pl.TJ;
+  if (n_tiles_i) *n_tiles_i = pl.nbi;
+  if (n_tiles_j) *n_tiles_j = (pl.nBeff + pl.TJ - 1) / pl.TJ;
+  if (padded_m) *padded_m = pl.MR;
   return SQFA_OK;
 }
 
 size_t sqfa_airm_workspace_bytes(int nA, int nB, int m, int dtype) {
-  int ti, tj, nbi, nbj, mr;
-  if (sqfa_airm_tiling(nA, nB, m, dtype, &ti, &tj, &nbi, &nbj, &mr) != SQFA_OK) return 0;
-  const int nBeff = nB == 0 ? nA : nB;
-  if (m > kRegMaxDim)
-    return layout_lds(nA, nBeff, lds_tiling(nA, nBeff, m, nB == 0 ? 1 : 0), dtype == SQFA_F32 ? 4 : 8, nB == 0 ? 1 : 0, 1).total;
-  // enough for any shard count: the regular row's and the small-launch row's layouts both fit
-  Geometry g;
-  find_geometry(m, dtype, -1, &g, -1);   // the regular row ...
-  size_t need = layout(nA, nBeff, g, dtype == SQFA_F32 ? 4 : 8, nB == 0 ? 1 : 0).total;
-  find_geometry(m, dtype, 0, &g, 1);     // ... and the small-launch row of the size, whatever policy a call will carry
-  need = std::max(need, layout(nA, nBeff, g, dtype == SQFA_F32 ? 4 : 8, nB == 0 ? 1 : 0).total);
-  return need;
-}
-
-// 64 < m <= 128 (arguments already checked): K0L, K1L (pair_kernel_lds.hip), K2 unchanged.  The class factor pass and
-// the geometry / class factor / mean metric policies do not apply here.
-static int pairwise_lds(const void* A, int nA, const void* B, int nB, int m, int dtype, double scale, double eps,
-                        int sqrt_mode, const void* pair_weights, double uniform_weight, int shard_index, int shard_count,
-                        void* loss_out, void* gradA_out, void* gradB_out, void* dist_out, void* eig_out,
-                        int* nonfinite_out, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                        const void* eig_weights, unsigned long long* sweep_counter) {
-  const bool self_mode = (B == nullptr);
-  const int nBeff = self_mode ? nA : nB;
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
-  const int f64 = dtype == SQFA_F64 ? 1 : 0;
-  const LdsTiling t = lds_tiling(nA, nBeff, m, self_mode ? 1 : 0);
-  const WorkspaceLayout w = layout_lds(nA, nBeff, t, esz, self_mode ? 1 : 0, shard_count);
-  if (workspace_bytes < w.total) return fail(SQFA_ERR_WORKSPACE, "workspace too small", hipSuccess);
-  char* ws = static_cast<char*>(workspace);
-
-  PairParams p;
-  memset(&p, 0, sizeof(p));
-  p.LT = ws + w.off_lt;
-  p.Linv = ws + w.off_linv;
-  p.W = pair_weights;
-  p.EW = eig_weights;
-  p.slab_grad = ws + w.off_slab;
-  p.slab_loss = ws + w.off_loss;
-  p.slab_flag = reinterpret_cast<int*>(ws + w.off_flag);
-  p.row_start = reinterpret_cast<int*>(ws + w.off_rows);
-  p.dist_out = dist_out;
-  p.eig_out = eig_out;
-  p.sweep_counter = sweep_counter;
-  p.nA = nA;
-  p.nB = nBeff;
-  p.m = m;
-  p.self_mode = self_mode ? 1 : 0;
-  p.sqrt_mode = sqrt_mode ? 1 : 0;
-  p.want_grad = gradA_out != nullptr ? 1 : 0;
-  p.shard_index = shard_index;
-  p.shard_count = shard_count;
-  p.nbi = (nA + t.TI - 1) / t.TI;
-  p.nbj = (nBeff + t.TJ - 1) / t.TJ;
-  p.tj = t.TJ;
-  p.factor_mode = -1;
-  p.scale = scale;
-  p.eps = eps;
-  p.uniform_weight = uniform_weight;
-  p.scale_f = (float)scale;
-  p.eps_f = (float)eps;
-  p.uniform_weight_f = (float)uniform_weight;
-
-  // K0L: factors (the first launch also writes the slab slot table)
-  hipError_t e;
-  if (self_mode) {
-    e = launch_lds_prologue(f64, A, nA, m, t.MR, ws + w.off_lt, ws + w.off_linv, p.row_start, p, t.TI, stream);
-  } else {
-    e = launch_lds_prologue(f64, A, nA, m, t.MR, ws + w.off_lt, nullptr, p.row_start, p, t.TI, stream);
-    if (e == hipSuccess) e = launch_lds_prologue(f64, B, nB, m, t.MR, nullptr, ws + w.off_linv, nullptr, p, t.TI, stream);
-  }
-  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "cholesky_lds_kernel", e);
-
-  // K1L: pair tiles
-  EventPair ev{};
-  bool prof = g_profile.load();
-  if (prof) {  // event records do not belong in a captured graph: profile eager launches only
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) prof = false;
-  }
-  if (prof) {
-    (void)hipEventCreate(&ev.a);
-    (void)hipEventCreate(&ev.b);
-    (void)hipEventRecord(ev.a, stream);
-  }
-  e = launch_pair_lds(f64, p, t.TI, t.MR, stream);
-  if (prof) {
-    (void)hipEventRecord(ev.b, stream);
-    std::lock_guard<std::mutex> lock(g_events_mutex);
-    g_events.push_back(ev);
-  }
-  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "pair_lds_kernel", e);
-
-  // K2: slab reduction (finalize_kernel, unchanged)
-  const int n_cls = nA + (self_mode ? 0 : nB);
-  const int k2_tri = t.MR * (t.MR + 1) / 2;
-  const int k2_bpc = (k2_tri + 127) / 128;  // workgroups per class (finalize_kernel's EPB; TRI > 256 here)
-  if (dtype == SQFA_F32) {
-    hipLaunchKernelGGL(finalize_kernel<float>, dim3(n_cls * k2_bpc + 1), dim3(SQFA_K2_THREADS), 0, stream, p, t.TI, t.TJ, t.MR,
-                       static_cast<float*>(gradA_out), static_cast<float*>(gradB_out),
-                       static_cast<float*>(loss_out), nonfinite_out);
-  } else {
-    hipLaunchKernelGGL(finalize_kernel<double>, dim3(n_cls * k2_bpc + 1), dim3(SQFA_K2_THREADS), 0, stream, p, t.TI, t.TJ, t.MR,
-                       static_cast<double*>(gradA_out), static_cast<double*>(gradB_out),
-                       static_cast<double*>(loss_out), nonfinite_out);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_kernel", e);
-  return SQFA_OK;
+  if (nA < 1 || nB < 0 || m < 1 || !known_dtype(dtype)) return 0;
+  // enough for any shard count, tile width and geometry policy: the regular row's and the small-launch row's layouts both fit
+  PairPlan regular, small;
+  if (!make_plan(nA, nB, m, dtype, 1, -1, &regular, true) || !make_plan(nA, nB, m, dtype, 1, 1, &small, true)) return 0;
+  return std::max(regular.w.total, small.w.total);
 }
 
 static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, int dtype, double scale,
@@ -1048,155 +1074,48 @@ static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, in
                          void* workspace, size_t workspace_bytes, void* stream_, const void* eig_weights,
                          const sqfa_airm_options* options) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  auto clamp = [](int v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); };
-  const int geometry_mode = options ? clamp(options->geometry_policy) : 0;
-  const int factor_mode = options ? clamp(options->class_factor_policy) : 0;
-  const int mean_mode = options ? clamp(options->mean_metric_policy) : 0;
-  g_last_error[0] = 0;
-  if (A == nullptr || nA < 1 || m < 1 || nB < 0 || workspace == nullptr) return fail(SQFA_ERR_BAD_ARGUMENT, "null/size argument", hipSuccess);
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return fail(SQFA_ERR_BAD_ARGUMENT, "dtype", hipSuccess);
-  if ((B == nullptr) != (nB == 0)) return fail(SQFA_ERR_BAD_ARGUMENT, "B and nB disagree", hipSuccess);
-  if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail(SQFA_ERR_BAD_ARGUMENT, "shard", hipSuccess);
-  const bool self_mode = (B == nullptr);
-  if (self_mode && nA < 2) return fail(SQFA_ERR_BAD_ARGUMENT, "self mode needs at least two classes", hipSuccess);
-  if (m > kRegMaxDim) {
-    if (m > kLdsMaxDim) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
-    return pairwise_lds(A, nA, B, nB, m, dtype, scale, eps, sqrt_mode, pair_weights, uniform_weight, shard_index,
-                        shard_count, loss_out, gradA_out, gradB_out, dist_out, eig_out, nonfinite_out, workspace,
-                        workspace_bytes, stream, eig_weights, options ? options->sweep_counter : nullptr);
-  }
-  Geometry g;
-  if (!find_geometry(m, dtype, pair_count(nA, nB, shard_count), &g, geometry_mode)) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
-  const int nBeff = self_mode ? nA : nB;
-  // tile width: halve while a shard's launch would leave workgroup slots empty.  Decided from
-  // the TOTAL tile count and shard_count only, so that every shard of a job picks the same
-  // tiling (tile ownership (bi + bj) % shard_count is defined on that tiling).
-  const int tj = choose_tile_width(nA, nBeff, g, self_mode ? 1 : 0, shard_count);
-  const int nbi = (nA + g.TI - 1) / g.TI, nbj = (nBeff + tj - 1) / tj;
-  const WorkspaceLayout w = layout(nA, nBeff, g, esz, self_mode ? 1 : 0, tj, shard_count);
-  if (workspace_bytes < w.total) return fail(SQFA_ERR_WORKSPACE, "workspace too small", hipSuccess);
+  const int rc = validate_pair_call(A, nA, B, nB, m, dtype, shard_index, shard_count, workspace);
+  if (rc != SQFA_OK) return rc;
+  PairPlan pl;
+  if (!make_plan(nA, nB, m, dtype, shard_count, options ? clamp_policy(options->geometry_policy) : 0, &pl))
+    return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+  if (workspace_bytes < pl.w.total) return fail(SQFA_ERR_WORKSPACE, "workspace too small", hipSuccess);
   char* ws = static_cast<char*>(workspace);
-
-  PairParams p;
-  memset(&p, 0, sizeof(p));
-  p.LT = ws + w.off_lt;
-  p.Linv = ws + w.off_linv;
-  p.W = pair_weights;
+  PairParams p = make_pair_params(pl, ws, shard_index, scale, eps, sqrt_mode, pair_weights, uniform_weight, gradA_out != nullptr,
+                                  dist_out, options);
   p.EW = eig_weights;
-  p.slab_grad = ws + w.off_slab;
-  p.slab_loss = ws + w.off_loss;
-  p.slab_flag = reinterpret_cast<int*>(ws + w.off_flag);
-  p.row_start = reinterpret_cast<int*>(ws + w.off_rows);
-  p.dist_out = dist_out;
   p.eig_out = eig_out;
-  p.sweep_counter = options ? options->sweep_counter : nullptr;
-  p.nA = nA;
-  p.nB = nBeff;
-  p.m = m;
-  p.self_mode = self_mode ? 1 : 0;
-  p.sqrt_mode = sqrt_mode ? 1 : 0;
-  p.want_grad = gradA_out != nullptr ? 1 : 0;
-  p.shard_index = shard_index;
-  p.shard_count = shard_count;
-  p.nbi = nbi;
-  p.nbj = nbj;
-  p.tj = tj;
-  p.factor_mode = factor_mode;
-  p.scale = scale;
-  p.eps = eps;
-  p.uniform_weight = uniform_weight;
-  p.scale_f = (float)scale;
-  p.eps_f = (float)eps;
-  p.uniform_weight_f = (float)uniform_weight;
 
-  // K0: factors
-  // mean-metric factor pass (class_factor_mean_kernel): will K0b run, and on a size that has it?  Same rule as
-  // launch_class_factors (the decision depends on (nA, nB, shard count, options) only: every shard of a job decides alike).
-  const long pairs_per_shard = pair_count(nA, nB, shard_count);
-  const bool want_mean = g.mean_metric && mean_mode > 0 && factor_mode >= 0 &&
-                         (factor_mode > 0 || pairs_per_shard >= g.factor_min_pairs) && nA >= 2;
-  double* mean_parts = reinterpret_cast<double*>(ws + w.off_mean);
-  double* mean_linv = mean_parts + (size_t)kMeanParts * g.MR * g.MR;
+  // K0: factors.  Mean-metric factor pass (class_factor_mean_kernel): will K0b run, and on a size that has it?  Same rule as
+  // launch_class_factors (the decision depends on (nA, nB, shard count, options) only: every shard of a job decides alike;
+  // above 64 there is no geometry row and no factor pass: pl.g is all zero).
+  const int mean_mode = options ? clamp_policy(options->mean_metric_policy) : 0;
+  const bool want_mean = pl.g.mean_metric && mean_mode > 0 && p.factor_mode >= 0 &&
+                         (p.factor_mode > 0 || pair_count(nA, nB, shard_count) >= pl.g.factor_min_pairs) && nA >= 2;
+  double* mean_parts = reinterpret_cast<double*>(ws + pl.w.off_mean);
+  double* mean_linv = mean_parts + (size_t)kMeanParts * pl.MR * pl.MR;
   const int n_parts = nA < kMeanParts ? nA : kMeanParts;
   if (want_mean) {
     if (dtype == SQFA_F32) hipLaunchKernelGGL(mean_partial_kernel<float>, dim3(n_parts), dim3(256), 0, stream, static_cast<const float*>(A), nA, m, mean_parts);
     else hipLaunchKernelGGL(mean_partial_kernel<double>, dim3(n_parts), dim3(256), 0, stream, static_cast<const double*>(A), nA, m, mean_parts);
     p.mean_linv = mean_linv;
   }
-  bool rows_done = false;
-  auto launch_chol = [&](auto zero, const void* src, int n, void* lt, void* li) {
-    using T = decltype(zero);
-    const T* sp = static_cast<const T*>(src);
-    T* ltp = static_cast<T*>(lt);
-    T* lip = static_cast<T*>(li);
-    int* rows = rows_done ? nullptr : p.row_start;  // the first prologue launch also writes the slab slot table
-    const bool with_mean = want_mean && src == A && !rows_done;   // the A-side launch carries the mean block
-    rows_done = true;
-    const int blocks = n + (with_mean ? 1 : 0);
-    const double* mp = with_mean ? mean_parts : nullptr;
-    if (m <= 16) hipLaunchKernelGGL((cholesky_kernel<T, 16>), dim3(blocks), dim3(256), 0, stream, sp, m, g.MR, ltp, lip, rows, p, g.TI, n, mp, n_parts, mean_linv);
-    else if (m <= 32) hipLaunchKernelGGL((cholesky_kernel<T, 32>), dim3(blocks), dim3(256), 0, stream, sp, m, g.MR, ltp, lip, rows, p, g.TI, n, mp, n_parts, mean_linv);
-    else hipLaunchKernelGGL((cholesky_kernel<T, 64>), dim3(blocks), dim3(256), 0, stream, sp, m, g.MR, ltp, lip, rows, p, g.TI, n, mp, n_parts, mean_linv);
-  };
-  void* ws_lt = ws + w.off_lt;
-  void* ws_li = ws + w.off_linv;
-  if (dtype == SQFA_F32) {
-    if (self_mode) {
-      launch_chol(0.0f, A, nA, ws_lt, ws_li);
-    } else {
-      launch_chol(0.0f, A, nA, ws_lt, nullptr);
-      launch_chol(0.0f, B, nB, nullptr, ws_li);
-    }
-  } else {
-    if (self_mode) {
-      launch_chol(0.0, A, nA, ws_lt, ws_li);
-    } else {
-      launch_chol(0.0, A, nA, ws_lt, nullptr);
-      launch_chol(0.0, B, nB, nullptr, ws_li);
-    }
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "cholesky_kernel", e);
-  if (g.factor != nullptr) {  // K0b: orthogonalise the columns of each A-side factor (same stream: after the Cholesky launches)
-    e = g.factor(p, stream);
+  // the A-side launch also writes the slab slot table and carries the mean block
+  hipError_t e = launch_factors(pl, p, stream, A, nA, ws + pl.w.off_lt, pl.self_mode ? ws + pl.w.off_linv : nullptr, p.row_start,
+                                want_mean ? mean_parts : nullptr, n_parts, mean_linv);
+  if (!pl.self_mode && e == hipSuccess) e = launch_factors(pl, p, stream, B, nB, nullptr, ws + pl.w.off_linv, nullptr);
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, pl.lds ? "cholesky_lds_kernel" : "cholesky_kernel", e);
+  if (pl.g.factor != nullptr) {  // K0b: orthogonalise the columns of each A-side factor (same stream: after the Cholesky launches)
+    e = pl.g.factor(p, stream);
     if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "class_factor_kernel", e);
   }
 
   // K1: pair tiles
-  EventPair ev{};
-  bool prof = g_profile.load();
-  if (prof) {  // event records do not belong in a captured graph: profile eager launches only
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) prof = false;
-  }
-  if (prof) {
-    (void)hipEventCreate(&ev.a);
-    (void)hipEventCreate(&ev.b);
-    (void)hipEventRecord(ev.a, stream);
-  }
-  e = g.launch(p, stream);
-  if (prof) {
-    (void)hipEventRecord(ev.b, stream);
-    std::lock_guard<std::mutex> lock(g_events_mutex);
-    g_events.push_back(ev);
-  }
-  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "pair_tile_kernel", e);
+  e = launch_profiled(stream, [&] { return pl.lds ? launch_pair_lds(dtype == SQFA_F64, p, pl.TI, pl.MR, stream) : pl.g.launch(p, stream); });
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, pl.lds ? "pair_lds_kernel" : "pair_tile_kernel", e);
 
   // K2: slab reduction
-  const int n_cls = nA + (self_mode ? 0 : nB);
-  const int k2_tri = g.MR * (g.MR + 1) / 2;
-  const int k2_bpc = k2_tri <= 256 ? 1 : (k2_tri + 127) / 128;  // workgroups per class (finalize_kernel's EPB)
-  if (dtype == SQFA_F32) {
-    hipLaunchKernelGGL(finalize_kernel<float>, dim3(n_cls * k2_bpc + 1), dim3(SQFA_K2_THREADS), 0, stream, p, g.TI, tj, g.MR,
-                       static_cast<float*>(gradA_out), static_cast<float*>(gradB_out),
-                       static_cast<float*>(loss_out), nonfinite_out);
-  } else {
-    hipLaunchKernelGGL(finalize_kernel<double>, dim3(n_cls * k2_bpc + 1), dim3(SQFA_K2_THREADS), 0, stream, p, g.TI, tj, g.MR,
-                       static_cast<double*>(gradA_out), static_cast<double*>(gradB_out),
-                       static_cast<double*>(loss_out), nonfinite_out);
-  }
-  e = hipGetLastError();
+  e = launch_finalize(pl, p, gradA_out, gradB_out, loss_out, nonfinite_out, stream);
   if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_kernel", e);
   return SQFA_OK;
 }
@@ -1208,7 +1127,20 @@ static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, in
 struct BwExtra {
   size_t off_tr, off_h, off_hsum, off_sinv, off_g, off_w, total;
 };
-static BwExtra bw_extra(size_t base, int nA, int nBeff, int m, int nbi, int TJ) {
+// widest tiling of a problem under any geometry policy: (most tile rows, widest tile); slab_h needs nbi (nB + TJ) entries
+// for any narrower width
+static void bw_tiles(int nA, int nB, int m, int dtype, int* nbi, int* TJ) {
+  PairPlan regular, small;
+  make_plan(nA, nB, m, dtype, 1, -1, &regular);
+  make_plan(nA, nB, m, dtype, 1, 1, &small);
+  *nbi = std::max(regular.nbi, small.nbi);
+  *TJ = std::max(regular.TJ, small.TJ);
+}
+// (the caller has made a plan of the same problem: its size is supported)
+static BwExtra bw_extra(size_t base, int nA, int nB, int m, int dtype) {
+  const int nBeff = nB == 0 ? nA : nB;
+  int nbi, TJ;
+  bw_tiles(nA, nB, m, dtype, &nbi, &TJ);
   BwExtra x;
   size_t o = base;
   x.off_tr = o;   o = align_up(o + (size_t)(nA + nBeff) * sizeof(double));
@@ -1220,220 +1152,90 @@ static BwExtra bw_extra(size_t base, int nA, int nBeff, int m, int nbi, int TJ) 
   x.total = o;
   return x;
 }
-// widest tiling of a problem: (tile rows, widest tile width); slab_h needs nbi (nB + TJ) entries for any narrower width
-static void bw_tiles(int nA, int nBeff, int m, int dtype, int self_mode, int* nbi, int* TJ) {
-  if (m > kRegMaxDim) {
-    const LdsTiling t = lds_tiling(nA, nBeff, m, self_mode);
-    *nbi = (nA + t.TI - 1) / t.TI;
-    *TJ = t.TJ;
-    return;
-  }
-  // the rows of any geometry policy: the smallest TI and the largest TJ among them
-  Geometry g1, g2;
-  find_geometry(m, dtype, -1, &g1, -1);
-  find_geometry(m, dtype, 0, &g2, 1);
-  const int TI = std::min(g1.TI, g2.TI);
-  *nbi = (nA + TI - 1) / TI;
-  *TJ = std::max(g1.TJ, g2.TJ);
-}
 
 static int bw_impl(const void* A, int nA, const void* B, int nB, int m, int dtype, double eps, int sqrt_mode,
                    const void* pair_weights, double uniform_weight, int shard_index, int shard_count, void* loss_out,
                    void* gradA_out, void* gradB_out, void* dist_out, int* nonfinite_out, void* workspace,
                    size_t workspace_bytes, void* stream_, const sqfa_airm_options* options) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  auto clamp = [](int v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); };
-  const int geometry_mode = options ? clamp(options->geometry_policy) : 0;
-  const int factor_mode = options ? clamp(options->class_factor_policy) : 0;
-  g_last_error[0] = 0;
-  if (A == nullptr || nA < 1 || m < 1 || nB < 0 || workspace == nullptr) return fail(SQFA_ERR_BAD_ARGUMENT, "null/size argument", hipSuccess);
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return fail(SQFA_ERR_BAD_ARGUMENT, "dtype", hipSuccess);
-  if ((B == nullptr) != (nB == 0)) return fail(SQFA_ERR_BAD_ARGUMENT, "B and nB disagree", hipSuccess);
-  if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail(SQFA_ERR_BAD_ARGUMENT, "shard", hipSuccess);
-  const bool self_mode = (B == nullptr);
-  if (self_mode && nA < 2) return fail(SQFA_ERR_BAD_ARGUMENT, "self mode needs at least two classes", hipSuccess);
-  if (m > kLdsMaxDim) return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
-  const int nBeff = self_mode ? nA : nB;
-  const int f64 = dtype == SQFA_F64 ? 1 : 0;
-  const bool lds = m > kRegMaxDim;
-
-  Geometry g;
-  LdsTiling lt{};
-  int TI, tj, MR;
-  WorkspaceLayout w;
-  if (lds) {
-    lt = lds_tiling(nA, nBeff, m, self_mode ? 1 : 0);
-    TI = lt.TI;
-    tj = lt.TJ;
-    MR = lt.MR;
-    w = layout_lds(nA, nBeff, lt, esz, self_mode ? 1 : 0, shard_count);
-  } else {
-    if (!find_geometry(m, dtype, pair_count(nA, nB, shard_count), &g, geometry_mode) || g.launch_bw == nullptr)
-      return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
-    TI = g.TI;
-    MR = g.MR;
-    tj = choose_tile_width(nA, nBeff, g, self_mode ? 1 : 0, shard_count);
-    w = layout(nA, nBeff, g, esz, self_mode ? 1 : 0, tj, shard_count);
-  }
-  int nbi_max, TJ_max;
-  bw_tiles(nA, nBeff, m, dtype, self_mode ? 1 : 0, &nbi_max, &TJ_max);
-  const BwExtra x = bw_extra(w.total, nA, nBeff, m, nbi_max, TJ_max);
+  const int rc = validate_pair_call(A, nA, B, nB, m, dtype, shard_index, shard_count, workspace);
+  if (rc != SQFA_OK) return rc;
+  PairPlan pl;
+  if (!make_plan(nA, nB, m, dtype, shard_count, options ? clamp_policy(options->geometry_policy) : 0, &pl))
+    return fail(SQFA_ERR_UNSUPPORTED_M, "matrix size not supported", hipSuccess);
+  const BwExtra x = bw_extra(pl.w.total, nA, nB, m, dtype);
   if (workspace_bytes < x.total) return fail(SQFA_ERR_WORKSPACE, "workspace too small", hipSuccess);
   char* ws = static_cast<char*>(workspace);
   double* tr = reinterpret_cast<double*>(ws + x.off_tr);
-
-  PairParams p;
-  memset(&p, 0, sizeof(p));
-  p.LT = ws + w.off_lt;
-  p.Linv = ws + w.off_linv;
-  p.W = pair_weights;
-  p.slab_grad = ws + w.off_slab;
-  p.slab_loss = ws + w.off_loss;
-  p.slab_flag = reinterpret_cast<int*>(ws + w.off_flag);
-  p.row_start = reinterpret_cast<int*>(ws + w.off_rows);
-  p.dist_out = dist_out;
-  p.sweep_counter = options ? options->sweep_counter : nullptr;
-  p.nA = nA;
-  p.nB = nBeff;
-  p.m = m;
-  p.self_mode = self_mode ? 1 : 0;
-  p.sqrt_mode = sqrt_mode ? 1 : 0;
-  p.want_grad = gradA_out != nullptr ? 1 : 0;
-  p.shard_index = shard_index;
-  p.shard_count = shard_count;
-  p.nbi = (nA + TI - 1) / TI;
-  p.nbj = (nBeff + tj - 1) / tj;
-  p.tj = tj;
-  p.factor_mode = lds ? -1 : factor_mode;
-  p.scale = 1.0;
-  p.eps = eps;
-  p.uniform_weight = uniform_weight;
-  p.scale_f = 1.0f;
-  p.eps_f = (float)eps;
-  p.uniform_weight_f = (float)uniform_weight;
+  double* sinv = reinterpret_cast<double*>(ws + x.off_sinv);
+  PairParams p = make_pair_params(pl, ws, shard_index, 1.0, eps, sqrt_mode, pair_weights, uniform_weight, gradA_out != nullptr,
+                                  dist_out, options);
   p.trA = tr;
-  p.trB = self_mode ? tr : tr + nA;
+  p.trB = pl.self_mode ? tr : tr + nA;
   p.slab_h = ws + x.off_h;
 
-  // K0: A-side factors (the affine-invariant prologue; its first launch writes the slab slot table) ...
-  hipError_t e = hipSuccess;
-  if (lds) {
-    e = launch_lds_prologue(f64, A, nA, m, MR, ws + w.off_lt, nullptr, p.row_start, p, TI, stream);
-  } else {
-    auto chol = [&](auto zero) {
-      using T = decltype(zero);
-      const T* sp = static_cast<const T*>(A);
-      T* ltp = static_cast<T*>(const_cast<void*>(p.LT));
-      if (m <= 16) hipLaunchKernelGGL((cholesky_kernel<T, 16>), dim3(nA), dim3(256), 0, stream, sp, m, MR, ltp, (T*)nullptr, p.row_start, p, TI);
-      else if (m <= 32) hipLaunchKernelGGL((cholesky_kernel<T, 32>), dim3(nA), dim3(256), 0, stream, sp, m, MR, ltp, (T*)nullptr, p.row_start, p, TI);
-      else hipLaunchKernelGGL((cholesky_kernel<T, 64>), dim3(nA), dim3(256), 0, stream, sp, m, MR, ltp, (T*)nullptr, p.row_start, p, TI);
-    };
-    if (dtype == SQFA_F32) chol(0.0f); else chol(0.0);
-    e = hipGetLastError();
-  }
+  // K0: A-side factors (the affine-invariant prologue; the launch also writes the slab slot table) ...
+  hipError_t e = launch_factors(pl, p, stream, A, nA, ws + pl.w.off_lt, nullptr, p.row_start);
   if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "cholesky_kernel", e);
   // ... and the BW prologue: R_j, R_j^-1 and traces of the B classes, traces of the A classes
-  {
+  auto by_dtype = [&](auto launch) {  // launch(T()) with the element type of the call
+    if (dtype == SQFA_F32) launch(0.0f);
+    else launch(0.0);
+    return hipGetLastError();
+  };
+  e = by_dtype([&](auto zero) {
+    using T = decltype(zero);
     const size_t lds_bytes = ((size_t)m * (m + 1) + m) * sizeof(double);
-    double* sinv = reinterpret_cast<double*>(ws + x.off_sinv);
-    auto launch = [&](auto zero, const void* S, int n, void* R, double* si, double* trace) {
-      using T = decltype(zero);
-      if (lds_bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bw_prologue_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      hipLaunchKernelGGL(bw_prologue_kernel<T>, dim3(n), dim3(256), lds_bytes, stream, static_cast<const T*>(S), m, MR,
+    if (lds_bytes > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bw_prologue_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    auto launch = [&](const void* S, int n, void* R, double* si, double* trace) {
+      hipLaunchKernelGGL(bw_prologue_kernel<T>, dim3(n), dim3(256), lds_bytes, stream, static_cast<const T*>(S), m, pl.MR,
                          static_cast<T*>(R), si, trace);
     };
-    void* rslot = ws + w.off_linv;
-    if (dtype == SQFA_F32) {
-      if (self_mode) launch(0.0f, A, nA, rslot, sinv, tr);
-      else { launch(0.0f, A, nA, nullptr, nullptr, tr); launch(0.0f, B, nB, rslot, sinv, tr + nA); }
-    } else {
-      if (self_mode) launch(0.0, A, nA, rslot, sinv, tr);
-      else { launch(0.0, A, nA, nullptr, nullptr, tr); launch(0.0, B, nB, rslot, sinv, tr + nA); }
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "bw_prologue_kernel", e);
-  }
-  if (!lds && g.factor != nullptr) {  // K0b on the A-side factors (plain metric: mean_metric_policy does not apply here)
-    e = g.factor(p, stream);
+    void* rslot = ws + pl.w.off_linv;
+    if (pl.self_mode) launch(A, nA, rslot, sinv, tr);
+    else { launch(A, nA, nullptr, nullptr, tr); launch(B, nB, rslot, sinv, tr + nA); }
+  });
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "bw_prologue_kernel", e);
+  if (pl.g.factor != nullptr) {  // K0b on the A-side factors (plain metric: mean_metric_policy does not apply here)
+    e = pl.g.factor(p, stream);
     if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "class_factor_kernel", e);
   }
 
   // K1: pair tiles
-  EventPair ev{};
-  bool prof = g_profile.load();
-  if (prof) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) prof = false;
-  }
-  if (prof) {
-    (void)hipEventCreate(&ev.a);
-    (void)hipEventCreate(&ev.b);
-    (void)hipEventRecord(ev.a, stream);
-  }
-  e = lds ? launch_pair_lds_bw(f64, p, TI, MR, stream) : g.launch_bw(p, stream);
-  if (prof) {
-    (void)hipEventRecord(ev.b, stream);
-    std::lock_guard<std::mutex> lock(g_events_mutex);
-    g_events.push_back(ev);
-  }
+  e = launch_profiled(stream, [&] { return pl.lds ? launch_pair_lds_bw(dtype == SQFA_F64, p, pl.TI, pl.MR, stream) : pl.g.launch_bw(p, stream); });
   if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "pair_tile_kernel (Bures-Wasserstein)", e);
 
   // K2: loss, flags and the diagonal of dist_out through finalize_kernel (its class blocks return at once without
   // want_grad), then the gradient reduction and the B-side sandwich
-  {
-    PairParams q = p;
-    q.want_grad = 0;
-    const int k2_tri = MR * (MR + 1) / 2;
-    const int k2_blocks = (nA + (self_mode ? 0 : nB)) * (!lds && k2_tri <= 256 ? 1 : (k2_tri + 127) / 128) + 1;  // the last one works
-    if (dtype == SQFA_F32)
-      hipLaunchKernelGGL(finalize_kernel<float>, dim3(k2_blocks), dim3(SQFA_K2_THREADS), 0, stream, q, TI, tj, MR, (float*)nullptr,
-                         (float*)nullptr, static_cast<float*>(loss_out), nonfinite_out);
-    else
-      hipLaunchKernelGGL(finalize_kernel<double>, dim3(k2_blocks), dim3(SQFA_K2_THREADS), 0, stream, q, TI, tj, MR, (double*)nullptr,
-                         (double*)nullptr, static_cast<double*>(loss_out), nonfinite_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_kernel", e);
-  }
+  PairParams q = p;
+  q.want_grad = 0;
+  e = launch_finalize(pl, q, nullptr, nullptr, loss_out, nonfinite_out, stream);
+  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_kernel", e);
   if (p.want_grad) {
-    const int TRI = MR * (MR + 1) / 2, BPC = (TRI + 255) / 256;
     double* G = reinterpret_cast<double*>(ws + x.off_g);
     double* W = reinterpret_cast<double*>(ws + x.off_w);
     double* hs = reinterpret_cast<double*>(ws + x.off_hsum);
-    const double* sinv = reinterpret_cast<const double*>(ws + x.off_sinv);
-    void* outB = self_mode ? gradA_out : gradB_out;
-    if (dtype == SQFA_F32) {
-      hipLaunchKernelGGL(finalize_bw_kernel<float>, dim3((nA + nBeff) * BPC), dim3(256), 0, stream, p, TI, tj, MR,
-                         static_cast<float*>(gradA_out), G, hs);
+    void* outB = pl.self_mode ? gradA_out : gradB_out;
+    e = by_dtype([&](auto zero) {
+      using T = decltype(zero);
+      hipLaunchKernelGGL(finalize_bw_kernel<T>, dim3((nA + pl.nBeff) * finalize_bw_bpc(pl.MR * (pl.MR + 1) / 2)), dim3(256), 0, stream,
+                         p, pl.TI, pl.tj, pl.MR, static_cast<T*>(gradA_out), G, hs);
       if (outB != nullptr)
-        hipLaunchKernelGGL(bw_sandwich_kernel<float>, dim3(nBeff), dim3(256), 0, stream, m, sinv, G, W, hs,
-                           static_cast<float*>(outB), self_mode ? 1 : 0);
-    } else {
-      hipLaunchKernelGGL(finalize_bw_kernel<double>, dim3((nA + nBeff) * BPC), dim3(256), 0, stream, p, TI, tj, MR,
-                         static_cast<double*>(gradA_out), G, hs);
-      if (outB != nullptr)
-        hipLaunchKernelGGL(bw_sandwich_kernel<double>, dim3(nBeff), dim3(256), 0, stream, m, sinv, G, W, hs,
-                           static_cast<double*>(outB), self_mode ? 1 : 0);
-    }
-    e = hipGetLastError();
+        hipLaunchKernelGGL(bw_sandwich_kernel<T>, dim3(pl.nBeff), dim3(256), 0, stream, m, sinv, G, W, hs, static_cast<T*>(outB),
+                           pl.self_mode);
+    });
     if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "finalize_bw_kernel", e);
   }
   return SQFA_OK;
 }
 
 size_t sqfa_airm_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy) {
-  int ti, tj, nbi, nbj, mr;
-  if (shard_count < 1 || sqfa_airm_tiling(nA, nB, m, dtype, &ti, &tj, &nbi, &nbj, &mr) != SQFA_OK) return 0;
-  if (m > kRegMaxDim) {
-    const int nBeff = nB == 0 ? nA : nB, self_mode = nB == 0 ? 1 : 0;
-    return layout_lds(nA, nBeff, lds_tiling(nA, nBeff, m, self_mode), dtype == SQFA_F32 ? 4 : 8, self_mode, shard_count).total;
-  }
-  Geometry g;
-  find_geometry(m, dtype, pair_count(nA, nB, shard_count), &g, geometry_policy > 0 ? 1 : (geometry_policy < 0 ? -1 : 0));
-  const int nBeff = nB == 0 ? nA : nB, self_mode = nB == 0 ? 1 : 0;
-  return layout(nA, nBeff, g, dtype == SQFA_F32 ? 4 : 8, self_mode,
-                choose_tile_width(nA, nBeff, g, self_mode, shard_count), shard_count).total;
+  PairPlan pl;
+  if (shard_count < 1 || nA < 1 || nB < 0 || m < 1 || !known_dtype(dtype) ||
+      !make_plan(nA, nB, m, dtype, shard_count, clamp_policy(geometry_policy), &pl))
+    return 0;
+  return pl.w.total;
 }
 
 int sqfa_airm_pairwise(const void* A, int nA, const void* B, int nB, int m, int dtype, double scale,
@@ -1470,20 +1272,12 @@ int sqfa_airm_eigenvalues_backward(const void* A, int nA, const void* B, int nB,
 
 size_t sqfa_bw_workspace_bytes(int nA, int nB, int m, int dtype) {
   const size_t base = sqfa_airm_workspace_bytes(nA, nB, m, dtype);
-  if (base == 0) return 0;
-  const int nBeff = nB == 0 ? nA : nB;
-  int nbi, TJ;
-  bw_tiles(nA, nBeff, m, dtype, nB == 0 ? 1 : 0, &nbi, &TJ);
-  return bw_extra(align_up(base), nA, nBeff, m, nbi, TJ).total;
+  return base == 0 ? 0 : bw_extra(align_up(base), nA, nB, m, dtype).total;
 }
 
 size_t sqfa_bw_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy) {
   const size_t base = sqfa_airm_workspace_bytes_sharded(nA, nB, m, dtype, shard_count, geometry_policy);
-  if (base == 0) return 0;
-  const int nBeff = nB == 0 ? nA : nB;
-  int nbi, TJ;
-  bw_tiles(nA, nBeff, m, dtype, nB == 0 ? 1 : 0, &nbi, &TJ);
-  return bw_extra(align_up(base), nA, nBeff, m, nbi, TJ).total;
+  return base == 0 ? 0 : bw_extra(align_up(base), nA, nB, m, dtype).total;
 }
 
 int sqfa_bw_pairwise(const void* A, int nA, const void* B, int nB, int m, int dtype, double eps, int sqrt_mode,
@@ -1496,7 +1290,7 @@ int sqfa_bw_pairwise(const void* A, int nA, const void* B, int nB, int m, int dt
 
 size_t sqfa_spd_function_workspace_bytes(int n, int m, int dtype) {
   Geometry g;
-  if (n < 1 || m < 1 || (dtype != SQFA_F32 && dtype != SQFA_F64) || !find_geometry(m, dtype, -1, &g, -1)) return 0;
+  if (n < 1 || m < 1 || !known_dtype(dtype) || !find_geometry(m, dtype, -1, &g, -1)) return 0;
   return align_up((size_t)n * g.MR * g.MR * (dtype == SQFA_F32 ? 4 : 8));
 }
 
@@ -1514,15 +1308,7 @@ int sqfa_spd_function(const void* S, int n, int m, int dtype, int kind, void* F_
   PairParams p;
   memset(&p, 0, sizeof(p));
   // Cholesky factor of every class, columns contiguous, identity padded to the size class (K0; double inside)
-  auto chol = [&](auto zero) {
-    using T = decltype(zero);
-    const T* sp = static_cast<const T*>(S);
-    T* ltp = static_cast<T*>(workspace);
-    if (m <= 16) hipLaunchKernelGGL((cholesky_kernel<T, 16>), dim3(n), dim3(256), 0, stream, sp, m, g.MR, ltp, (T*)nullptr, (int*)nullptr, p, g.TI);
-    else if (m <= 32) hipLaunchKernelGGL((cholesky_kernel<T, 32>), dim3(n), dim3(256), 0, stream, sp, m, g.MR, ltp, (T*)nullptr, (int*)nullptr, p, g.TI);
-    else hipLaunchKernelGGL((cholesky_kernel<T, 64>), dim3(n), dim3(256), 0, stream, sp, m, g.MR, ltp, (T*)nullptr, (int*)nullptr, p, g.TI);
-  };
-  if (dtype == SQFA_F32) chol(0.0f); else chol(0.0);
+  launch_cholesky(dtype, m, stream, S, n, g.MR, workspace, nullptr, nullptr, p, g.TI);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "cholesky_kernel", e);
   e = g.eig(workspace, n, m, U_out, lam_out, stream);

@@ -1,0 +1,101 @@
+"""Every host-side decision of the pairwise C ABI as a text table: tilings, workspace sizes, and the return code and
+message of each argument rejection.  Needs no GPU (without one the library assumes 256 CUs, the MI355X's count; every
+call below is rejected before it launches anything).  The check is the diff of two runs:
+
+    SQFA_HIP_LIBRARY=/path/to/other/libsqfa_hip.so python tools/host_decisions.py > a.txt
+    python tools/host_decisions.py > b.txt && diff a.txt b.txt
+"""
+import ctypes
+import itertools
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from sqfa_amd import _lib  # noqa: E402
+
+NA = (2, 7, 30, 100, 300, 1000)
+NB = (0, 7, 1000)
+M = (1, 4, 5, 8, 12, 16, 17, 20, 24, 32, 33, 40, 48, 64, 65, 96, 128, 129)
+SHARDS = (1, 2, 8)
+POLICIES = (-1, 0, 1)
+
+
+def sizes(lib):
+    for nA, nB, m, dtype in itertools.product(NA, NB, M, (_lib.SQFA_F32, _lib.SQFA_F64)):
+        out = [ctypes.c_int(-1) for _ in range(5)]
+        rc = lib.sqfa_airm_tiling(nA, nB, m, dtype, *[ctypes.byref(v) for v in out])
+        print(f"nA={nA} nB={nB} m={m} dtype={dtype}: tiling rc={rc} {[v.value for v in out]}"
+              f" airm_ws={lib.sqfa_airm_workspace_bytes(nA, nB, m, dtype)} bw_ws={lib.sqfa_bw_workspace_bytes(nA, nB, m, dtype)}")
+        for shards, policy in itertools.product(SHARDS, POLICIES):
+            print(f"  shards={shards} policy={policy}:"
+                  f" airm_ws={lib.sqfa_airm_workspace_bytes_sharded(nA, nB, m, dtype, shards, policy)}"
+                  f" bw_ws={lib.sqfa_bw_workspace_bytes_sharded(nA, nB, m, dtype, shards, policy)}")
+    for n, m, dtype in itertools.product(NA, M, (_lib.SQFA_F32, _lib.SQFA_F64)):
+        print(f"spd n={n} m={m} dtype={dtype}: ws={lib.sqfa_spd_function_workspace_bytes(n, m, dtype)}")
+
+
+def rejections(lib):
+    """Host memory stands in for the device pointers: a rejected call never touches them."""
+    buf = ctypes.create_string_buffer(64)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    opts = _lib.AirmOptions(0, 0, None, 0)
+
+    # name -> (A, nA, B, nB, m, dtype, shard_index, shard_count, workspace, workspace_bytes)
+    def case(A=ptr, nA=30, B=None, nB=0, m=16, dtype=_lib.SQFA_F32, shard=(0, 1), ws=ptr, ws_bytes=1 << 40):
+        return A, nA, B, nB, m, dtype, shard[0], shard[1], ws, ws_bytes
+
+    cases = {
+        "null A": case(A=None),
+        "null workspace": case(ws=None),
+        "bad dtype": case(dtype=7),
+        "B without nB": case(B=ptr, nB=0),
+        "nB without B": case(B=None, nB=7),
+        "shard index": case(shard=(2, 2)),
+        "shard count": case(shard=(0, 0)),
+        "self mode, one class": case(nA=1),
+        "m=129": case(m=129),
+    }
+    for m, dtype, nB in itertools.product((16, 40, 96), (_lib.SQFA_F32, _lib.SQFA_F64), (0, 7)):
+        cases[f"airm workspace one byte short m={m} dtype={dtype} nB={nB}"] = case(
+            m=m, dtype=dtype, B=ptr if nB else None, nB=nB, ws_bytes=lib.sqfa_airm_workspace_bytes_sharded(30, nB, m, dtype, 1, 0) - 1)
+        cases[f"bw workspace one byte short m={m} dtype={dtype} nB={nB}"] = case(
+            m=m, dtype=dtype, B=ptr if nB else None, nB=nB, ws_bytes=lib.sqfa_bw_workspace_bytes_sharded(30, nB, m, dtype, 1, 0) - 1)
+
+    def report(fn, name, rc):
+        print(f"{fn} [{name}]: rc={rc} error={lib.sqfa_hip_last_error().decode()!r}")
+
+    for name, (A, nA, B, nB, m, dtype, si, sc, ws, nbytes) in cases.items():
+        if not name.startswith("bw workspace"):
+            args = (A, nA, B, nB, m, dtype, 1.0, 1e-6, 1, None, 1.0, si, sc, ptr, ptr, None, None, None, None, ws, nbytes, None)
+            report("sqfa_airm_pairwise", name, lib.sqfa_airm_pairwise(*args))
+            report("sqfa_airm_pairwise_opt", name, lib.sqfa_airm_pairwise_opt(*args, ctypes.byref(opts)))
+            if sc == 1:  # the eigenvalue backward takes no shard
+                report("sqfa_airm_eigenvalues_backward", name,
+                       lib.sqfa_airm_eigenvalues_backward(A, nA, B, nB, m, dtype, ptr, ptr, None, ws, nbytes, None, None))
+        if not name.startswith("airm workspace"):
+            report("sqfa_bw_pairwise", name,
+                   lib.sqfa_bw_pairwise(A, nA, B, nB, m, dtype, 1e-6, 1, None, 1.0, si, sc, ptr, ptr, None, None, None, ws, nbytes,
+                                        None, None))
+    report("sqfa_airm_eigenvalues_backward", "null eig_weights",
+           lib.sqfa_airm_eigenvalues_backward(ptr, 30, None, 0, 16, 0, None, ptr, None, ptr, 1 << 40, None, None))
+
+    def spd(S=ptr, n=30, m=16, dtype=_lib.SQFA_F32, kind=0, U=ptr, ws=ptr, ws_bytes=1 << 40):
+        return lib.sqfa_spd_function(S, n, m, dtype, kind, None, U, ptr, ws, ws_bytes, None)
+
+    report("sqfa_spd_function", "null S", spd(S=None))
+    report("sqfa_spd_function", "null workspace", spd(ws=None))
+    report("sqfa_spd_function", "bad dtype", spd(dtype=7))
+    report("sqfa_spd_function", "bad kind", spd(kind=9))
+    report("sqfa_spd_function", "m=65", spd(m=65))
+    report("sqfa_spd_function", "m=129", spd(m=129))
+    for m, dtype in itertools.product((16, 40, 64), (_lib.SQFA_F32, _lib.SQFA_F64)):
+        report("sqfa_spd_function", f"workspace one byte short m={m} dtype={dtype}",
+               spd(m=m, dtype=dtype, ws_bytes=lib.sqfa_spd_function_workspace_bytes(30, m, dtype) - 1))
+    report("sqfa_spd_function_backward", "m=65", lib.sqfa_spd_function_backward(ptr, ptr, ptr, 30, 65, 0, 0, ptr, None))
+
+
+if __name__ == "__main__":
+    library = _lib.load()
+    print(f"# version {library.sqfa_hip_version()} arch {library.sqfa_hip_arch().decode()} max_dim {library.sqfa_hip_max_dim()}")
+    sizes(library)
+    rejections(library)

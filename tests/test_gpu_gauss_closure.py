@@ -1,7 +1,7 @@
 """GPU tests of the fused Gaussian pair closure: sqfa_gauss_pairwise_loss (fused mode of the Gaussian pair kernels),
 _native.GaussPairwiseLoss and SQFA's closure with bhattacharyya / hellinger / mahalanobis_sq / mahalanobis as
 distance_fun, against the reference's values (golden G8, tests/golden/make_golden_gauss_closure.py) and a float64 torch
-expression of the definitions.
+expression of the definitions (tests/gauss_oracle.py).
 
 Tolerances (the rule of tests/test_gpu_other_operators.py): float64 1e-9 (values) / 1e-8 (gradients; Hellinger
 gradients 1e-6); float32 max(1e-5, 5 x the reference's own float32-vs-float64 deviation on that case, G8's f32 keys).
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_err
+from gauss_oracle import _full_expression, _rows_D
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -38,38 +39,6 @@ def _tol(key, op, what, dtype, floor64):
 
 def _grad_floor(op):
     return 1e-6 if op == "hellinger" else 1e-8
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# the definitions, in float64 torch (rows of classes against all classes)
-
-def _rows_D(mu_r, cov_r, mu, cov, kind):
-    """(R,C) distances of the classes (mu_r, cov_r) to all classes (mu, cov); the log-determinant term of a class with
-    itself is not special-cased here: callers mask the diagonal."""
-    Sbar = 0.5 * (cov_r[:, None] + cov[None])
-    delta = mu_r[:, None] - mu[None]
-    sol = torch.linalg.solve(Sbar, delta.unsqueeze(-1)).squeeze(-1)
-    Q = (delta * sol).sum(-1)
-    if kind == 2:
-        return Q
-    if kind == 3:
-        return torch.sqrt(Q + EPS)
-    Bh = Q / 8 + 0.5 * (torch.logdet(Sbar) - 0.5 * (torch.logdet(cov_r)[:, None] + torch.logdet(cov)[None]))
-    return Bh if kind == 0 else torch.sqrt(1 - torch.exp(-Bh) + EPS)
-
-
-def _full_expression(mu, cov, kind, weight):
-    """loss = weight * sum_{i>j} D_ij, its gradients, and D with the reference's diagonal."""
-    mu = mu.detach().double().requires_grad_(True)
-    cov = cov.detach().double().requires_grad_(True)
-    D = _rows_D(mu, cov, mu, cov, kind)
-    C = mu.shape[0]
-    rows, cols = torch.tril_indices(C, C, offset=-1)
-    loss = weight * D[rows, cols].sum()
-    gmu, gcov = torch.autograd.grad(loss, (mu, cov))
-    D = D.detach().clone()
-    D.fill_diagonal_(0.0 if kind in (0, 2) else EPS ** 0.5)
-    return loss.detach(), gmu, gcov, D
 
 
 def _native_call(mu, cov, kind, weight, want_grad=True, want_dist=True):

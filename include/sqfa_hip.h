@@ -346,6 +346,33 @@ int sqfa_gauss_pairwise_loss(const void *mu, const void *cov, int n, int m, int 
                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Fused closure loss of the log-Euclidean distances (log_euclidean[_sq] of the reference, src/sqfa/distances.py:92-138, as
+ * a model's distance_fun): for the n SPD matrices S_c, with L_c = log S_c and d2_ij = || L_i - L_j ||_F^2,
+ *     sqrt_mode 0   D_ij = d2_ij
+ *     sqrt_mode 1   D_ij = sqrt(d2_ij + eps)
+ *     loss = uniform_weight * sum_{i>j} D_ij      (uniform_weight = -1/P, P = n(n-1)/2: the reference's -mean)
+ * together with its gradient wrt S.  Stages, all on the caller's stream: the per-class stages of sqfa_spd_function (L, and
+ * the double-precision U and lambda of the backward); ONE pass over the ordered pairs (log_euclidean_kernel.hip: the
+ * differences L_i - L_j are formed entry by entry -- no Gram-matrix expansion, which loses the digits that matter for close
+ * classes -- and every class row has one writer); sqfa_spd_function_backward on G_i = sum_{j != i} c_ij (L_i - L_j);
+ * a one-workgroup reduction of the per-class partial losses and counters.  No float atomics anywhere: results are
+ * bitwise reproducible.  No (n,n) matrix is stored unless dist_out is given.
+ *   S (n,m,m): row-major, dtype; n >= 2, 1 <= m <= 64
+ *   loss_out (1) dtype or NULL; gradS_out (n,m,m, full symmetric matrices) or NULL = forward only; dist_out (n,n) or NULL:
+ *   D_ij, both triangles, the diagonal as the reference gives it (0, or sqrt(eps) for the square-root kind);
+ *   nonfinite_out (2) int32 or NULL: {#NaN, #inf} among the pairs i > j (a class that is not positive definite yields
+ *   NaN and is counted, never a fault)
+ *   workspace: sqfa_log_euclidean_workspace_bytes(n, m, dtype) bytes (0 = shape or dtype not supported)
+ * Returns SQFA_ERR_BAD_ARGUMENT (null S, n < 2, m < 1, dtype, sqrt_mode outside {0, 1}), SQFA_ERR_UNSUPPORTED_M (m > 64),
+ * SQFA_ERR_WORKSPACE; every argument check runs before the first HIP call.
+ */
+size_t sqfa_log_euclidean_workspace_bytes(int n, int m, int dtype);
+int sqfa_log_euclidean_pairwise_loss(const void *S, int n, int m, int dtype, int sqrt_mode,
+                                     double eps, double uniform_weight,
+                                     void *loss_out, void *gradS_out, void *dist_out, int *nonfinite_out,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the
  * reference (src/sqfa/linalg.py:165-183, 121-141: torch.linalg.eigh + einsum), as used by log_euclidean[_sq]
  * (src/sqfa/distances.py:92-138).  The eigen-decomposition is one-sided Jacobi, run to convergence, on the Cholesky

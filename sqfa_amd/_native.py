@@ -467,6 +467,54 @@ class SpdFunction(torch.autograd.Function):
         return gS, None
 
 
+def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, want_dist=False):
+    """sqfa_log_euclidean_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe
+    inside a graph capture).  S (n,m,m) SPD.  Returns dict(loss, gS, dist, nonfinite) (None where not requested)."""
+    lib = _lib.load()
+    if not S.is_cuda:
+        raise RuntimeError("sqfa_amd's fused log-Euclidean pair loss runs on the GPU only (no CPU fallback)")
+    S = S.detach().contiguous()
+    n, m = S.shape[0], S.shape[-1]
+    if m > SPD_FUNCTION_MAX_DIM:
+        raise NotImplementedError(f"matrix size {m} exceeds the native per-class SPD functions' limit ({SPD_FUNCTION_MAX_DIM})")
+    code = _dtype_code(S)
+    nbytes = lib.sqfa_log_euclidean_workspace_bytes(n, m, code)
+    if nbytes == 0:
+        raise _lib.NativeLibraryError("sqfa_log_euclidean_workspace_bytes rejected the problem shape")
+    dev, dt = S.device, S.dtype
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=dt, device=dev)
+        nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
+        gS = torch.empty_like(S) if want_grad else None
+        dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        status = lib.sqfa_log_euclidean_pairwise_loss(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps), float(weight),
+                                                      _ptr(loss), _ptr(gS), _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes,
+                                                      stream)
+    _lib.check(status, "sqfa_log_euclidean_pairwise_loss")
+    return {"loss": loss, "gS": gS, "dist": dist, "nonfinite": nonfinite}
+
+
+class LogEuclideanPairwiseLoss(torch.autograd.Function):
+    """Fused closure loss of log_euclidean (sqrt_mode True) / log_euclidean_sq (False): weight * sum over the unordered
+    class pairs, with its gradient wrt the (C,K,K) SPD matrices, from ONE pass over the pairs between the per-class
+    logarithm and its Daleckii-Krein backward (sqfa_log_euclidean_pairwise_loss) -- in place of SpdFunction forward ->
+    cdist -> square / sqrt -> tril gather -> mean and their autograd backward.  Returns (loss, flags {#NaN, #inf})."""
+
+    @staticmethod
+    def forward(ctx, S, sqrt_mode, eps, weight):
+        out = hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight)
+        ctx.save_for_backward(out["gS"])
+        ctx.mark_non_differentiable(out["nonfinite"])
+        return out["loss"], out["nonfinite"]
+
+    @staticmethod
+    def backward(ctx, gloss, _gflag):
+        (gS,) = ctx.saved_tensors
+        return gS * gloss, None, None, None
+
+
 def spd_function(M, kind):
     """(..., m, m) -> (..., m, m) on the native kernels (the caller has checked spd_function_supported)."""
     lead = M.shape[:-2]

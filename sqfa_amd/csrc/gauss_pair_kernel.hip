@@ -668,6 +668,18 @@ __global__ __launch_bounds__(256) void gauss_finalize_kernel(const double* loss_
   }
 }
 
+// (also the last stage of sqfa_log_euclidean_pairwise_loss, log_euclidean_kernel.hip)
+hipError_t launch_pair_loss_finalize(const double* loss_part, const int* cnt_part, int n, int dtype, void* loss_out,
+                                     int* nonfinite_out, hipStream_t stream) {
+  if (dtype == SQFA_F32)
+    hipLaunchKernelGGL((gauss_finalize_kernel<float>), dim3(1), dim3(256), 0, stream, loss_part, cnt_part, n,
+                       static_cast<float*>(loss_out), nonfinite_out);
+  else
+    hipLaunchKernelGGL((gauss_finalize_kernel<double>), dim3(1), dim3(256), 0, stream, loss_part, cnt_part, n,
+                       static_cast<double*>(loss_out), nonfinite_out);
+  return hipGetLastError();
+}
+
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 }  // namespace sqfa
 
@@ -759,11 +771,6 @@ extern "C" int sqfa_gauss_pairwise_loss(const void* mu, const void* cov, int n, 
     if (dispatch_gauss<GAUSS_PRE>(pre, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   }
   if (dispatch_gauss<GAUSS_FUSED>(p, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
-  if (dtype == SQFA_F32)
-    hipLaunchKernelGGL((gauss_finalize_kernel<float>), dim3(1), dim3(256), 0, stream, p.loss_part, p.cnt_part, n,
-                       static_cast<float*>(loss_out), nonfinite_out);
-  else
-    hipLaunchKernelGGL((gauss_finalize_kernel<double>), dim3(1), dim3(256), 0, stream, p.loss_part, p.cnt_part, n,
-                       static_cast<double*>(loss_out), nonfinite_out);
-  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+  return launch_pair_loss_finalize(p.loss_part, p.cnt_part, n, dtype, loss_out, nonfinite_out, stream) == hipSuccess
+             ? SQFA_OK : SQFA_ERR_LAUNCH;
 }

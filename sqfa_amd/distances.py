@@ -8,7 +8,9 @@ either model; for GPU tensors their pair-dependent terms run on the native Gauss
 (``bhattacharyya`` / ``mahalanobis[_sq]`` / ``hellinger`` / ``fisher_rao_same_cov``: sqfa_gauss_pair_terms) or avoid
 the reference's (nA,nB,m,m) tensor (``log_euclidean[_sq]``: per-class logarithms + exact pairwise distances); CPU
 tensors keep the reference's torch expression.  As ``SQFA``'s ``distance_fun``, ``bhattacharyya`` / ``hellinger`` /
-``mahalanobis[_sq]`` train through one fused loss+gradient pass per closure (sqfa_gauss_pairwise_loss, GAUSS_FUSED_CLOSURE).
+``mahalanobis[_sq]`` train through one fused loss+gradient pass per closure (sqfa_gauss_pairwise_loss, GAUSS_FUSED_CLOSURE);
+as ``SecondMomentsSQFA``'s ``distance_fun``, ``log_euclidean[_sq]`` do the same through sqfa_log_euclidean_pairwise_loss
+(LOG_EUCLIDEAN_FUSED_CLOSURE, ``class_fused_spec``).  Called directly, every operator keeps its own implementation.
 """
 import torch
 
@@ -157,6 +159,20 @@ def log_euclidean_sq(A, B):
 def log_euclidean(A, B):
     """reference: src/sqfa/distances.py:119-138"""
     return torch.sqrt(log_euclidean_sq(A, B) + EPSILON)
+
+
+# log_euclidean / log_euclidean_sq as SecondMomentsSQFA's distance_fun: per-class logarithm -> one pass over the class pairs
+# -> Daleckii-Krein backward in one native call (_native.LogEuclideanPairwiseLoss), captured in a HIP graph by the fitting
+# loop.  False restores the generic closure (SpdFunction -> cdist -> validity check on the host -> autograd, no graph).
+# These two are not pair-kernel operators: they stay out of _FUSED (fused_spec is None for them) and have their own lookup.
+LOG_EUCLIDEAN_FUSED_CLOSURE = True
+_CLASS_FUSED = {log_euclidean: ("spd", True), log_euclidean_sq: ("spd", False)}
+
+
+def class_fused_spec(fn):
+    """(input kind, sqrt_mode) if `fn` is an operator whose closure runs as per-class stages around one pass over the
+    class pairs (log_euclidean, log_euclidean_sq), else None; None for everything when the switch is off."""
+    return _CLASS_FUSED.get(fn) if LOG_EUCLIDEAN_FUSED_CLOSURE else None
 
 
 def _gaussian_inputs(statistics_A, statistics_B):

@@ -149,7 +149,14 @@ class SecondMomentsSQFA(nn.Module):
     def _has_fused_closure(self):
         """True when distance_fun is the native operator this model's fused closure evaluates."""
         spec = distances.fused_spec(self.distance_fun)
-        if spec is None or spec[0] != self._fused_kind:
+        if spec is None:
+            # log_euclidean[_sq]: per-class stages around one pass over the class pairs, within the per-class SPD functions'
+            # limits; single-process fits only (a sharded fit keeps the generic closure, as _log_euclidean_closure_loss does)
+            cspec = distances.class_fused_spec(self.distance_fun)
+            nm = self.noise_mat
+            return (cspec is not None and cspec[0] == self._fused_kind and nm.dtype in (torch.float32, torch.float64)
+                    and nm.shape[0] <= _native.SPD_FUNCTION_MAX_DIM and self.pair_shard is None and self.class_shard is None)
+        if spec[0] != self._fused_kind:
             return False
         if spec[3] == "gauss":   # the Gaussian pair kernels' own limits: beyond them the generic closure, never captured
             nm = self.noise_mat   # (K,K), the model's dtype (reading self.filters would run the parametrization)
@@ -185,6 +192,8 @@ class SecondMomentsSQFA(nn.Module):
         if not self._has_fused_closure():
             return None
         spec = distances.fused_spec(self.distance_fun)
+        if spec is None:
+            return self._log_euclidean_closure_loss(prepared)
         scale, sqrt_mode, metric = spec[1], spec[2], spec[3]
         if metric == "gauss":
             return self._gauss_closure_loss(prepared, scale)
@@ -219,6 +228,24 @@ class SecondMomentsSQFA(nn.Module):
         C = cov.shape[0]
         weight = -1.0 / (C * (C - 1) // 2)
         return _native.GaussPairwiseLoss.apply(mu, cov, int(kind), distances.EPSILON, weight)
+
+    def _log_euclidean_closure_loss(self, prepared):
+        """(loss, flags) for log_euclidean / log_euclidean_sq as the chain parametrization -> projection -> noise ->
+        _native.LogEuclideanPairwiseLoss (any parametrization; the native projection where it applies), or None -- the fitting
+        loop's generic closure -- where the native call does not apply: sharded fits, statistics that are not a (C,D,D)
+        tensor, CPU or non-float32/64 tensors, fewer than two classes, more than _native.SPD_FUNCTION_MAX_DIM filters."""
+        cspec = distances.class_fused_spec(self.distance_fun)
+        if cspec is None or self.pair_shard is not None or self.class_shard is not None:
+            return None
+        if not torch.is_tensor(prepared) or prepared.dim() != 3 or not prepared.is_cuda:
+            return None
+        S = self._feature_scatters(prepared, True)
+        if not (S.is_cuda and S.dim() == 3 and S.dtype in (torch.float32, torch.float64) and S.shape[0] >= 2
+                and S.shape[-1] <= _native.SPD_FUNCTION_MAX_DIM):
+            return None
+        C = S.shape[0]
+        weight = -1.0 / (C * (C - 1) // 2)
+        return _native.LogEuclideanPairwiseLoss.apply(S, cspec[1], distances.EPSILON, weight)
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once

@@ -395,6 +395,31 @@ int sqfa_spd_function(const void *S, int n, int m, int dtype, int kind, void *F_
 int sqfa_spd_function_backward(const double *U, const double *lam, const void *G, int n, int m, int dtype, int kind,
                                void *gradS_out, void *stream);
 
+/*
+ * The orthogonal filter constraint (constraint="orthogonal" of the reference, src/sqfa/model.py:416-431, which registers
+ * torch.nn.utils.parametrizations.orthogonal: torch's _Orthogonal with orthogonal_map="householder" -- the map torch picks
+ * for n_filters != n_dim -- and use_trivialization=True), forward and backward, in compact WY form:
+ *     V (D,K) = strictly-lower(X^T) + [I_K; 0],  s_i = int(X[i,i]) (the stored +-1 diagonal, not differentiated)
+ *     M = striu(V^T V) + diag(|v_i|^2 / 2),  W = M^-1 V_top^T,  P = [I_K; 0] - V W   (= H_1 ... H_K [I_K; 0], orgqr convention)
+ *     F = (base (P * s))^T
+ * in place of tril -> column norms -> torch.linalg.householder_product -> sign -> base @ Q and their autograd backward.
+ * Every K x K quantity (V^T V, M, both triangular solves) is computed in double whatever the dtype; sums over D are
+ * per-block partial sums added in a fixed order (no atomics): results are bitwise reproducible.  Nothing is allocated,
+ * synchronised or read back: the calls can be captured in a HIP graph on the caller's stream.
+ *   X (K,D) raw parameter, base (D,D), F_out / gF / gX_out (K,D): row-major, dtype; 1 <= K <= 64, K < D
+ *   gX_out: gradient of sum(F * gF) wrt X, exactly 0 on and above the diagonal of X^T (as torch returns)
+ *   workspace: sqfa_orthogonal_workspace_bytes(K, D, dtype) bytes for either call (0 = shape or dtype not supported).
+ *   sqfa_orthogonal_backward recomputes M and W from X: it needs X, base, gF and ANY workspace of that size, nothing
+ *   of a forward call's workspace.
+ * Returns SQFA_ERR_BAD_ARGUMENT (null pointers, K < 1, K >= D, dtype), SQFA_ERR_UNSUPPORTED_M (K > 64),
+ * SQFA_ERR_WORKSPACE; every argument check runs before the first HIP call.
+ */
+size_t sqfa_orthogonal_workspace_bytes(int K, int D, int dtype);
+int sqfa_orthogonal_forward(const void *X, const void *base, int K, int D, int dtype,
+                            void *F_out, void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_orthogonal_backward(const void *X, const void *base, const void *gF, int K, int D, int dtype,
+                             void *gX_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Introspection (benchmarks / development; not needed by a reference-side binding).
  *
  * sqfa_airm_profile(1): every following sqfa_airm_pairwise call brackets its pair tile kernel

@@ -130,6 +130,17 @@ PROTOTYPES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "sqfa_orthogonal_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sqfa_orthogonal_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_size_t, ctypes.c_void_p],
+    ),
+    "sqfa_orthogonal_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
+    ),
     "sqfa_lbfgs_max_history": (ctypes.c_int, []),
     "sqfa_lbfgs_work_elems": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "sqfa_lbfgs_push": (

@@ -747,6 +747,63 @@ def project_scatters(scatters, filters):
 
 
 # ------------------------------------------------------------------------------------------
+# the orthogonal filter constraint (torch's _Orthogonal, Householder map with a `base` matrix)
+
+ORTHOGONAL_MAX_FILTERS = 64
+
+
+def orthogonal_supported(X, base):
+    """The native map handles a contiguous float32/float64 (K,D) raw parameter on the GPU with K <= 64 and K < D (the
+    shapes for which torch picks the Householder map) and a contiguous (D,D) base of the same dtype and device; anything
+    else keeps torch's own forward."""
+    if X is None or base is None:
+        return False
+    return bool(X.is_cuda and base.is_cuda and X.dtype in (torch.float32, torch.float64) and base.dtype == X.dtype
+                and X.dim() == 2 and base.dim() == 2 and 1 <= X.shape[0] <= ORTHOGONAL_MAX_FILTERS
+                and X.shape[0] < X.shape[1] and tuple(base.shape) == (X.shape[1], X.shape[1])
+                and X.device == base.device and X.is_contiguous() and base.is_contiguous())
+
+
+def _orthogonal_call(forward, X, base, gF=None):
+    """sqfa_orthogonal_forward / sqfa_orthogonal_backward on the current stream (workspace from the torch allocator, no
+    host read-back: safe inside a graph capture).  Returns F or dL/dX, (K,D)."""
+    lib = _lib.load()
+    K, D = X.shape
+    code = _dtype_code(X)
+    nbytes = lib.sqfa_orthogonal_workspace_bytes(K, D, code)
+    if nbytes == 0:
+        raise _lib.NativeLibraryError("sqfa_orthogonal_workspace_bytes rejected the problem shape")
+    with torch.cuda.device(X.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+        out = torch.empty_like(X)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+        if forward:
+            _lib.check(lib.sqfa_orthogonal_forward(_ptr(X), _ptr(base), K, D, code, _ptr(out), _ptr(ws), nbytes, stream),
+                       "sqfa_orthogonal_forward")
+        else:
+            _lib.check(lib.sqfa_orthogonal_backward(_ptr(X), _ptr(base), _ptr(gF), K, D, code, _ptr(out), _ptr(ws), nbytes,
+                                                    stream), "sqfa_orthogonal_backward")
+    return out
+
+
+class OrthogonalFilters(torch.autograd.Function):
+    """F = (base @ householder_product(tril(X^T, -1), tau) * sign)^T, torch's _Orthogonal.forward for a wide (K,D) raw
+    parameter (reference: src/sqfa/model.py:416-431), through sqfa_orthogonal_forward / sqfa_orthogonal_backward
+    (compact WY form, 4 launches each way).  The backward recomputes from X: nothing but X and base is saved."""
+
+    @staticmethod
+    def forward(ctx, X, base):
+        Xc, Bc = X.detach().contiguous(), base.detach().contiguous()
+        ctx.save_for_backward(Xc, Bc)
+        return _orthogonal_call(True, Xc, Bc)
+
+    @staticmethod
+    def backward(ctx, gF):
+        Xc, Bc = ctx.saved_tensors
+        return _orthogonal_call(False, Xc, Bc, gF.detach().contiguous()), None
+
+
+# ------------------------------------------------------------------------------------------
 # the whole closure as one autograd node (SURVEY.md 8f rank 3; VERDICT r1 item 8)
 
 
@@ -764,9 +821,10 @@ def fused_closure_supported(raw_filters, scatters, means):
 
 
 def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
-    """First half of a closure evaluation, no autograd: sphere -> T = Psi F^T -> [m = mu F^T] -> S | E
+    """First half of a closure evaluation, no autograd: parametrization -> T = Psi F^T -> [m = mu F^T] -> S | E
     (feature scatters + noise, or their Calvo-Oller embedding), written into `out_S` when given (a slice of
-    the all-gather buffer of a class-sharded evaluation).  Returns what the backward stage needs."""
+    the all-gather buffer of a class-sharded evaluation).  Returns what the backward stage needs.
+    `sphere`: True (Sphere), False (Identity), or the (D,D) `base` tensor of an orthogonal parametrization."""
     lib = _lib.load()
     X = raw.detach().contiguous()
     Psi = scatters.detach()
@@ -776,7 +834,11 @@ def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
     dev, dt = Psi.device, Psi.dtype
     with torch.cuda.device(dev):
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if sphere:
+        base = sphere.detach() if torch.is_tensor(sphere) else None
+        sphere = base is None and bool(sphere)
+        if base is not None:
+            F, norms = _orthogonal_call(True, X, base), None
+        elif sphere:
             F = torch.empty_like(X)
             norms = torch.empty(K, dtype=dt, device=dev)
             _lib.check(lib.sqfa_sphere_forward(_ptr(X), K, D, code, _ptr(F), _ptr(norms), stream), "sqfa_sphere_forward")
@@ -792,7 +854,7 @@ def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
         _lib.check(lib.sqfa_feature_scatters_ex(_ptr(F), K, D, _ptr(T), C, code, float(noise), _ptr(m), _ptr(S), stream),
                    "sqfa_feature_scatters_ex")
     return {"X": X, "norms": norms, "T": T, "m": m, "means": means.detach() if means is not None else None,
-            "S": S, "S_shape": tuple(S.shape), "sphere": sphere}
+            "S": S, "S_shape": tuple(S.shape), "sphere": sphere, "base": base}
 
 
 def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None, metric="airm"):
@@ -818,7 +880,8 @@ def closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight,
 
 def closure_stage_backward(st, gS, gloss):
     """Kernels from dL/dS (or dL/dE) back to the raw filter parameter: backward product, [means path],
-    class reduction + sphere backward (+ multiplication by `gloss`, a device scalar or None)."""
+    class reduction + sphere backward (+ multiplication by `gloss`, a device scalar or None); for an orthogonal
+    parametrization the class reduction (sphere backward without norms) and then sqfa_orthogonal_backward."""
     lib = _lib.load()
     X, norms, T, m, means = st["X"], st["norms"], st["T"], st["m"], st["means"]
     C, D, K = T.shape
@@ -842,6 +905,8 @@ def closure_stage_backward(st, gS, gloss):
         gl = gloss.detach().to(dt).contiguous() if gloss is not None else None
         _lib.check(lib.sqfa_sphere_backward(_ptr(X), _ptr(norms if st["sphere"] else None), K, D, code, _ptr(partial), groups,
                                             _ptr(extra), _ptr(gl), _ptr(grad), stream), "sqfa_sphere_backward")
+        if st.get("base") is not None:
+            grad = _orthogonal_call(False, X, st["base"], grad)
     return grad
 
 
@@ -849,9 +914,10 @@ class FusedClosure(torch.autograd.Function):
     """loss(raw filters) of one closure evaluation as ONE autograd node, 8 launches for
     SecondMomentsSQFA and 11 for SQFA instead of ~40:
 
-        forward   sphere (or nothing)  ->  T = Psi F^T (streaming)  ->  [m = mu F^T]  ->
+        forward   sphere (or nothing, or the orthogonal map: 4 launches)  ->  T = Psi F^T (streaming)  ->  [m = mu F^T]  ->
                   S = F T + noise I  |  E = [[S + m m^T, m], [m^T, 1]]  ->  K0 / K1 / K2 (loss, dL/dS, flags)
         backward  (G + G^T) T^T partial sums  ->  [g_m, g_m^T mu]  ->  class reduction + sphere backward + gloss
+                  [-> orthogonal backward: 4 launches]
 
     Same arithmetic as the chain Sphere -> ProjectScatters -> (+noise) -> embed_gaussian -> PairwiseLoss
     it replaces (reference: src/sqfa/constraints.py:37, src/sqfa/model.py:172-188, 508-546,

@@ -6,12 +6,11 @@ and their backward run on the HIP kernels (distances.py, _native.py).
 """
 import torch
 import torch.nn as nn
-from torch.nn.utils.parametrizations import orthogonal
 from torch.nn.utils.parametrize import register_parametrization, remove_parametrizations
 
 from . import _native, distances
 from ._optim import fitting_loop
-from .constraints import FixedFilters, Identity, Sphere
+from .constraints import FixedFilters, Identity, Orthogonal, Sphere, orthogonal
 from .linalg import conjugate_matrix
 from .statistics import class_statistics, pca, pca_from_scatter
 
@@ -167,15 +166,20 @@ class SecondMomentsSQFA(nn.Module):
     SINGLE_NODE_CLOSURE = True
 
     def _single_node_inputs(self, prepared, allow_class_shard=False):
-        """(raw parameter, scatters, means, sphere?) when the closure can run as one node: a single
-        Sphere or Identity parametrization on the filters, supported shapes; class-sharded statistics
-        only for the fitting loop's staged (graph) closure, which places the collectives itself."""
+        """(raw parameter, scatters, means, kind) when the closure can run as one node: a single Sphere (kind True),
+        Identity (False) or native Orthogonal (its `base` tensor) parametrization on the filters, supported shapes;
+        class-sharded statistics only for the fitting loop's staged (graph) closure, which places the collectives itself."""
         if not self.SINGLE_NODE_CLOSURE or (self.class_shard is not None and not allow_class_shard):
             return None
         plist = getattr(getattr(self, "parametrizations", None), "filters", None)
-        if plist is None or len(plist) != 1 or type(plist[0]) not in (Sphere, Identity):
+        if plist is None or len(plist) != 1 or type(plist[0]) not in (Sphere, Identity, Orthogonal):
             return None
         raw = plist.original
+        kind = type(plist[0]) is Sphere
+        if type(plist[0]) is Orthogonal:
+            kind = plist[0].native_base(raw)
+            if kind is None:
+                return None
         if isinstance(prepared, dict):
             scatters, means = prepared["covariances"], prepared["means"]
         else:
@@ -184,7 +188,7 @@ class SecondMomentsSQFA(nn.Module):
             return None
         if not _native.fused_closure_supported(raw, scatters, means):
             return None
-        return raw, scatters, means, type(plist[0]) is Sphere
+        return raw, scatters, means, kind
 
     def _fused_closure_loss(self, prepared):
         """(loss, flags) through one fused loss+gradient launch, or None when the model's

@@ -204,8 +204,9 @@ int sqfa_airm_eigenvalues_backward(const void *A, int nA, const void *B, int nB,
  * Psi (C,D,D) is read from HBM exactly once; S_c = F T_c and, in the backward pass,
  * dL/dF = sum_c (G_c + G_c^T) T_c^T need only T (C,D,K).  Psi_c is assumed symmetric
  * (covariance / second-moment matrices).
- *   F (K,D) row-major, Psi (C,D,D), T_out (C,D,K) row-major; float32 or float64, D % 4 == 0, K <= 64
- *   (SQFA_ERR_UNSUPPORTED_M otherwise: the caller keeps its own path for those shapes).
+ *   F (K,D) row-major, Psi (C,D,D), T_out (C,D,K) row-major; float32 or float64, D % 4 == 0, K <= 64, Psi 16-byte
+ *   aligned -- it is read with 16-byte loads only; F and T_out may have any element alignment
+ *   (SQFA_ERR_UNSUPPORTED_M otherwise, decided before any HIP call: the caller keeps its own path for those inputs).
  */
 int sqfa_project_scatters(const void *F, int K, int D, const void *Psi, int C, int dtype, void *T_out,
                           void *stream);
@@ -220,8 +221,10 @@ int sqfa_project_scatters(const void *F, int K, int D, const void *Psi, int C, i
  *   sqfa_pack_scatters              Psi (C,D,D) -> packed_out (C, sqfa_packed_scatter_elems(D)); reads the LOWER triangle
  *                                   and the diagonal blocks of Psi
  *   sqfa_project_scatters_packed    T_out (C,D,K) = Psi_c F^T from the packed form
- * float32, D % 16 == 0, 16 <= D <= 4096, K <= 64 (SQFA_ERR_UNSUPPORTED_M otherwise: keep the full tensor and
- * sqfa_project_scatters).  One workgroup per class: meant for C >= a few hundred classes.
+ * float32, D % 16 == 0, 16 <= D <= 4096, K <= 64; 16-byte aligned pointers: Psi and packed_out of sqfa_pack_scatters,
+ * packed and F of sqfa_project_scatters_packed, and its T_out when K % 4 == 0 (these kernels have no scalar paths)
+ * (SQFA_ERR_UNSUPPORTED_M otherwise, decided before any HIP call: keep the full tensor and sqfa_project_scatters).
+ * One workgroup per class: meant for C >= a few hundred classes.
  */
 size_t sqfa_packed_scatter_elems(int D);
 int sqfa_pack_scatters(const void *Psi, int C, int D, int dtype, void *packed_out, void *stream);

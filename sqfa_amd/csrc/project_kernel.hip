@@ -174,6 +174,9 @@ extern "C" int sqfa_project_scatters(const void* F, int K, int D, const void* Ps
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (F == nullptr || Psi == nullptr || T_out == nullptr || K < 1 || D < 4 || C < 1) return SQFA_ERR_BAD_ARGUMENT;
   if ((dtype != SQFA_F32 && dtype != SQFA_F64) || (D % 4) != 0 || K > 64 || K > D) return SQFA_ERR_UNSUPPORTED_M;
+  // the kernel reads Psi with 16-byte loads whatever the shape (F and T_out have scalar paths): a Psi that is not
+  // 16-byte aligned is the caller's own path, like D % 4 != 0 -- decided here, before any HIP call
+  if ((reinterpret_cast<size_t>(Psi) & 15) != 0) return SQFA_ERR_UNSUPPORTED_M;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   bool prof = sqfa_profile_enabled();
   if (prof) {  // no event records inside a captured graph

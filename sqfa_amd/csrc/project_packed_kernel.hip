@@ -327,6 +327,8 @@ extern "C" int sqfa_pack_scatters(const void* Psi, int C, int D, int dtype, void
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (Psi == nullptr || packed_out == nullptr || C < 1 || D < 1) return SQFA_ERR_BAD_ARGUMENT;
   if (dtype != SQFA_F32 || D < 16 || (D % 16) != 0 || D > 4096) return SQFA_ERR_UNSUPPORTED_M;
+  // 16-byte loads of Psi and 16-byte stores of the packed form, unconditionally
+  if (((reinterpret_cast<size_t>(Psi) | reinterpret_cast<size_t>(packed_out)) & 15) != 0) return SQFA_ERR_UNSUPPORTED_M;
   const size_t ce = packed_class_elems(D);
   const dim3 grid((unsigned)((ce / 4 + 255) / 256), C, 1);
   hipLaunchKernelGGL(pack_scatters_kernel, grid, dim3(256), 0, stream, static_cast<const float*>(Psi), static_cast<float*>(packed_out), D, ce);
@@ -339,6 +341,10 @@ extern "C" int sqfa_project_scatters_packed(const void* F, int K, int D, const v
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (F == nullptr || packed == nullptr || T_out == nullptr || K < 1 || D < 1 || C < 1) return SQFA_ERR_BAD_ARGUMENT;
   if (dtype != SQFA_F32 || D < 16 || (D % 16) != 0 || D > 4096 || K > 64 || K > D) return SQFA_ERR_UNSUPPORTED_M;
+  // 16-byte loads of the packed tiles and of F (the row-output operand), 16-byte stores of T_out when K % 4 == 0: none
+  // of them has a scalar path in this kernel
+  if (((reinterpret_cast<size_t>(packed) | reinterpret_cast<size_t>(F)) & 15) != 0) return SQFA_ERR_UNSUPPORTED_M;
+  if ((K & 3) == 0 && (reinterpret_cast<size_t>(T_out) & 15) != 0) return SQFA_ERR_UNSUPPORTED_M;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   bool prof = sqfa_profile_enabled();
   if (prof) {  // no event records inside a captured graph

@@ -131,3 +131,27 @@ def test_argument_validation_of_the_round2_entry_points():
     assert lib.sqfa_spd_function(fake, 3, 4, 0, 0, fake, fake, fake, fake, 8, z) == -3               # workspace
     assert lib.sqfa_spd_function_backward(fake, fake, z, 3, 4, 0, 0, fake, z) == -1                  # null G
     assert lib.sqfa_spd_function_backward(fake, fake, fake, 3, 65, 0, 0, fake, z) == -2
+
+
+def test_projection_entries_refuse_misaligned_vector_operands():
+    """The streaming projection reads Psi with 16-byte loads only, and the packed pair of entries reads and writes every
+    operand that way (include/sqfa_hip.h): a pointer that is not 16-byte aligned is SQFA_ERR_UNSUPPORTED_M -- the caller
+    keeps its own path, as for D % 4 != 0 -- decided on the host before any HIP call.  (Only refused calls are made here:
+    nothing is launched.)"""
+    lib = _lib.load()
+    z, fake = ctypes.c_void_p(0), ctypes.c_void_p(4096)
+    for off in (4, 8, 12):
+        mis = ctypes.c_void_p(4096 + off)
+        for dtype in (_lib.SQFA_F32, _lib.SQFA_F64):
+            assert lib.sqfa_project_scatters(fake, 4, 8, mis, 3, dtype, fake, z) == -2
+            assert lib.sqfa_project_scatters(mis, 4, 8, mis, 3, dtype, mis, z) == -2
+        assert lib.sqfa_pack_scatters(mis, 3, 64, _lib.SQFA_F32, fake, z) == -2
+        assert lib.sqfa_pack_scatters(fake, 3, 64, _lib.SQFA_F32, mis, z) == -2
+        assert lib.sqfa_project_scatters_packed(fake, 4, 64, mis, 3, _lib.SQFA_F32, fake, z) == -2      # packed
+        assert lib.sqfa_project_scatters_packed(mis, 4, 64, fake, 3, _lib.SQFA_F32, fake, z) == -2      # F
+        assert lib.sqfa_project_scatters_packed(fake, 4, 64, fake, 3, _lib.SQFA_F32, mis, z) == -2      # T_out, K % 4 == 0
+    # the argument checks that come first keep their codes
+    assert lib.sqfa_project_scatters(fake, 4, 8, z, 3, 0, fake, z) == -1
+    assert lib.sqfa_project_scatters(fake, 4, 10, ctypes.c_void_p(4100), 3, 0, fake, z) == -2
+    assert lib.sqfa_pack_scatters(z, 3, 64, 0, fake, z) == -1
+    assert lib.sqfa_project_scatters_packed(fake, 4, 64, z, 3, 0, fake, z) == -1

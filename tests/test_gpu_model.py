@@ -435,7 +435,10 @@ def test_class_statistics_on_gpu_vs_reference(dtype, tol):
 @pytest.mark.parametrize("constraint", ["sphere", "none"])
 @pytest.mark.parametrize("model_name,C,D,K", [("smsqfa", 24, 96, 4), ("sqfa", 24, 96, 4), ("sqfa", 300, 64, 16),
                                               ("smsqfa", 7, 132, 32), ("sqfa", 5, 40, 8), ("sqfa", 12, 64, 9),
-                                              ("smsqfa", 300, 96, 2), ("sqfa", 40, 48, 1), ("smsqfa", 9, 72, 17)])
+                                              ("smsqfa", 300, 96, 2), ("sqfa", 40, 48, 1), ("smsqfa", 9, 72, 17),
+                                              # SQFA above K = 16: the embedding epilogue with two to four filter blocks;
+                                              # K = 64 is m = 65, the LDS pair kernel
+                                              ("sqfa", 12, 72, 17), ("sqfa", 8, 132, 33), ("sqfa", 6, 132, 64)])
 def test_single_node_closure_matches_autograd_chain(model_name, C, D, K, constraint, dtype):
     """_native.FusedClosure (sphere -> projection -> noise/embedding -> pair loss as ONE autograd node,
     8 / 11 launches) against the chain of autograd nodes it replaces: same loss, flags and gradient
@@ -458,6 +461,43 @@ def test_single_node_closure_matches_autograd_chain(model_name, C, D, K, constra
     tol = 1e-12 if dtype == torch.float64 else 2e-6
     assert abs(l1 - l0) <= tol * abs(l0)
     assert rel_err(g1.cpu(), g0.cpu()) <= (1e-10 if dtype == torch.float64 else 2e-4)
+
+
+@pytest.mark.parametrize("constraint", ["sphere", "none"])
+@pytest.mark.parametrize("C,D,K", [(12, 72, 17), (8, 132, 33), (6, 132, 64)])
+def test_sqfa_closure_above_16_filters_vs_cpu_reference_f64(C, D, K, constraint):
+    """SQFA closures with m = K + 1 = 18, 34 and 65 (the last on the LDS pair kernel) through the single-node path, float64,
+    against a reference that shares no code with them: tests/projection_oracle.stage (normalise -> F Psi F^T + noise I ->
+    oracle.reference_path.embed_gaussian, differentiated by torch autograd on the CPU) around
+    oracle.reference_path.pairwise_loss_and_grad (the reference's eigh route; scale 1/2 on the embeddings).  Loss and
+    raw-parameter gradient for a non-unit incoming gradient, at the bounds of test_closure_f64."""
+    import projection_oracle as po
+    from oracle import reference_path
+    stats = mc.c2_statistics(C=C, D=D)
+    model = mc.make_model("sqfa", D, K, 0.01, constraint, torch.float64, DEV)
+    prepared = model._prepare_statistics({k: v.to(DEV) for k, v in stats.items()})
+    assert model._single_node_inputs(prepared) is not None, "the closure fell back to the chain of autograd nodes"
+    raw = model.parametrizations.filters.original.detach().cpu().numpy()
+    kind = "sphere" if constraint == "sphere" else "identity"
+    cov, mu = stats["covariances"].numpy(), stats["means"].numpy()
+    # the regulariser the model holds, not 0.01: noise_mat is built from a float32 scalar as in the reference
+    # (src/sqfa/model.py:160), 0.009999999776...; 0.01 itself moves the loss by 3e-10
+    noise = float(model.noise_mat[0, 0])
+    assert noise == float(np.float32(0.01))
+    E = po.stage(raw, cov, mu, noise, kind, np.zeros((C, K + 1, K + 1)), 1.0)["out"].value
+    loss_ref, gE, _ = reference_path.pairwise_loss_and_grad(torch.tensor(E), scale=0.5, sqrt_mode=True)
+    gE = gE.numpy()
+    gref = po.stage(raw, cov, mu, noise, kind, 0.5 * (gE + gE.transpose(0, 2, 1)), 3.0)["dX_autograd"]
+    model.zero_grad()
+    loss, flags = model._fused_closure_loss(prepared)
+    (3.0 * loss).backward()
+    assert flags.tolist() == [0, 0]
+    g = model.parametrizations.filters.original.grad.cpu().numpy()
+    err_l = abs(loss.item() - float(loss_ref)) / abs(float(loss_ref))
+    err_g = np.linalg.norm(g - gref) / max(np.linalg.norm(gref), 1e-3)
+    print(f"SQFA C={C} D={D} K={K} {constraint}: loss rel err {err_l:.2e}, gradient rel err {err_g:.2e}")
+    assert err_l <= 1e-10
+    assert err_g <= 1e-7
 
 
 def test_c1_config_full_fit_matches_reference_f64():

@@ -7,10 +7,12 @@ functions call through); it refuses CPU tensors and there is no other implementa
 this package.
 """
 import ctypes
+import math
 
 import torch
 
 from . import _lib
+from ._memo import TensorMemo
 
 EPSILON = 1e-6  # value added inside square roots (reference: src/sqfa/distances.py:29)
 
@@ -29,6 +31,22 @@ def _ptr(t):
 
 def max_dim():
     return _lib.load().sqfa_hip_max_dim()
+
+
+class _on_stream(torch.cuda.device):
+    """with _on_stream(dev) as stream: `dev` is current (torch allocates there), `stream` its current stream as the C ABI's handle."""
+
+    def __enter__(self):
+        super().__enter__()
+        return ctypes.c_void_p(torch.cuda.current_stream(self.idx).cuda_stream)
+
+
+def _workspace(query, *args):
+    """(uint8 workspace on the current device, its size) as the library's `query(*args)` asks for."""
+    nbytes = query(*args)
+    if nbytes == 0:
+        raise _lib.NativeLibraryError(f"{query.__name__} rejected the problem shape")
+    return torch.empty(nbytes, dtype=torch.uint8, device="cuda"), nbytes
 
 
 # Per-call policies of the pair kernels (sqfa_airm_options, include/sqfa_hip.h), read at every launch -- from whichever
@@ -100,13 +118,10 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
         )
     opts = _options()
     ws_query = lib.sqfa_bw_workspace_bytes_sharded if metric == "bw" else lib.sqfa_airm_workspace_bytes_sharded
-    nbytes = ws_query(nA, nB, m, code, int(shard[1]), opts.geometry_policy)
-    if nbytes == 0:
-        raise _lib.NativeLibraryError(f"{ws_query.__name__} rejected the problem shape")
     dev = A.device
     nBe = nA if B is None else nB
-    with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(ws_query, nA, nB, m, code, int(shard[1]), opts.geometry_policy)
         # out_loss / out_gradA: caller-provided views (e.g. into a fused all-reduce buffer)
         # (loss and the two validity counters are always written by the finalize kernel: no memset)
         loss = (out_loss if out_loss is not None else torch.empty((), dtype=A.dtype, device=dev)) if want_loss else None
@@ -122,13 +137,12 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
             weights = weights.detach().to(dtype=A.dtype, device=dev).contiguous()
             if tuple(weights.shape) != (nA, nBe):
                 raise ValueError("pair weights must have shape (nA, nB)")
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if metric == "bw":
             status = lib.sqfa_bw_pairwise(
                 _ptr(A), nA, _ptr(B), nB, m, code, float(eps), int(bool(sqrt_mode)),
                 _ptr(weights), float(uniform_weight), int(shard[0]), int(shard[1]),
                 _ptr(loss), _ptr(gradA), _ptr(gradB), _ptr(dist), _ptr(nonfinite),
-                _ptr(ws), nbytes, ctypes.c_void_p(stream), ctypes.byref(opts),
+                _ptr(ws), nbytes, stream, ctypes.byref(opts),
             )
             _lib.check(status, "sqfa_bw_pairwise")
             return {"loss": loss, "gradA": gradA, "gradB": gradB, "dist": dist, "eig": None, "nonfinite": nonfinite}
@@ -138,7 +152,7 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
             _ptr(weights), float(uniform_weight),
             int(shard[0]), int(shard[1]),
             _ptr(loss), _ptr(gradA), _ptr(gradB), _ptr(dist), _ptr(eig), _ptr(nonfinite),
-            _ptr(ws), nbytes, ctypes.c_void_p(stream), ctypes.byref(opts),
+            _ptr(ws), nbytes, stream, ctypes.byref(opts),
         )
     _lib.check(status, "sqfa_airm_pairwise_opt")
     return {"loss": loss, "gradA": gradA, "gradB": gradB, "dist": dist, "eig": eig, "nonfinite": nonfinite}
@@ -180,7 +194,42 @@ class PairDistanceMatrix(torch.autograd.Function):
         return out["gradA"], out["gradB"], None, None, None, None
 
 
-class PairwiseLoss(torch.autograd.Function):
+def fused_reduce_owner(reducer, shard):
+    """The reducer's owner when a sharded evaluation goes through the fused all-reduce buffer [loss, nan, inf, grad...] (the
+    pair kernel writes loss and gradient straight into it: no packing copies, ONE all-reduce), else None."""
+    owner = getattr(reducer, "__self__", None)
+    if reducer is not None and shard[1] > 1 and _pair_backend is hip_pair_backend and hasattr(owner, "reduce_fused"):
+        return owner
+    return None
+
+
+def fused_buffer(shape, dtype, device):
+    return torch.empty(math.prod(shape) + 3, dtype=dtype, device=device)
+
+
+def fused_outputs(fused, shape):
+    """The views of the buffer that the pair backend writes through (its out_loss / out_gradA arguments)."""
+    return {"out_loss": fused[0], "out_gradA": fused[3:].view(shape)}
+
+
+class _SavedGradientLoss(torch.autograd.Function):
+    """Base of the fused closure losses: forward gets loss, flags and the gradients of the first inputs from ONE native
+    pass and keeps the gradients (`_saved`); backward only scales them by the upstream gradient of the loss."""
+
+    @staticmethod
+    def _saved(ctx, n_inputs, loss, nonfinite, *grads):
+        ctx.save_for_backward(*grads)
+        ctx.n_inputs = n_inputs
+        ctx.mark_non_differentiable(nonfinite)
+        return loss, nonfinite
+
+    @staticmethod
+    def backward(ctx, gloss, _gflag):
+        grads = ctx.saved_tensors
+        return tuple(g * gloss for g in grads) + (None,) * (ctx.n_inputs - len(grads))
+
+
+class PairwiseLoss(_SavedGradientLoss):
     """Fused closure loss: sum over the unordered pairs i>j of  weight * dist(S_i, S_j)
     (weight = -1/P gives the reference's -mean, src/sqfa/_optim.py:94) together with its
     gradient, in one pass.  `reducer(loss, nonfinite, grad)` combines shards (all-reduce)."""
@@ -188,14 +237,10 @@ class PairwiseLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, S, scale, eps, sqrt_mode, weight, shard, reducer, metric="airm"):
         extra = {"metric": metric} if metric != "airm" else {}
-        fused = None
-        owner = getattr(reducer, "__self__", None)
-        if (reducer is not None and shard[1] > 1 and _pair_backend is hip_pair_backend
-                and hasattr(owner, "reduce_fused")):
-            # the kernel writes loss and gradient straight into the all-reduce buffer
-            # [loss, nan, inf, grad...]: no packing copies
-            fused = torch.empty(S.numel() + 3, dtype=S.dtype, device=S.device)
-            extra.update({"out_loss": fused[0], "out_gradA": fused[3:].view(S.shape)})
+        owner = fused_reduce_owner(reducer, shard)
+        fused = fused_buffer(S.shape, S.dtype, S.device) if owner is not None else None
+        if fused is not None:
+            extra.update(fused_outputs(fused, S.shape))
         out = _pair_backend(S, None, scale=scale, eps=eps, sqrt_mode=sqrt_mode, weights=None,
                             uniform_weight=weight, shard=shard, want_loss=True, want_grad=True,
                             want_dist=False, want_eig=False, **extra)
@@ -204,14 +249,7 @@ class PairwiseLoss(torch.autograd.Function):
             loss, nonfinite, grad = owner.reduce_fused(fused, nonfinite, S.shape)
         elif reducer is not None:
             loss, nonfinite, grad = reducer(loss, nonfinite, grad)
-        ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(nonfinite)
-        return loss, nonfinite
-
-    @staticmethod
-    def backward(ctx, gloss, _gflag):
-        (grad,) = ctx.saved_tensors
-        return grad * gloss, None, None, None, None, None, None, None
+        return _SavedGradientLoss._saved(ctx, 8, loss, nonfinite, grad)
 
 
 def hip_eigenvalues_backward(A, B, eig_weights):
@@ -225,16 +263,12 @@ def hip_eigenvalues_backward(A, B, eig_weights):
     W = eig_weights.detach().to(A.dtype).contiguous()
     nA, nB, m = A.shape[0], B.shape[0], A.shape[-1]
     code = _dtype_code(A)
-    nbytes = lib.sqfa_airm_workspace_bytes(nA, nB, m, code)
-    if nbytes == 0:
-        raise _lib.NativeLibraryError("sqfa_airm_workspace_bytes rejected the problem shape")
-    with torch.cuda.device(A.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+    with _on_stream(A.device) as stream:
+        ws, nbytes = _workspace(lib.sqfa_airm_workspace_bytes, nA, nB, m, code)
         gA, gB = torch.empty_like(A), torch.empty_like(B)
-        stream = torch.cuda.current_stream(A.device).cuda_stream
         opts = _options()   # the policies of the forward call: the kernel's eigenvalue order depends on the lane geometry
         status = lib.sqfa_airm_eigenvalues_backward(_ptr(A), nA, _ptr(B), nB, m, code, _ptr(W), _ptr(gA), _ptr(gB),
-                                                    _ptr(ws), nbytes, ctypes.c_void_p(stream), ctypes.byref(opts))
+                                                    _ptr(ws), nbytes, stream, ctypes.byref(opts))
     _lib.check(status, "sqfa_airm_eigenvalues_backward")
     return gA, gB
 
@@ -275,6 +309,22 @@ def generalized_eigenvalues_raw(A, B):
 # Gaussian pair terms (bhattacharyya / mahalanobis / hellinger / fisher_rao_same_cov)
 
 
+def _gauss_padded_size(m, n_pairs):
+    """The one-pair-per-lane kernel reads whole 16-byte rows when the matrices ARE its padded size (4 / 8 / 12 / 16): from
+    20000 pairs on the callers pad with an identity block themselves (_pad_gauss) instead of letting the kernel pad with
+    scalar loads and selects (K=15 at C=1000: 1.11 -> 0.55 ms forward + backward)."""
+    return (m + 3) // 4 * 4 if (m < 16 and m % 4 != 0 and n_pairs >= 20000) else m
+
+
+def _pad_gauss(mu, cov, M):
+    """Identity padding of (n,m) means / (n,m,m) covariances to size M: exact for Q, logdet and the distances built on
+    them (log 1 = 0; the padded coordinates have delta = 0)."""
+    m = cov.shape[-1]
+    cov_p = torch.eye(M, dtype=cov.dtype, device=cov.device).repeat(cov.shape[0], 1, 1)
+    cov_p[:, :m, :m] = cov
+    return torch.nn.functional.pad(mu, (0, M - m)), cov_p
+
+
 def hip_gauss_terms(muA, covA, muB, covB, gQ=None, gLD=None, want_outputs=True, want_grad=False):
     """sqfa_gauss_pair_terms on the current stream.  Returns (Q, LD, gmuA, gcovA) (None where not requested)."""
     lib = _lib.load()
@@ -282,32 +332,20 @@ def hip_gauss_terms(muA, covA, muB, covB, gQ=None, gLD=None, want_outputs=True, 
         raise RuntimeError("sqfa_amd's native Gaussian pair terms run on the GPU only")
     muA, covA, muB, covB = (t.detach().contiguous() for t in (muA, covA, muB, covB))
     nA, nB, m = covA.shape[0], covB.shape[0], covA.shape[-1]
-    m_true = m
-    if m < 16 and m % 4 != 0 and nA * nB >= 20000:
-        # the one-pair-per-lane kernel reads whole 16-byte rows when the matrices ARE its padded size (4 / 8 / 12 / 16):
-        # pad with an identity block here (exact: logdet + log 1, Q unchanged) instead of letting it pad with scalar
-        # loads and selects (K=15 at C=1000: 1.11 -> 0.55 ms forward + backward)
-        M = (m + 3) // 4 * 4
-
-        def pad(mu, cov):
-            cov_p = torch.eye(M, dtype=cov.dtype, device=cov.device).repeat(cov.shape[0], 1, 1)
-            cov_p[:, :m, :m] = cov
-            return torch.nn.functional.pad(mu, (0, M - m)), cov_p
-
-        same = muB.data_ptr() == muA.data_ptr() and covB.data_ptr() == covA.data_ptr() and nA == nB
-        muA, covA = pad(muA, covA)
-        muB, covB = (muA, covA) if same else pad(muB, covB)
-        m = M
+    m_true, m = m, _gauss_padded_size(m, nA * nB)
+    if m != m_true:
+        same = muB.data_ptr() == muA.data_ptr() and covB.data_ptr() == covA.data_ptr() and nA == nB   # B is A: pad once
+        muA, covA = _pad_gauss(muA, covA, m)
+        muB, covB = (muA, covA) if same else _pad_gauss(muB, covB, m)
     code = _dtype_code(covA)
     dev, dt = covA.device, covA.dtype
-    with torch.cuda.device(dev):
+    with _on_stream(dev) as stream:
         Q = torch.empty((nA, nB), dtype=dt, device=dev) if want_outputs else None
         LD = torch.empty((nA, nB), dtype=dt, device=dev) if want_outputs else None
         gmu = torch.empty((nA, m), dtype=dt, device=dev) if want_grad else None
         gcov = torch.empty((nA, m, m), dtype=dt, device=dev) if want_grad else None
         gQ = gQ.detach().to(dt).contiguous() if gQ is not None else None
         gLD = gLD.detach().to(dt).contiguous() if gLD is not None else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         status = lib.sqfa_gauss_pair_terms(_ptr(muA), _ptr(covA), nA, _ptr(muB), _ptr(covB), nB, m, code,
                                            _ptr(gQ), _ptr(gLD), _ptr(Q), _ptr(LD), _ptr(gmu), _ptr(gcov), stream)
     _lib.check(status, "sqfa_gauss_pair_terms")
@@ -345,15 +383,6 @@ class GaussPairTerms(torch.autograd.Function):
         return gmuA, gcovA, gmuB, gcovB, None
 
 
-def _pad_gauss(mu, cov, M):
-    """Identity padding of (n,m) means / (n,m,m) covariances to size M: exact for Q, logdet and the distances built on
-    them (log 1 = 0; the padded coordinates have delta = 0)."""
-    m = cov.shape[-1]
-    cov_p = torch.eye(M, dtype=cov.dtype, device=cov.device).repeat(cov.shape[0], 1, 1)
-    cov_p[:, :m, :m] = cov
-    return torch.nn.functional.pad(mu, (0, M - m)), cov_p
-
-
 def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dist=False):
     """sqfa_gauss_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe inside
     a graph capture).  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested)."""
@@ -366,24 +395,18 @@ def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dis
     n, m = cov.shape[0], cov.shape[-1]
     if m > GAUSS_MAX_DIM:
         raise NotImplementedError(f"feature dimension {m} exceeds the native Gaussian pair kernels' limit ({GAUSS_MAX_DIM})")
-    m_true = m
-    if m < 16 and m % 4 != 0 and n * n >= 20000:
-        # same rule as hip_gauss_terms: the one-pair-per-lane kernel reads whole 16-byte rows at its own sizes
-        m = (m + 3) // 4 * 4
+    m_true, m = m, _gauss_padded_size(m, n * n)
+    if m != m_true:
         mu, cov = _pad_gauss(mu, cov, m)
     code = _dtype_code(cov)
-    nbytes = lib.sqfa_gauss_pairwise_workspace_bytes(n, m, code)
-    if nbytes == 0:
-        raise _lib.NativeLibraryError("sqfa_gauss_pairwise_workspace_bytes rejected the problem shape")
     dev, dt = cov.device, cov.dtype
-    with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(lib.sqfa_gauss_pairwise_workspace_bytes, n, m, code)
         loss = torch.empty((), dtype=dt, device=dev)
         nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
         gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad else None
         gcov = torch.empty((n, m, m), dtype=dt, device=dev) if want_grad else None
         dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         status = lib.sqfa_gauss_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), float(weight),
                                               _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist), _ptr(nonfinite),
                                               _ptr(ws), nbytes, stream)
@@ -393,7 +416,7 @@ def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dis
     return {"loss": loss, "gmu": gmu, "gcov": gcov, "dist": dist, "nonfinite": nonfinite}
 
 
-class GaussPairwiseLoss(torch.autograd.Function):
+class GaussPairwiseLoss(_SavedGradientLoss):
     """Fused closure loss of the Gaussian pair distances (kind: _lib.SQFA_GAUSS_*): weight * sum over the unordered
     class pairs of bhattacharyya / hellinger / mahalanobis[_sq], with its gradient wrt means (C,K) and covariances
     (C,K,K), from ONE pass over the pairs (sqfa_gauss_pairwise_loss) -- in place of GaussPairTerms forward + the
@@ -402,14 +425,7 @@ class GaussPairwiseLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, covariances, kind, eps, weight):
         out = hip_gauss_pairwise_loss(means, covariances, kind, eps, weight)
-        ctx.save_for_backward(out["gmu"], out["gcov"])
-        ctx.mark_non_differentiable(out["nonfinite"])
-        return out["loss"], out["nonfinite"]
-
-    @staticmethod
-    def backward(ctx, gloss, _gflag):
-        gmu, gcov = ctx.saved_tensors
-        return gmu * gloss, gcov * gloss, None, None, None
+        return _SavedGradientLoss._saved(ctx, 5, out["loss"], out["nonfinite"], out["gmu"], out["gcov"])
 
 
 # ------------------------------------------------------------------------------------------
@@ -437,16 +453,12 @@ class SpdFunction(torch.autograd.Function):
         S3 = S.detach().contiguous()
         n, m = S3.shape[0], S3.shape[-1]
         code = _dtype_code(S3)
-        nbytes = lib.sqfa_spd_function_workspace_bytes(n, m, code)
-        if nbytes == 0:
-            raise _lib.NativeLibraryError("sqfa_spd_function_workspace_bytes rejected the problem shape")
         dev = S3.device
-        with torch.cuda.device(dev):
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _on_stream(dev) as stream:
+            ws, nbytes = _workspace(lib.sqfa_spd_function_workspace_bytes, n, m, code)
             F = torch.empty_like(S3)
             U = torch.empty((n, m, m), dtype=torch.float64, device=dev)
             lam = torch.empty((n, m), dtype=torch.float64, device=dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(lib.sqfa_spd_function(_ptr(S3), n, m, code, int(kind), _ptr(F), _ptr(U), _ptr(lam), _ptr(ws), nbytes, stream),
                        "sqfa_spd_function")
         ctx.save_for_backward(U, lam)
@@ -459,9 +471,8 @@ class SpdFunction(torch.autograd.Function):
         lib = _lib.load()
         G = gF.detach().contiguous()
         n, m = G.shape[0], G.shape[-1]
-        with torch.cuda.device(G.device):
+        with _on_stream(G.device) as stream:
             gS = torch.empty_like(G)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(G.device).cuda_stream)
             _lib.check(lib.sqfa_spd_function_backward(_ptr(U), _ptr(lam), _ptr(G), n, m, _dtype_code(G), ctx.kind, _ptr(gS), stream),
                        "sqfa_spd_function_backward")
         return gS, None
@@ -478,17 +489,13 @@ def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, w
     if m > SPD_FUNCTION_MAX_DIM:
         raise NotImplementedError(f"matrix size {m} exceeds the native per-class SPD functions' limit ({SPD_FUNCTION_MAX_DIM})")
     code = _dtype_code(S)
-    nbytes = lib.sqfa_log_euclidean_workspace_bytes(n, m, code)
-    if nbytes == 0:
-        raise _lib.NativeLibraryError("sqfa_log_euclidean_workspace_bytes rejected the problem shape")
     dev, dt = S.device, S.dtype
-    with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(lib.sqfa_log_euclidean_workspace_bytes, n, m, code)
         loss = torch.empty((), dtype=dt, device=dev)
         nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
         gS = torch.empty_like(S) if want_grad else None
         dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         status = lib.sqfa_log_euclidean_pairwise_loss(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps), float(weight),
                                                       _ptr(loss), _ptr(gS), _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes,
                                                       stream)
@@ -496,7 +503,7 @@ def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, w
     return {"loss": loss, "gS": gS, "dist": dist, "nonfinite": nonfinite}
 
 
-class LogEuclideanPairwiseLoss(torch.autograd.Function):
+class LogEuclideanPairwiseLoss(_SavedGradientLoss):
     """Fused closure loss of log_euclidean (sqrt_mode True) / log_euclidean_sq (False): weight * sum over the unordered
     class pairs, with its gradient wrt the (C,K,K) SPD matrices, from ONE pass over the pairs between the per-class
     logarithm and its Daleckii-Krein backward (sqfa_log_euclidean_pairwise_loss) -- in place of SpdFunction forward ->
@@ -505,14 +512,7 @@ class LogEuclideanPairwiseLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, S, sqrt_mode, eps, weight):
         out = hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight)
-        ctx.save_for_backward(out["gS"])
-        ctx.mark_non_differentiable(out["nonfinite"])
-        return out["loss"], out["nonfinite"]
-
-    @staticmethod
-    def backward(ctx, gloss, _gflag):
-        (gS,) = ctx.saved_tensors
-        return gS * gloss, None, None, None
+        return _SavedGradientLoss._saved(ctx, 4, out["loss"], out["nonfinite"], out["gS"])
 
 
 def spd_function(M, kind):
@@ -527,7 +527,7 @@ def spd_function(M, kind):
 
 
 _symmetry_check_warned = False
-_symmetry_checked = {}   # id(tensor) -> (weakref to the tensor, _version, verdict): dies with the tensor, never reused by another
+_symmetry_checked = TensorMemo()   # scatters -> verdict
 
 
 def _is_symmetric_batch(scatters):
@@ -538,10 +538,9 @@ def _is_symmetric_batch(scatters):
     read), outside any graph capture; asymmetry at rounding level (a GEMM-built X^T X) passes.  The verdict is
     keyed on the tensor OBJECT (weak reference), not on its address: the caching allocator hands a freed address
     to the next tensor.  Any failure of the check itself (e.g. out of memory) selects the general torch expression."""
-    import weakref
-    hit = _symmetry_checked.get(id(scatters))
-    if hit is not None and hit[0]() is scatters and hit[1] == scatters._version:
-        return hit[2]
+    hit = _symmetry_checked.get(scatters)
+    if hit is not None:
+        return hit
     if torch.cuda.is_current_stream_capturing():
         return False  # never seen outside a capture: take the general torch expression
     tol = 1e-5 if scatters.dtype == torch.float32 else 1e-12
@@ -564,13 +563,7 @@ def _is_symmetric_batch(scatters):
             import warnings
             warnings.warn(f"sqfa_amd: the symmetry check of the scatter matrices itself failed ({err!r}); this tensor keeps the "
                           "general torch projection (slower, same results)")
-    key = id(scatters)
-    try:
-        ref = weakref.ref(scatters, lambda _r, k=key: _symmetry_checked.pop(k, None))
-    except TypeError:
-        return ok
-    _symmetry_checked[key] = (ref, scatters._version, ok)
-    return ok
+    return _symmetry_checked.put(ok, scatters)
 
 
 def native_projection_supported(scatters, filters):
@@ -602,7 +595,7 @@ PACKED_PROJECTION = True
 PACKED_MIN_CLASSES = 512      # one workgroup per class, two resident per CU
 PACKED_MIN_DIM = 768
 PACKED_MAX_FILTERS = 16       # one 16-filter block: beyond it the packed kernel is MFMA-bound and loses to the full-tensor stream
-_packed_cache = {}            # id(scatters) -> (weakref, _version, packed tensor)
+_packed = TensorMemo()        # scatters -> packed copy
 
 
 def packed_supported(scatters):
@@ -619,9 +612,8 @@ def pack_scatters(scatters):
     n = lib.sqfa_packed_scatter_elems(D)
     if n == 0:
         raise ValueError(f"n_dim = {D} has no packed form (needs D % 16 == 0)")
-    with torch.cuda.device(scatters.device):
+    with _on_stream(scatters.device) as stream:
         out = torch.empty((C, n), dtype=scatters.dtype, device=scatters.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(scatters.device).cuda_stream)
         _lib.check(lib.sqfa_pack_scatters(_ptr(scatters), C, D, _dtype_code(scatters), _ptr(out), stream), "sqfa_pack_scatters")
     return out
 
@@ -629,7 +621,6 @@ def pack_scatters(scatters):
 def prepare_packed(scatters, n_filters):
     """Pack `scatters` once (outside any graph capture) if the packed projection applies to it and to this filter count;
     later projections of the same tensor object / version find the packed copy through packed_for."""
-    import weakref
     if (not torch.is_tensor(scatters) or n_filters > PACKED_MAX_FILTERS or not packed_supported(scatters)
             or torch.cuda.is_current_stream_capturing()):
         return None
@@ -638,22 +629,11 @@ def prepare_packed(scatters, n_filters):
         return hit
     if not _is_symmetric_batch(scatters):
         return None
-    packed = pack_scatters(scatters)
-    key = id(scatters)
-    try:
-        ref = weakref.ref(scatters, lambda _r, k=key: _packed_cache.pop(k, None))
-    except TypeError:
-        return None
-    _packed_cache[key] = (ref, scatters._version, packed)
-    return packed
+    return _packed.put(pack_scatters(scatters), scatters)
 
 
 def packed_for(scatters, n_filters=1):
-    hit = _packed_cache.get(id(scatters))
-    if (hit is not None and hit[0]() is scatters and hit[1] == scatters._version and PACKED_PROJECTION
-            and n_filters <= PACKED_MAX_FILTERS):
-        return hit[2]
-    return None
+    return _packed.get(scatters) if (PACKED_PROJECTION and n_filters <= PACKED_MAX_FILTERS) else None
 
 
 def _launch_projection(lib, F, Psi, T, K, D, C, code, stream):
@@ -705,10 +685,9 @@ class ProjectScatters(torch.autograd.Function):
         K, D = F.shape
         C = Psi.shape[0]
         code = _dtype_code(Psi)
-        with torch.cuda.device(Psi.device):
+        with _on_stream(Psi.device) as stream:
             T = torch.empty((C, D, K), dtype=Psi.dtype, device=Psi.device)
             S = torch.empty((C, K, K), dtype=Psi.dtype, device=Psi.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(Psi.device).cuda_stream)
             _launch_projection(lib, F, scatters if scatters.is_contiguous() else Psi, T, K, D, C, code, stream)
             if C >= ProjectScatters.NATIVE_PRODUCTS_MIN_CLASSES:
                 _lib.check(lib.sqfa_feature_scatters(_ptr(F), K, D, _ptr(T), C, code, _ptr(S), stream),
@@ -726,9 +705,8 @@ class ProjectScatters(torch.autograd.Function):
             lib = _lib.load()
             G = gS.contiguous()
             groups = backward_groups(C, D, ProjectScatters.BACKWARD_GROUPS)
-            with torch.cuda.device(T.device):
+            with _on_stream(T.device) as stream:
                 partial = torch.empty((groups, K, D), dtype=T.dtype, device=T.device)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(T.device).cuda_stream)
                 _lib.check(lib.sqfa_feature_scatters_backward(_ptr(G), _ptr(T), C, D, K, _dtype_code(T), groups,
                                                               _ptr(partial), stream), "sqfa_feature_scatters_backward")
             return partial.sum(dim=0), None
@@ -770,13 +748,9 @@ def _orthogonal_call(forward, X, base, gF=None):
     lib = _lib.load()
     K, D = X.shape
     code = _dtype_code(X)
-    nbytes = lib.sqfa_orthogonal_workspace_bytes(K, D, code)
-    if nbytes == 0:
-        raise _lib.NativeLibraryError("sqfa_orthogonal_workspace_bytes rejected the problem shape")
-    with torch.cuda.device(X.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    with _on_stream(X.device) as stream:
+        ws, nbytes = _workspace(lib.sqfa_orthogonal_workspace_bytes, K, D, code)
         out = torch.empty_like(X)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
         if forward:
             _lib.check(lib.sqfa_orthogonal_forward(_ptr(X), _ptr(base), K, D, code, _ptr(out), _ptr(ws), nbytes, stream),
                        "sqfa_orthogonal_forward")
@@ -807,19 +781,6 @@ class OrthogonalFilters(torch.autograd.Function):
 # the whole closure as one autograd node
 
 
-def fused_closure_supported(raw_filters, scatters, means):
-    """Conditions of the single-node closure: the streaming projection's (symmetric (C,D,D) scatters,
-    D % 4 == 0, K <= 64, 16-byte aligned), float32/float64 on the GPU; the means (SQFA) on the same
-    device/dtype."""
-    K = raw_filters.shape[0]
-    if not (raw_filters.is_cuda and raw_filters.dim() == 2 and raw_filters.is_contiguous()):
-        return False
-    if means is not None and not (means.is_cuda and means.dtype == scatters.dtype and means.dim() == 2
-                                  and not means.requires_grad):
-        return False
-    return native_projection_supported(scatters, raw_filters)
-
-
 def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
     """First half of a closure evaluation, no autograd: parametrization -> T = Psi F^T -> [m = mu F^T] -> S | E
     (feature scatters + noise, or their Calvo-Oller embedding), written into `out_S` when given (a slice of
@@ -832,8 +793,7 @@ def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
     C = Psi.shape[0]
     code = _dtype_code(Psi)
     dev, dt = Psi.device, Psi.dtype
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with _on_stream(dev) as stream:
         base = sphere.detach() if torch.is_tensor(sphere) else None
         sphere = base is None and bool(sphere)
         if base is not None:
@@ -862,20 +822,13 @@ def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None, metric="
     [loss, nan, inf, dL/dS...] in place (the all-reduce buffer of a sharded evaluation)."""
     extra = {"metric": metric} if metric != "airm" else {}
     if fused is not None:
-        extra.update({"out_loss": fused[0], "out_gradA": fused[3:].view(S.shape)})
+        extra.update(fused_outputs(fused, S.shape))
     out = _pair_backend(S, None, scale=scale, eps=EPSILON, sqrt_mode=sqrt_mode, weights=None,
                         uniform_weight=weight, shard=shard, want_loss=True, want_grad=True,
                         want_dist=False, want_eig=False, **extra)
     if fused is not None:
         fused[1:3].copy_(out["nonfinite"])   # int32 -> real in the copy itself
     return out["loss"], out["nonfinite"], out["gradA"]
-
-
-def closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, sphere, fused=None, metric="airm"):
-    """Both halves (closure_stage_project + closure_stage_pairs) for statistics that are not class-sharded."""
-    st = closure_stage_project(raw, scatters, means, noise, sphere)
-    st["loss"], st["nonfinite"], st["gS"] = closure_stage_pairs(st["S"], scale, sqrt_mode, weight, shard, fused, metric)
-    return st
 
 
 def closure_stage_backward(st, gS, gloss):
@@ -890,8 +843,7 @@ def closure_stage_backward(st, gS, gloss):
     groups = backward_groups(C, D, FusedClosure.BACKWARD_GROUPS)
     gS = gS.contiguous()
     ldg = gS.shape[-1]
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with _on_stream(dev) as stream:
         partial = torch.empty((groups, K, D), dtype=dt, device=dev)
         # gS is the pair kernels' dL/dS (or dL/dE): written symmetric by sqfa_airm_pairwise, sums of shards included
         _lib.check(lib.sqfa_feature_scatters_backward_ex(_ptr(gS), ldg, _ptr(T), C, D, K, code, groups, 1, _ptr(partial), stream),
@@ -928,19 +880,18 @@ class FusedClosure(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere, metric="airm"):
+        owner = fused_reduce_owner(reducer, shard)
         fused = None
-        owner = getattr(reducer, "__self__", None)
-        if reducer is not None and shard[1] > 1 and _pair_backend is hip_pair_backend and hasattr(owner, "reduce_fused"):
-            C, K = scatters.shape[0], raw.shape[0]
-            m = K + 1 if means is not None else K
-            fused = torch.empty(C * m * m + 3, dtype=scatters.dtype, device=scatters.device)
-        st = closure_stage_forward(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, sphere, fused, metric)
-        loss, nonfinite, gS = st["loss"], st["nonfinite"], st["gS"]
+        if owner is not None:
+            m = raw.shape[0] + (1 if means is not None else 0)
+            fused = fused_buffer((scatters.shape[0], m, m), scatters.dtype, scatters.device)
+        st = closure_stage_project(raw, scatters, means, noise, sphere)
+        loss, nonfinite, gS = closure_stage_pairs(st.pop("S"), scale, sqrt_mode, weight, shard, fused, metric)
         if fused is not None:
             loss, nonfinite, gS = owner.reduce_fused(fused, nonfinite, st["S_shape"])
         elif reducer is not None:
             loss, nonfinite, gS = reducer(loss, nonfinite, gS)
-        ctx.st = {k: v for k, v in st.items() if k not in ("loss", "nonfinite", "gS", "S")}
+        ctx.st = st
         ctx.gS = gS
         ctx.mark_non_differentiable(nonfinite)
         return loss, nonfinite

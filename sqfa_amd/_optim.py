@@ -98,6 +98,76 @@ def raise_on_flags(flags):
         raise ValueError(_INF_MSG)
 
 
+def read_head(packed):
+    """Loss of a packed [loss, nan, inf, ...] after ONE read-back of these three (none for a host tensor); raises on the flags."""
+    head = packed[:3].cpu()
+    raise_on_flags(head[1:3].round().to(torch.int32))
+    return head[0]
+
+
+class GraphRunner:
+    """A closure evaluation as a list of stage functions over static tensors: GRAPH_WARMUP_CLOSURES eager passes, then
+    ONE attempt to capture every stage in a HIP graph of its own (a failure warns once and the runner stays eager for
+    good), then replays.  The stages whose index is in `eager_stages` -- the collectives -- stay plain calls between the
+    replays.  The stages hand tensors on through `box`; a stage may read `state` ("warmup" | "capturing" | "on" | "eager")."""
+
+    def __init__(self, stages, box, eager_stages=(), armed=True, what="closure", capture_error_mode=None):
+        self.stages, self.box, self.eager_stages = stages, box, frozenset(eager_stages)
+        self.state, self.calls, self.graphs = ("warmup" if armed else "eager"), 0, None
+        self.what = what
+        self.graph_options = {"capture_error_mode": capture_error_mode} if capture_error_mode else {}
+
+    def _capture(self):
+        self.state = "capturing"
+        graphs, pool = [], None     # the graphs of one evaluation share a memory pool
+        for i, stage in enumerate(self.stages):
+            if i in self.eager_stages:
+                stage()
+                graphs.append(None)
+                continue
+            g = torch.cuda.CUDAGraph()
+            with _no_gc(), torch.cuda.graph(g, pool=pool, **self.graph_options):
+                stage()
+            pool = g.pool()
+            graphs.append(g)
+        self.graphs, self.state = graphs, "on"
+
+    def run(self, eager=False):
+        """Enqueue one evaluation (no host sync) and return the box.  eager=True runs the stages as plain launches even
+        after the capture (profiling passes: the library's HIP event records around its kernels happen at launch time,
+        which a graph replay does not repeat) and returns that pass's own copy of the box."""
+        if eager:
+            # The stage functions REBIND the box's entries to fresh tensors, while captured graphs keep writing into the
+            # tensors bound at capture time (and the eager stages between the graphs read the box).  An eager pass after
+            # the capture therefore works on its own bindings, which are dropped again afterwards: the next replay must
+            # find the capture-time tensors (ADVICE r3: it all-reduced and returned the stale eager ones).
+            saved = dict(self.box) if self.state == "on" else None
+            for stage in self.stages:
+                stage()
+            out = dict(self.box)
+            if saved is not None:
+                self.box.clear()
+                self.box.update(saved)
+            return out
+        if self.state == "warmup" and self.calls >= GRAPH_WARMUP_CLOSURES:
+            try:
+                self._capture()
+            except Exception as err:  # capture is an optimisation: report and continue eagerly
+                warnings.warn(f"sqfa_amd: HIP graph capture of the {self.what} failed ({err}); running eagerly")
+                self.state = "eager"
+        if self.state == "on":
+            for stage, g in zip(self.stages, self.graphs):
+                if g is None:
+                    stage()
+                else:
+                    g.replay()
+        else:
+            self.calls += 1
+            for stage in self.stages:
+                stage()
+        return self.box
+
+
 def _n_classes(data_statistics):
     if isinstance(data_statistics, dict):
         return data_statistics["means"].shape[0]
@@ -123,11 +193,10 @@ def _broadcast_replicated_state(model):
     all-reduced gradient).  Rank 0's parameters and buffers are therefore broadcast once per
     fitting_loop call: ranks that were initialised from different seeds (the default
     ``torch.randn`` filters) would otherwise mix inconsistent shards without any error."""
-    shard = getattr(model, "pair_shard", None) or getattr(model, "class_shard", None)
-    if shard is None or getattr(shard, "world_size", 1) <= 1:
+    group, sharded = _sharded_group(model)
+    if not sharded:
         return
     import torch.distributed as dist
-    group = getattr(shard, "group", None)
     src = dist.get_global_rank(group, 0) if group is not None else 0
     with torch.no_grad():
         for t in list(model.parameters()) + list(model.buffers()):
@@ -148,40 +217,45 @@ class ShardedClosure:
     Used by fitting_loop and, directly, by bench.py's N > 1 closure leg."""
 
     @staticmethod
+    def _plan(model, prepared):
+        """The model's closure plan when it is what the staged graphs evaluate: the single node on the affine-invariant
+        pair kernels (other pair metrics and evaluators stay eager)."""
+        plan = model._closure_plan(prepared, staged=True) if hasattr(model, "_closure_plan") else None
+        return plan if plan is not None and plan.evaluator == "single_node" and plan.metric == "airm" else None
+
+    @staticmethod
     def supported(model, prepared):
-        from . import distances
         params = list(model.parameters())
         return bool(GRAPH_CLOSURE and len(params) == 1 and params[0].is_cuda
                     and getattr(model, "pair_shard", None) is not None and model.pair_shard.world_size > 1
-                    and hasattr(model, "_has_fused_closure") and model._has_fused_closure()
-                    # the staged graphs evaluate the affine-invariant family only: other pair metrics stay eager
-                    and distances.fused_spec(model.distance_fun)[3] == "airm"
-                    and hasattr(model, "_single_node_inputs")
-                    and model._single_node_inputs(prepared, allow_class_shard=True) is not None
-                    and model._noise_scalar() is not None)
+                    and ShardedClosure._plan(model, prepared) is not None)
 
     def __init__(self, model, prepared):
-        self.state, self.calls, self.graphs = "warmup", 0, None
-        self.stages, self.box = self._build(model, prepared)
+        stages, box = self._build(model, prepared)
+        # thread_local: the process group's watchdog thread polls its events while this thread captures; under the
+        # default "global" mode such a call from ANOTHER thread invalidates the capture
+        self.runner = GraphRunner(stages, box, eager_stages=(1, 3, 5), what="sharded closure",
+                                  capture_error_mode="thread_local")
+
+    state = property(lambda self: self.runner.state)
+    graphs = property(lambda self: self.runner.graphs)
 
     @staticmethod
     def _build(model, prepared):
-        """Stage functions over static tensors, for eager warm-up and capture."""
-        from . import _native, distances
+        """Stage functions over static tensors, for eager warm-up and capture; the odd ones are the collectives."""
+        from . import _native
         import torch.distributed as dist
-        raw, scatters, means, sphere = model._single_node_inputs(prepared, allow_class_shard=True)
-        spec = distances.fused_spec(model.distance_fun)
-        scale, sqrt_mode = spec[1], spec[2]
-        noise = model._noise_scalar()
+        plan = ShardedClosure._plan(model, prepared)
+        raw, scatters, means, sphere, noise = plan.inputs
+        scale, sqrt_mode, weight = plan.scale, plan.sqrt_mode, plan.weight
         shard = model.pair_shard
         cshard = getattr(model, "class_shard", None)
         C_loc, K = scatters.shape[0], raw.shape[0]
         C = cshard.n_classes if cshard is not None else C_loc
         offset = cshard.offset if cshard is not None else 0
         m = K + 1 if means is not None else K
-        weight = -1.0 / (C * (C - 1) // 2)
         S_full = torch.empty((C, m, m), dtype=scatters.dtype, device=scatters.device)
-        fused = torch.empty(C * m * m + 3, dtype=scatters.dtype, device=scatters.device)
+        fused = _native.fused_buffer(S_full.shape, scatters.dtype, scatters.device)
         box = {}
         if cshard is not None:
             # every rank sends its slice padded to the largest shard (equal sizes: RCCL and gloo alike)
@@ -211,7 +285,7 @@ class ShardedClosure:
             dist.all_reduce(fused, op=dist.ReduceOp.SUM, group=shard.group)
 
         def stage_backward():
-            gS = fused[3:].view(C, m, m)[offset:offset + C_loc]
+            gS = _native.fused_outputs(fused, S_full.shape)["out_gradA"][offset:offset + C_loc]
             box["grad"] = _native.closure_stage_backward(box["st"], gS, None)
 
         def reduce_grad():
@@ -224,56 +298,13 @@ class ShardedClosure:
         return [stage_project, gather, stage_pairs, reduce, stage_backward, reduce_grad, stage_pack], box
 
     def _capture(self):
-        graphs = []
-        pool = None
-        for i, stage in enumerate(self.stages):
-            if i % 2 == 1:          # the collectives stay eager
-                stage()
-                graphs.append(None)
-                continue
-            g = torch.cuda.CUDAGraph()
-            # thread_local: the process group's watchdog thread polls its events while this thread captures; under
-            # the default "global" mode such a call from ANOTHER thread invalidates the capture
-            with _no_gc(), torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                stage()
-            pool = g.pool()
-            graphs.append(g)
-        self.graphs, self.state = graphs, "on"
+        self.runner._capture()
 
     def run(self, eager=False):
-        """Enqueue one evaluation; returns (packed [loss, nan, inf, grad...], grad) as device tensors, no host sync.
-        eager=True runs the stages as plain launches even after the capture (profiling passes: the library's HIP
-        event records around its kernels happen at launch time, which a graph replay does not repeat)."""
-        if eager:
-            # The stage functions REBIND box["st"] / box["grad"] / box["packed"] to fresh tensors, while captured graphs keep
-            # writing into the tensors bound at capture time (and the eager collectives between the graphs read the box).
-            # An eager pass after the capture therefore works on its own bindings, which are dropped again afterwards:
-            # the next replay must find the capture-time tensors (ADVICE r3: it all-reduced and returned the stale eager ones).
-            saved = dict(self.box) if self.state == "on" else None
-            for stage in self.stages:
-                stage()
-            out = self.box["packed"], self.box["grad"]
-            if saved is not None:
-                self.box.clear()
-                self.box.update(saved)
-            return out
-        if self.state == "warmup" and self.calls >= GRAPH_WARMUP_CLOSURES:
-            try:
-                self._capture()
-            except Exception as err:
-                warnings.warn(f"sqfa_amd: HIP graph capture of the sharded closure failed ({err}); running eagerly")
-                self.state = "eager"
-        if self.state == "on":
-            for stage, g in zip(self.stages, self.graphs):
-                if g is None:
-                    stage()
-                else:
-                    g.replay()
-        else:
-            self.calls += 1
-            for stage in self.stages:
-                stage()
-        return self.box["packed"], self.box["grad"]
+        """Enqueue one evaluation; returns (packed [loss, nan, inf, grad...], grad) as device tensors, no host sync
+        (eager: GraphRunner.run)."""
+        out = self.runner.run(eager)
+        return out["packed"], out["grad"]
 
 
 def fitting_loop(model, data_statistics, max_epochs=200, lr=0.1, atol=1e-6, show_progress=True,
@@ -334,85 +365,63 @@ def fitting_loop(model, data_statistics, max_epochs=200, lr=0.1, atol=1e-6, show
             model._sync_gradients()
         return loss.detach(), flags
 
-    def pack(loss, flags):
+    def pack(loss, flags, with_grads=True):
         """[loss, nan, inf, grad...] in one device tensor: a single copy brings it to the host."""
         dtype = loss.dtype
         head = [loss.reshape(1), flags.to(dtype) if flags is not None else loss.new_zeros(2)]
-        return torch.cat(head + [p.grad.reshape(-1).to(dtype) for p in device_params])
+        return torch.cat(head + [p.grad.reshape(-1).to(dtype) for p in device_params] if with_grads else head)
 
     def unpack_to_host(packed):
         host = packed.cpu()  # the only synchronisation of the closure
-        raise_on_flags(host[1:3].round().to(torch.int32))
+        loss = read_head(host)
         offset = 3
         for p, h in zip(device_params, opt_params):
             n = p.numel()
             h.grad = host[offset:offset + n].view_as(h).to(h.dtype)
             offset += n
-        return host[0]
+        return loss
+
+    def finish(packed, defer):
+        """The closure's value from a packed result: the loss on the host (host-side optimizer state: with the gradient, one
+        copy), or [loss, nan, inf] still on the device for CompactLBFGS' own read-back (defer)."""
+        if use_host:
+            return unpack_to_host(packed)
+        return packed[:3] if defer else read_head(packed)
 
     # ---- sharded fits: captured graphs around the collectives (ShardedClosure below) -------------------
     split = ShardedClosure(model, prepared) if (len(device_params) == 1 and ShardedClosure.supported(model, prepared)) else None
 
-    def split_closure(defer=False):
-        push_parameters()
-        packed, grad = split.run()
-        device_params[0].grad = grad
-        if use_host:
-            return unpack_to_host(packed)
-        if defer:
-            return packed[:3]
-        head = packed[:3].cpu()
-        raise_on_flags(head[1:3].round().to(torch.int32))
-        return head[0]
+    # ---- single-process fits: the whole closure is the one stage of a GraphRunner -------------------------
+    box = {}
 
-    graph = {"state": "off", "calls": 0, "graph": None, "packed": None, "grads": None}
-    if (GRAPH_CLOSURE and len(device_params) > 0 and all(p.is_cuda for p in device_params)
-            and getattr(model, "pair_shard", None) is None and getattr(model, "class_shard", None) is None
-            and hasattr(model, "_has_fused_closure") and model._has_fused_closure()):
-        graph["state"] = "warmup"
-
-    def capture():
+    def stage():
         for p in device_params:
             p.grad = None
-        g = torch.cuda.CUDAGraph()
-        with _no_gc(), torch.cuda.graph(g):
-            loss, flags = evaluate()
-            packed = pack(loss, flags)
-        graph.update(graph=g, packed=packed, grads=[p.grad for p in device_params], state="on")
+        box["loss"], box["flags"] = evaluate()
+        if runner.state == "capturing":   # the graph hands out [loss, nan, inf, grad...] and the gradient tensors it writes
+            box["packed"], box["grads"] = pack(box["loss"], box["flags"]), [p.grad for p in device_params]
+
+    runner = GraphRunner([stage], box, armed=bool(
+        GRAPH_CLOSURE and len(device_params) > 0 and all(p.is_cuda for p in device_params)
+        and getattr(model, "pair_shard", None) is None and getattr(model, "class_shard", None) is None
+        and hasattr(model, "_has_fused_closure") and model._has_fused_closure()))
 
     def closure(defer=False):
         """defer=True (device-side optimizer state only): enqueue everything and return [loss, nan, inf] as a
         DEVICE tensor without synchronising -- CompactLBFGS reads it back together with its own decision
         scalars and then calls closure.check_flags (one host synchronisation per LBFGS iteration)."""
-        if split is not None:
-            return split_closure(defer)
         push_parameters()
-        if graph["state"] == "warmup" and graph["calls"] >= GRAPH_WARMUP_CLOSURES:
-            try:
-                capture()
-            except Exception as err:  # capture is an optimisation: report and continue eagerly
-                warnings.warn(f"sqfa_amd: HIP graph capture of the closure failed ({err}); running eagerly")
-                graph["state"] = "off"
-        if graph["state"] == "on":
-            graph["graph"].replay()
-            packed = graph["packed"]
-            for p, grad in zip(device_params, graph["grads"]):
+        if split is not None:
+            packed, device_params[0].grad = split.run()
+            return finish(packed, defer)
+        runner.run()
+        if runner.state == "on":
+            for p, grad in zip(device_params, box["grads"]):
                 p.grad = grad  # the static gradient tensors the graph writes
-            if use_host:
-                return unpack_to_host(packed)
-            if defer:
-                return packed[:3]
-            head = packed[:3].cpu()  # loss and flags in one read-back; the gradient stays on the device
-            raise_on_flags(head[1:3].round().to(torch.int32))
-            return head[0]
-        graph["calls"] += 1
-        for p in device_params:
-            p.grad = None
-        loss, flags = evaluate()
-        if use_host:
-            return unpack_to_host(pack(loss, flags))
-        if defer:
-            return torch.cat([loss.reshape(1), flags.to(loss.dtype) if flags is not None else loss.new_zeros(2)])
+            return finish(box["packed"], defer)
+        loss, flags = box["loss"], box["flags"]
+        if use_host or defer:
+            return finish(pack(loss, flags, with_grads=use_host), defer)
         if flags is not None:
             raise_on_flags(flags)
         return loss

@@ -4,11 +4,14 @@
 F Sigma_c F^T, the parametrizations and LBFGS stay in PyTorch-ROCm; the pairwise distances
 and their backward run on the HIP kernels (distances.py, _native.py).
 """
+import collections
+
 import torch
 import torch.nn as nn
 from torch.nn.utils.parametrize import register_parametrization, remove_parametrizations
 
 from . import _native, distances
+from ._memo import TensorMemo
 from ._optim import fitting_loop
 from .constraints import FixedFilters, Identity, Orthogonal, Sphere, orthogonal
 from .linalg import conjugate_matrix
@@ -45,7 +48,7 @@ def _check_statistics(data_statistics, needs_dict=False):
         )
 
 
-_scatter_cache = {}   # (id(cov), id(mu)) -> (weakref cov, weakref mu, versions, second moments); entries die with their inputs
+_scatters = TensorMemo(max_entries=4)   # (cov, mu) -> second moments; a handful of live statistics at most (C*D*D values each)
 
 
 def _stats_to_scatter(statistics):
@@ -59,20 +62,16 @@ def _stats_to_scatter(statistics):
     mu, cov = statistics["means"], statistics["covariances"]
     if not (torch.is_tensor(mu) and torch.is_tensor(cov)) or mu.requires_grad or cov.requires_grad:
         return cov + mu[:, :, None] * mu[:, None, :]
-    import weakref
-    key = (id(cov), id(mu))
-    hit = _scatter_cache.get(key)
-    if hit is not None and hit[0]() is cov and hit[1]() is mu and hit[2] == (cov._version, mu._version):
-        return hit[3]
-    out = cov + mu[:, :, None] * mu[:, None, :]
-    drop = lambda _r, k=key: _scatter_cache.pop(k, None)
-    try:
-        _scatter_cache[key] = (weakref.ref(cov, drop), weakref.ref(mu, drop), (cov._version, mu._version), out)
-    except TypeError:
-        pass
-    while len(_scatter_cache) > 4:            # a handful of live statistics at most (each entry holds C*D*D values)
-        _scatter_cache.pop(next(iter(_scatter_cache)))
-    return out
+    hit = _scatters.get(cov, mu)
+    return hit if hit is not None else _scatters.put(cov + mu[:, :, None] * mu[:, None, :], cov, mu)
+
+
+# What one closure evaluation runs (SecondMomentsSQFA._closure_plan): the method _evaluate_<evaluator> and its static
+# arguments.  scale: the pair kernels' scale, or the SQFA_GAUSS_* kind code; metric: "airm" | "bw" | "gauss" | None;
+# weight: -1 / #pairs; shard, reducer: the pair tiles of a multi-GPU fit; inputs: the single node's (raw filters, scatters,
+# means, parametrization kind, noise).  weight and inputs are None in a plan made without statistics.
+ClosurePlan = collections.namedtuple("ClosurePlan", "evaluator scale sqrt_mode metric weight shard reducer inputs")
+_NATIVE_DTYPES = (torch.float32, torch.float64)
 
 
 class SecondMomentsSQFA(nn.Module):
@@ -146,21 +145,8 @@ class SecondMomentsSQFA(nn.Module):
     _fused_kind = "spd"
 
     def _has_fused_closure(self):
-        """True when distance_fun is the native operator this model's fused closure evaluates."""
-        spec = distances.fused_spec(self.distance_fun)
-        if spec is None:
-            # log_euclidean[_sq]: per-class stages around one pass over the class pairs, within the per-class SPD functions'
-            # limits; single-process fits only (a sharded fit keeps the generic closure, as _log_euclidean_closure_loss does)
-            cspec = distances.class_fused_spec(self.distance_fun)
-            nm = self.noise_mat
-            return (cspec is not None and cspec[0] == self._fused_kind and nm.dtype in (torch.float32, torch.float64)
-                    and nm.shape[0] <= _native.SPD_FUNCTION_MAX_DIM and self.pair_shard is None and self.class_shard is None)
-        if spec[0] != self._fused_kind:
-            return False
-        if spec[3] == "gauss":   # the Gaussian pair kernels' own limits: beyond them the generic closure, never captured
-            nm = self.noise_mat   # (K,K), the model's dtype (reading self.filters would run the parametrization)
-            return nm.shape[0] <= _native.GAUSS_MAX_DIM and nm.dtype in (torch.float32, torch.float64)
-        return True
+        """True when distance_fun is a native operator this model's fused closure evaluates."""
+        return self._closure_plan() is not None
 
     # the whole closure as ONE autograd node (8 / 11 launches instead of ~40): _native.FusedClosure
     SINGLE_NODE_CLOSURE = True
@@ -186,70 +172,97 @@ class SecondMomentsSQFA(nn.Module):
             scatters, means = prepared, None
         if not torch.is_tensor(scatters) or scatters.dim() != 3 or scatters.dtype != raw.dtype:
             return None
-        if not _native.fused_closure_supported(raw, scatters, means):
+        if not (raw.is_cuda and raw.dim() == 2 and raw.is_contiguous()):
             return None
-        return raw, scatters, means, kind
+        if means is not None and not (means.is_cuda and means.dtype == scatters.dtype and means.dim() == 2
+                                      and not means.requires_grad):
+            return None
+        # the streaming projection's conditions: symmetric float32/float64 scatters on the GPU, D % 4 == 0, K <= 64, 16-byte aligned
+        return (raw, scatters, means, kind) if _native.native_projection_supported(scatters, raw) else None
+
+    @staticmethod
+    def _pair_weight(C):
+        """-1 / #unordered class pairs: the kernels' sum over the pairs becomes the reference's -mean (src/sqfa/_optim.py:94)."""
+        return -1.0 / (C * (C - 1) // 2)
+
+    def _closure_plan(self, prepared=None, staged=False):
+        """The ClosurePlan of this model's fused closure, or None: the fitting loop's generic closure, never captured in a
+        graph.  THE place where an evaluator is chosen and where its limits are written.  Without `prepared` only the
+        conditions that need no statistics apply (what the fitting loop arms its graph capture on; the pair family then
+        names the chain); with it the plan is final: whatever it names, _fused_closure_loss evaluates.
+        `staged`: the caller places the collectives itself (_optim.ShardedClosure): class-sharded statistics may take the
+        single node."""
+        fn, nm = self.distance_fun, self.noise_mat   # noise_mat: (K,K), the model's dtype (reading self.filters would run the parametrization)
+        sharded = self.pair_shard is not None or self.class_shard is not None
+        spec = distances.fused_spec(fn)
+        cspec = distances.class_fused_spec(fn) if spec is None else None
+        plan = inputs = None
+        if spec is not None and spec[0] == self._fused_kind and spec[3] != "gauss":
+            # affine-invariant / Bures-Wasserstein pair kernels: any device (through _pair_backend), any sharding
+            shard, reducer = (self.pair_shard.shard, self.pair_shard.reduce) if self.pair_shard is not None else ((0, 1), None)
+            plan = ClosurePlan("chain", spec[1], spec[2], spec[3], None, shard, reducer, None)
+            if prepared is not None:
+                single = self._single_node_inputs(prepared, allow_class_shard=staged)
+                noise = self._noise_scalar() if single is not None else None   # a non-scalar noise_mat keeps the chain
+                if noise is not None:
+                    plan, inputs = plan._replace(evaluator="single_node"), single + (noise,)
+        elif spec is not None and spec[0] == self._fused_kind:
+            # bhattacharyya / hellinger / mahalanobis[_sq]: single process, <= GAUSS_MAX_DIM filters, a dict of float32/64 GPU statistics
+            if sharded or nm.shape[0] > _native.GAUSS_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
+                return None
+            if prepared is not None:
+                if not isinstance(prepared, dict):
+                    return None
+                mu, cov = prepared["means"], prepared["covariances"]
+                cov_dtype = torch.promote_types(cov.dtype, nm.dtype)   # of F cov F^T + noise_mat
+                if not (cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[0] >= 2 and cov_dtype in _NATIVE_DTYPES
+                        and mu.dtype == cov_dtype and mu.device == cov.device):
+                    return None
+            plan = ClosurePlan("gauss", spec[1], spec[2], "gauss", None, (0, 1), None, None)
+        elif cspec is not None and cspec[0] == self._fused_kind:
+            # log_euclidean[_sq]: single process, within the per-class SPD functions' limit, a (C,D,D) float32/64 GPU tensor
+            if sharded or nm.shape[0] > _native.SPD_FUNCTION_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
+                return None
+            if prepared is not None and not (
+                    torch.is_tensor(prepared) and prepared.dim() == 3 and prepared.is_cuda and prepared.shape[0] >= 2
+                    and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
+                return None
+            plan = ClosurePlan("log_euclidean", None, cspec[1], None, None, (0, 1), None, None)
+        if plan is None or prepared is None:
+            return plan
+        return plan._replace(weight=self._pair_weight(self._n_classes_total(prepared)), inputs=inputs)
 
     def _fused_closure_loss(self, prepared):
-        """(loss, flags) through one fused loss+gradient launch, or None when the model's
-        distance_fun is not a native affine-invariant operator."""
-        if not self._has_fused_closure():
-            return None
-        spec = distances.fused_spec(self.distance_fun)
-        if spec is None:
-            return self._log_euclidean_closure_loss(prepared)
-        scale, sqrt_mode, metric = spec[1], spec[2], spec[3]
-        if metric == "gauss":
-            return self._gauss_closure_loss(prepared, scale)
-        single = self._single_node_inputs(prepared)
-        if single is not None:
-            raw, scatters, means, sphere = single
-            C = scatters.shape[0]
-            weight = -1.0 / (C * (C - 1) // 2)
-            shard, reducer = (0, 1), None
-            if self.pair_shard is not None:
-                shard, reducer = self.pair_shard.shard, self.pair_shard.reduce
-            noise = self._noise_scalar()
-            if noise is None:
-                return self._fused_closure_loss_chain(prepared, scale, sqrt_mode, metric)
-            return _native.FusedClosure.apply(raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere,
-                                              metric)
-        return self._fused_closure_loss_chain(prepared, scale, sqrt_mode, metric)
+        """(loss, flags) through the fused loss+gradient evaluator of _closure_plan, or None when there is none (the
+        fitting loop's generic closure)."""
+        plan = self._closure_plan(prepared)
+        return None if plan is None else getattr(self, "_evaluate_" + plan.evaluator)(plan, prepared)
 
-    def _gauss_closure_loss(self, prepared, kind):
-        """(loss, flags) for bhattacharyya / hellinger / mahalanobis[_sq] as the chain parametrization -> projection ->
-        noise -> _native.GaussPairwiseLoss (one fused pass over the class pairs), or None -- the fitting loop's generic
-        closure -- where the native kernels do not apply: CPU or non-float32/64 statistics, more than
-        _native.GAUSS_MAX_DIM filters, sharded fits."""
-        if self.pair_shard is not None or self.class_shard is not None or not isinstance(prepared, dict):
-            return None
+    def _evaluate_single_node(self, plan, prepared):
+        """The whole closure as ONE autograd node (_native.FusedClosure)."""
+        raw, scatters, means, sphere, noise = plan.inputs
+        return _native.FusedClosure.apply(raw, scatters, means, noise, plan.scale, plan.sqrt_mode, plan.weight, plan.shard,
+                                          plan.reducer, sphere, plan.metric)
+
+    def _evaluate_chain(self, plan, prepared):
+        """The same loss as a chain of autograd nodes (parametrization -> projection -> noise -> [embedding] ->
+        PairwiseLoss): any parametrization or device, class-sharded statistics, a non-scalar noise_mat."""
+        S = self._fused_input(prepared)
+        if self.class_shard is not None:
+            S = self.class_shard.gather(S)
+        return _native.PairwiseLoss.apply(S, plan.scale, distances.EPSILON, plan.sqrt_mode, plan.weight, plan.shard,
+                                          plan.reducer, plan.metric)
+
+    def _evaluate_gauss(self, plan, prepared):
+        """parametrization -> projection -> noise -> _native.GaussPairwiseLoss (one fused pass over the class pairs)."""
         stats = self._feature_statistics(prepared, True)
-        mu, cov = stats["means"], stats["covariances"]
-        if not (cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[-1] <= _native.GAUSS_MAX_DIM
-                and cov.shape[0] >= 2 and cov.dtype in (torch.float32, torch.float64) and mu.dtype == cov.dtype
-                and mu.device == cov.device):
-            return None
-        C = cov.shape[0]
-        weight = -1.0 / (C * (C - 1) // 2)
-        return _native.GaussPairwiseLoss.apply(mu, cov, int(kind), distances.EPSILON, weight)
+        return _native.GaussPairwiseLoss.apply(stats["means"], stats["covariances"], int(plan.scale), distances.EPSILON,
+                                               plan.weight)
 
-    def _log_euclidean_closure_loss(self, prepared):
-        """(loss, flags) for log_euclidean / log_euclidean_sq as the chain parametrization -> projection -> noise ->
-        _native.LogEuclideanPairwiseLoss (any parametrization; the native projection where it applies), or None -- the fitting
-        loop's generic closure -- where the native call does not apply: sharded fits, statistics that are not a (C,D,D)
-        tensor, CPU or non-float32/64 tensors, fewer than two classes, more than _native.SPD_FUNCTION_MAX_DIM filters."""
-        cspec = distances.class_fused_spec(self.distance_fun)
-        if cspec is None or self.pair_shard is not None or self.class_shard is not None:
-            return None
-        if not torch.is_tensor(prepared) or prepared.dim() != 3 or not prepared.is_cuda:
-            return None
-        S = self._feature_scatters(prepared, True)
-        if not (S.is_cuda and S.dim() == 3 and S.dtype in (torch.float32, torch.float64) and S.shape[0] >= 2
-                and S.shape[-1] <= _native.SPD_FUNCTION_MAX_DIM):
-            return None
-        C = S.shape[0]
-        weight = -1.0 / (C * (C - 1) // 2)
-        return _native.LogEuclideanPairwiseLoss.apply(S, cspec[1], distances.EPSILON, weight)
+    def _evaluate_log_euclidean(self, plan, prepared):
+        """parametrization -> projection (native where it applies) -> noise -> _native.LogEuclideanPairwiseLoss."""
+        return _native.LogEuclideanPairwiseLoss.apply(self._feature_scatters(prepared, True), plan.sqrt_mode,
+                                                      distances.EPSILON, plan.weight)
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once
@@ -266,19 +279,6 @@ class SecondMomentsSQFA(nn.Module):
             value = None
         self._noise_cache = (key, value)
         return value
-
-    def _fused_closure_loss_chain(self, prepared, scale, sqrt_mode, metric="airm"):
-        """The same loss as a chain of autograd nodes (parametrization -> projection -> noise ->
-        [embedding] -> PairwiseLoss): any parametrization, class-sharded statistics, odd filter counts."""
-        S = self._fused_input(prepared)
-        if self.class_shard is not None:
-            S = self.class_shard.gather(S)
-        C = S.shape[0]
-        weight = -1.0 / (C * (C - 1) // 2)
-        shard, reducer = (0, 1), None
-        if self.pair_shard is not None:
-            shard, reducer = self.pair_shard.shard, self.pair_shard.reduce
-        return _native.PairwiseLoss.apply(S, scale, distances.EPSILON, sqrt_mode, weight, shard, reducer, metric)
 
     def _sync_gradients(self):
         """Called by the fitting loop after backward: sums the filter gradient over class shards."""

@@ -354,7 +354,7 @@ def test_sharded_closure_eager_pass_does_not_disturb_the_captured_graphs():
     the captured graphs write (it returned and all-reduced the stale eager tensors afterwards).  The stage /
     graph mechanics with stand-ins for the HIP graphs: a 'graph' re-runs its stage's arithmetic INTO the tensors that were
     bound when it was captured, exactly what a replay does."""
-    from sqfa_amd._optim import ShardedClosure
+    from sqfa_amd._optim import GraphRunner, ShardedClosure
     sc = ShardedClosure.__new__(ShardedClosure)
     x = torch.zeros(3)
     box = {}
@@ -386,12 +386,13 @@ def test_sharded_closure_eager_pass_does_not_disturb_the_captured_graphs():
             box.clear()
             box.update(saved)
 
-    sc.stages, sc.box, sc.calls = [compute, collective, pack], box, 99
+    sc.runner = GraphRunner([compute, collective, pack], box, eager_stages=(1,))
+    sc.runner.calls = 99
     x.fill_(1.0)
     graphs = [FakeGraph(compute, [], ["grad"]), None]
     collective()
     graphs.append(FakeGraph(pack, ["grad"], ["packed"]))
-    sc.graphs, sc.state = graphs, "on"
+    sc.runner.graphs, sc.runner.state = graphs, "on"
     packed, grad = sc.run()
     assert packed.tolist() == [3.0] * 3
     x.fill_(5.0)

@@ -347,6 +347,20 @@ int sqfa_gauss_pairwise_loss(const void *mu, const void *cov, int n, int m, int 
                              double eps, double uniform_weight,
                              void *loss_out, void *gmu_out, void *gcov_out, void *dist_out, int *nonfinite_out,
                              void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The same with per-pair weights:  loss = sum_{i>j} w_ij D_ij,  w_ij = pair_weights[i*n + j].
+ *   pair_weights (n,n) dtype, row-major, or NULL.  NULL: this IS sqfa_gauss_pairwise_loss (same kernels, same bits);
+ *   otherwise uniform_weight is ignored.  The matrix MUST BE SYMMETRIC: the kernels visit the ordered pairs -- class row i
+ *   owns its gradient and weighs the pair (i, j) with w_ij, class row j weighs it with w_ji, and the loss counts j < i
+ *   with w_ij -- so both entries are read and an asymmetric matrix gives a gradient that belongs to no loss.  The diagonal
+ *   is never read into a result.  Every pair is evaluated and counted in nonfinite_out whatever its weight; dist_out is
+ *   unweighted.  (For the closure's -sum W D / sum W the caller passes -W / sum_{i>j} W.)
+ * Workspace, limits, error codes and reproducibility as above.
+ */
+int sqfa_gauss_pairwise_loss_weighted(const void *mu, const void *cov, int n, int m, int dtype, int kind,
+                                      double eps, const void *pair_weights, double uniform_weight,
+                                      void *loss_out, void *gmu_out, void *gcov_out, void *dist_out, int *nonfinite_out,
+                                      void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Fused closure loss of the log-Euclidean distances (log_euclidean[_sq] of the reference, src/sqfa/distances.py:92-138, as
@@ -374,6 +388,19 @@ int sqfa_log_euclidean_pairwise_loss(const void *S, int n, int m, int dtype, int
                                      double eps, double uniform_weight,
                                      void *loss_out, void *gradS_out, void *dist_out, int *nonfinite_out,
                                      void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The same with per-pair weights:  loss = sum_{i>j} w_ij D_ij,  G_i = sum_{j != i} c_ij (L_i - L_j) with
+ * c_ij = 2 w_ij | w_ij / D_ij,  w_ij = pair_weights[i*n + j].
+ *   pair_weights (n,n) dtype, row-major, or NULL.  NULL: this IS sqfa_log_euclidean_pairwise_loss (same kernels, same
+ *   bits); otherwise uniform_weight is ignored.  The matrix MUST BE SYMMETRIC (the pass visits the ordered pairs: row i
+ *   reads w_ij, row j reads w_ji, the loss counts j < i with w_ij).  The diagonal is never read into a result.  Every pair
+ *   is evaluated and counted in nonfinite_out whatever its weight; dist_out is unweighted.
+ * Workspace, limits, error codes and the order of the argument checks as above.
+ */
+int sqfa_log_euclidean_pairwise_loss_weighted(const void *S, int n, int m, int dtype, int sqrt_mode,
+                                              double eps, const void *pair_weights, double uniform_weight,
+                                              void *loss_out, void *gradS_out, void *dist_out, int *nonfinite_out,
+                                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the

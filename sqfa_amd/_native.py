@@ -161,6 +161,36 @@ def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, sh
 _pair_backend = hip_pair_backend
 
 
+def normalized_pair_weights(pair_weights, n_classes, dtype, device):
+    """The closures' static weight tensor of one fit: validates a (C,C) tensor-like of per-pair class weights on the host
+    (ValueError naming the condition) and returns  Wn = -W / sum_{i>j} W_ij  with a zero diagonal, in `dtype` on `device`,
+    so that  sum_{i>j} Wn_ij D_ij  is the loss  -sum_{i>j} W_ij D_ij / sum_{i>j} W_ij.  None stays None."""
+    if pair_weights is None:
+        return None
+    W = torch.as_tensor(pair_weights).detach().to(device="cpu", dtype=torch.float64)
+    C = int(n_classes)
+    if tuple(W.shape) != (C, C):
+        raise ValueError(f"pair_weights must have shape (n_classes, n_classes) = ({C}, {C}), got {tuple(W.shape)}")
+    if not bool(torch.isfinite(W).all()):
+        raise ValueError("pair_weights must be finite (found NaN or inf)")
+    if bool((W < 0).any()):
+        raise ValueError("pair_weights must be non-negative")
+    if not bool(torch.equal(W, W.t())):
+        raise ValueError("pair_weights must be symmetric")
+    total = torch.tril(W, -1).sum()
+    if not float(total) > 0.0:
+        raise ValueError("pair_weights must have a positive sum over the pairs i > j")
+    Wn = -W / total
+    Wn.fill_diagonal_(0.0)
+    return Wn.to(device=device, dtype=dtype).contiguous()
+
+
+def _self_pair_weights(pair_weights):
+    """What the affine-invariant / Bures-Wasserstein kernels take for the closure's symmetric weights: in self mode they
+    weigh the unordered pair with w_ij + w_ji, so they get the strict lower triangle."""
+    return None if pair_weights is None else torch.tril(pair_weights, -1)
+
+
 # ------------------------------------------------------------------------------------------
 # autograd wrappers
 
@@ -232,16 +262,17 @@ class _SavedGradientLoss(torch.autograd.Function):
 class PairwiseLoss(_SavedGradientLoss):
     """Fused closure loss: sum over the unordered pairs i>j of  weight * dist(S_i, S_j)
     (weight = -1/P gives the reference's -mean, src/sqfa/_optim.py:94) together with its
-    gradient, in one pass.  `reducer(loss, nonfinite, grad)` combines shards (all-reduce)."""
+    gradient, in one pass.  `reducer(loss, nonfinite, grad)` combines shards (all-reduce).  `pair_weights`: the symmetric
+    (C,C) per-pair weights of normalized_pair_weights in place of `weight`."""
 
     @staticmethod
-    def forward(ctx, S, scale, eps, sqrt_mode, weight, shard, reducer, metric="airm"):
+    def forward(ctx, S, scale, eps, sqrt_mode, weight, shard, reducer, metric="airm", pair_weights=None):
         extra = {"metric": metric} if metric != "airm" else {}
         owner = fused_reduce_owner(reducer, shard)
         fused = fused_buffer(S.shape, S.dtype, S.device) if owner is not None else None
         if fused is not None:
             extra.update(fused_outputs(fused, S.shape))
-        out = _pair_backend(S, None, scale=scale, eps=eps, sqrt_mode=sqrt_mode, weights=None,
+        out = _pair_backend(S, None, scale=scale, eps=eps, sqrt_mode=sqrt_mode, weights=_self_pair_weights(pair_weights),
                             uniform_weight=weight, shard=shard, want_loss=True, want_grad=True,
                             want_dist=False, want_eig=False, **extra)
         loss, nonfinite, grad = out["loss"], out["nonfinite"], out["gradA"]
@@ -249,7 +280,7 @@ class PairwiseLoss(_SavedGradientLoss):
             loss, nonfinite, grad = owner.reduce_fused(fused, nonfinite, S.shape)
         elif reducer is not None:
             loss, nonfinite, grad = reducer(loss, nonfinite, grad)
-        return _SavedGradientLoss._saved(ctx, 8, loss, nonfinite, grad)
+        return _SavedGradientLoss._saved(ctx, 9, loss, nonfinite, grad)
 
 
 def hip_eigenvalues_backward(A, B, eig_weights):
@@ -383,9 +414,21 @@ class GaussPairTerms(torch.autograd.Function):
         return gmuA, gcovA, gmuB, gcovB, None
 
 
-def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dist=False):
-    """sqfa_gauss_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe inside
-    a graph capture).  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested)."""
+def _pair_weight_matrix(pair_weights, n, dtype, device):
+    """(n,n) per-pair weights as the fused entries read them: contiguous, the statistics' dtype and device."""
+    if pair_weights is None:
+        return None
+    W = pair_weights.detach().to(dtype=dtype, device=device).contiguous()
+    if tuple(W.shape) != (n, n):
+        raise ValueError(f"pair weights must have shape ({n}, {n}), got {tuple(W.shape)}")
+    return W
+
+
+def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_gauss_pairwise_loss[_weighted] on the current stream (no host read-back, workspace from the torch allocator:
+    safe inside a graph capture).  `pair_weights`: symmetric (n,n) per-pair weights in place of `weight` (never padded: the
+    identity padding below changes K, not the classes).  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not
+    requested)."""
     lib = _lib.load()
     if not cov.is_cuda:
         raise RuntimeError("sqfa_amd's fused Gaussian pair loss runs on the GPU only (no CPU fallback)")
@@ -407,9 +450,15 @@ def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dis
         gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad else None
         gcov = torch.empty((n, m, m), dtype=dt, device=dev) if want_grad else None
         dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        status = lib.sqfa_gauss_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), float(weight),
-                                              _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist), _ptr(nonfinite),
-                                              _ptr(ws), nbytes, stream)
+        if pair_weights is None:
+            status = lib.sqfa_gauss_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), float(weight),
+                                                  _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist), _ptr(nonfinite),
+                                                  _ptr(ws), nbytes, stream)
+        else:
+            W = _pair_weight_matrix(pair_weights, n, dt, dev)
+            status = lib.sqfa_gauss_pairwise_loss_weighted(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), _ptr(W),
+                                                           0.0, _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist),
+                                                           _ptr(nonfinite), _ptr(ws), nbytes, stream)
     _lib.check(status, "sqfa_gauss_pairwise_loss")
     if m != m_true and want_grad:
         gmu, gcov = gmu[:, :m_true].contiguous(), gcov[:, :m_true, :m_true].contiguous()
@@ -423,9 +472,9 @@ class GaussPairwiseLoss(_SavedGradientLoss):
     element-wise chain + its backward + GaussPairTerms backward.  Returns (loss, flags {#NaN, #inf})."""
 
     @staticmethod
-    def forward(ctx, means, covariances, kind, eps, weight):
-        out = hip_gauss_pairwise_loss(means, covariances, kind, eps, weight)
-        return _SavedGradientLoss._saved(ctx, 5, out["loss"], out["nonfinite"], out["gmu"], out["gcov"])
+    def forward(ctx, means, covariances, kind, eps, weight, pair_weights=None):
+        out = hip_gauss_pairwise_loss(means, covariances, kind, eps, weight, pair_weights=pair_weights)
+        return _SavedGradientLoss._saved(ctx, 6, out["loss"], out["nonfinite"], out["gmu"], out["gcov"])
 
 
 # ------------------------------------------------------------------------------------------
@@ -478,9 +527,10 @@ class SpdFunction(torch.autograd.Function):
         return gS, None
 
 
-def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, want_dist=False):
-    """sqfa_log_euclidean_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe
-    inside a graph capture).  S (n,m,m) SPD.  Returns dict(loss, gS, dist, nonfinite) (None where not requested)."""
+def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_log_euclidean_pairwise_loss[_weighted] on the current stream (no host read-back, workspace from the torch
+    allocator: safe inside a graph capture).  S (n,m,m) SPD; `pair_weights`: symmetric (n,n) per-pair weights in place of
+    `weight`.  Returns dict(loss, gS, dist, nonfinite) (None where not requested)."""
     lib = _lib.load()
     if not S.is_cuda:
         raise RuntimeError("sqfa_amd's fused log-Euclidean pair loss runs on the GPU only (no CPU fallback)")
@@ -496,9 +546,15 @@ def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, w
         nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
         gS = torch.empty_like(S) if want_grad else None
         dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        status = lib.sqfa_log_euclidean_pairwise_loss(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps), float(weight),
-                                                      _ptr(loss), _ptr(gS), _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes,
-                                                      stream)
+        if pair_weights is None:
+            status = lib.sqfa_log_euclidean_pairwise_loss(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps), float(weight),
+                                                          _ptr(loss), _ptr(gS), _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes,
+                                                          stream)
+        else:
+            W = _pair_weight_matrix(pair_weights, n, dt, dev)
+            status = lib.sqfa_log_euclidean_pairwise_loss_weighted(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps),
+                                                                   _ptr(W), 0.0, _ptr(loss), _ptr(gS), _ptr(dist),
+                                                                   _ptr(nonfinite), _ptr(ws), nbytes, stream)
     _lib.check(status, "sqfa_log_euclidean_pairwise_loss")
     return {"loss": loss, "gS": gS, "dist": dist, "nonfinite": nonfinite}
 
@@ -510,9 +566,9 @@ class LogEuclideanPairwiseLoss(_SavedGradientLoss):
     cdist -> square / sqrt -> tril gather -> mean and their autograd backward.  Returns (loss, flags {#NaN, #inf})."""
 
     @staticmethod
-    def forward(ctx, S, sqrt_mode, eps, weight):
-        out = hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight)
-        return _SavedGradientLoss._saved(ctx, 4, out["loss"], out["nonfinite"], out["gS"])
+    def forward(ctx, S, sqrt_mode, eps, weight, pair_weights=None):
+        out = hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, pair_weights=pair_weights)
+        return _SavedGradientLoss._saved(ctx, 5, out["loss"], out["nonfinite"], out["gS"])
 
 
 def spd_function(M, kind):
@@ -817,13 +873,14 @@ def closure_stage_project(raw, scatters, means, noise, sphere, out_S=None):
             "S": S, "S_shape": tuple(S.shape), "sphere": sphere, "base": base}
 
 
-def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None, metric="airm"):
+def closure_stage_pairs(S, scale, sqrt_mode, weight, shard, fused=None, metric="airm", pair_weights=None):
     """Second half: K0 / K1 / K2 on the (C,m,m) batch.  `fused` (S.numel() + 3 elements), when given, receives
-    [loss, nan, inf, dL/dS...] in place (the all-reduce buffer of a sharded evaluation)."""
+    [loss, nan, inf, dL/dS...] in place (the all-reduce buffer of a sharded evaluation).  `pair_weights`: the symmetric
+    (C,C) per-pair weights of normalized_pair_weights in place of `weight`."""
     extra = {"metric": metric} if metric != "airm" else {}
     if fused is not None:
         extra.update(fused_outputs(fused, S.shape))
-    out = _pair_backend(S, None, scale=scale, eps=EPSILON, sqrt_mode=sqrt_mode, weights=None,
+    out = _pair_backend(S, None, scale=scale, eps=EPSILON, sqrt_mode=sqrt_mode, weights=_self_pair_weights(pair_weights),
                         uniform_weight=weight, shard=shard, want_loss=True, want_grad=True,
                         want_dist=False, want_eig=False, **extra)
     if fused is not None:
@@ -879,14 +936,15 @@ class FusedClosure(torch.autograd.Function):
     BACKWARD_GROUPS = 64
 
     @staticmethod
-    def forward(ctx, raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere, metric="airm"):
+    def forward(ctx, raw, scatters, means, noise, scale, sqrt_mode, weight, shard, reducer, sphere, metric="airm",
+                pair_weights=None):
         owner = fused_reduce_owner(reducer, shard)
         fused = None
         if owner is not None:
             m = raw.shape[0] + (1 if means is not None else 0)
             fused = fused_buffer((scatters.shape[0], m, m), scatters.dtype, scatters.device)
         st = closure_stage_project(raw, scatters, means, noise, sphere)
-        loss, nonfinite, gS = closure_stage_pairs(st.pop("S"), scale, sqrt_mode, weight, shard, fused, metric)
+        loss, nonfinite, gS = closure_stage_pairs(st.pop("S"), scale, sqrt_mode, weight, shard, fused, metric, pair_weights)
         if fused is not None:
             loss, nonfinite, gS = owner.reduce_fused(fused, nonfinite, st["S_shape"])
         elif reducer is not None:
@@ -899,4 +957,4 @@ class FusedClosure(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gflag):
         grad = closure_stage_backward(ctx.st, ctx.gS, gloss)
-        return grad, None, None, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None, None, None

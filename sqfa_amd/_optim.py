@@ -187,19 +187,20 @@ def _sharded_group(model):
     return getattr(shard, "group", None), True
 
 
-def _broadcast_replicated_state(model):
+def _broadcast_replicated_state(model, tensors=None):
     """Multi-GPU fits assume bit-identical filters on every rank (each rank evaluates its tile
     shard of the SAME feature scatters, and every rank repeats the same LBFGS update on the
     all-reduced gradient).  Rank 0's parameters and buffers are therefore broadcast once per
     fitting_loop call: ranks that were initialised from different seeds (the default
-    ``torch.randn`` filters) would otherwise mix inconsistent shards without any error."""
+    ``torch.randn`` filters) would otherwise mix inconsistent shards without any error.  `tensors`: broadcast
+    these instead (further replicated state of the fit: its normalised pair weights)."""
     group, sharded = _sharded_group(model)
     if not sharded:
         return
     import torch.distributed as dist
     src = dist.get_global_rank(group, 0) if group is not None else 0
     with torch.no_grad():
-        for t in list(model.parameters()) + list(model.buffers()):
+        for t in (list(model.parameters()) + list(model.buffers()) if tensors is None else tensors):
             dist.broadcast(t.data, src=src, group=group)
 
 
@@ -247,7 +248,7 @@ class ShardedClosure:
         import torch.distributed as dist
         plan = ShardedClosure._plan(model, prepared)
         raw, scatters, means, sphere, noise = plan.inputs
-        scale, sqrt_mode, weight = plan.scale, plan.sqrt_mode, plan.weight
+        scale, sqrt_mode, weight, pair_weights = plan.scale, plan.sqrt_mode, plan.weight, plan.pair_weights
         shard = model.pair_shard
         cshard = getattr(model, "class_shard", None)
         C_loc, K = scatters.shape[0], raw.shape[0]
@@ -279,7 +280,7 @@ class ShardedClosure:
                 for r, n in enumerate(cshard.counts):
                     S_full[start:start + n].copy_(recv[r, :n])
                     start += n
-            _native.closure_stage_pairs(S_full, scale, sqrt_mode, weight, shard.shard, fused)
+            _native.closure_stage_pairs(S_full, scale, sqrt_mode, weight, shard.shard, fused, pair_weights=pair_weights)
 
         def reduce():
             dist.all_reduce(fused, op=dist.ReduceOp.SUM, group=shard.group)
@@ -308,10 +309,21 @@ class ShardedClosure:
 
 
 def fitting_loop(model, data_statistics, max_epochs=200, lr=0.1, atol=1e-6, show_progress=True,
-                 return_loss=False, **kwargs):
+                 return_loss=False, pair_weights=None, **kwargs):
     """Learn the filters with LBFGS.  Same arguments, stopping rule (|dloss| < atol for three
     consecutive epochs), messages and return value as the reference's fitting_loop
-    (src/sqfa/_optim.py:33-145); extra keyword arguments go to torch.optim.LBFGS."""
+    (src/sqfa/_optim.py:33-145); extra keyword arguments go to torch.optim.LBFGS.
+    `pair_weights`: optional symmetric non-negative (C,C) weights W of the class pairs (C: all classes, also for
+    class-sharded statistics); every closure then evaluates -sum_{i>j} W_ij D_ij / sum_{i>j} W_ij.  Validated once, here
+    (_native.normalized_pair_weights), and kept as a static device tensor for the whole call."""
+    saved_pair_weights = getattr(model, "_pair_weights", None)
+    try:
+        return _fitting_loop(model, data_statistics, max_epochs, lr, atol, show_progress, return_loss, pair_weights, kwargs)
+    finally:
+        model._pair_weights = saved_pair_weights
+
+
+def _fitting_loop(model, data_statistics, max_epochs, lr, atol, show_progress, return_loss, pair_weights, kwargs):
     _broadcast_replicated_state(model)
     device_params = list(model.parameters())
     # the compact form is four (history x n) matrix-vector products per iteration: on the host
@@ -347,6 +359,14 @@ def fitting_loop(model, data_statistics, max_epochs=200, lr=0.1, atol=1e-6, show
     if n_classes < 2:
         raise ValueError("At least two classes are needed to fit the filters.")
     rows, cols = torch.tril_indices(n_classes, n_classes, offset=-1)
+    # the fit's pair weights: checked on the host once, before any capture; the model hands them to its closure plan
+    Wn = None
+    if pair_weights is not None:
+        from . import _native
+        ref = device_params[0] if device_params else torch.zeros(())
+        Wn = _native.normalized_pair_weights(pair_weights, n_classes, ref.dtype, ref.device)
+        _broadcast_replicated_state(model, tensors=[Wn])
+    model._pair_weights = Wn
 
     def evaluate():
         """Enqueue loss and gradient on the device: (loss, flags or None); no host sync."""
@@ -358,7 +378,11 @@ def fitting_loop(model, data_statistics, max_epochs=200, lr=0.1, atol=1e-6, show
                 raise NotImplementedError("class-sharded statistics need one of the native distance operators")
             distances = model.get_class_distances(prepared, regularized=True)
             check_distances_valid(distances)
-            loss = -distances[rows.to(distances.device), cols.to(distances.device)].mean()
+            r, c = rows.to(distances.device), cols.to(distances.device)
+            if Wn is None:
+                loss = -distances[r, c].mean()
+            else:
+                loss = (Wn.to(device=distances.device, dtype=distances.dtype)[r, c] * distances[r, c]).sum()
             flags = None
         loss.backward()
         if hasattr(model, "_sync_gradients"):

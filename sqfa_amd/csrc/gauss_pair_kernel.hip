@@ -25,6 +25,10 @@
 // of the per-class log-determinants, -(1/4) (sum_j w dD/dBh_ij) Sigma_i^-1, uses the j == i step of the walk (Sbar_ii is
 // Sigma_i exactly), which parks Sigma_i^-1 in the workspace until the row's sum is known.  MODE = GAUSS_PRE is the
 // per-class pre-pass: the same Cholesky arithmetic on the pairs (c, c), writing logdet Sigma_c only.
+// MODE = GAUSS_FUSED_W (sqfa_gauss_pairwise_loss_weighted with a weight matrix): w becomes w_ij = W[i n + j], read by the
+// row's owner for every ordered pair -- W must be symmetric, since class j weighs the same pair with W[j n + i].  The
+// register kernel reads a coalesced row segment per round (lane = class j), issued behind the factorisation and covered
+// by the forward substitution; the LDS kernel reads one broadcast value per pair.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
@@ -67,9 +71,12 @@ struct GaussParams {
   void *dist;                // (n,n) or nullptr
   double *loss_part;         // (n) per-class partial losses
   int *cnt_part;             // (n,2) per-class {#NaN, #inf}
+  const void *W;             // (n,n) symmetric per-pair weights (MODE = GAUSS_FUSED_W only; `weight` is then unused)
 };
 
-enum { GAUSS_PLAIN = 0, GAUSS_FUSED = 1, GAUSS_PRE = 2 };
+// GAUSS_FUSED_W: the fused mode with w_ij = W[i n + j] in place of the scalar weight -- an instantiation of its own, so
+// that the uniform fused kernels stay the code they were
+enum { GAUSS_PLAIN = 0, GAUSS_FUSED = 1, GAUSS_PRE = 2, GAUSS_FUSED_W = 3 };
 
 template <typename T> __device__ __forceinline__ T fused_weight(const GaussParams& p);
 template <> __device__ __forceinline__ float fused_weight<float>(const GaussParams& p) { return p.weightf; }
@@ -106,7 +113,7 @@ __device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi
 
 template <typename T, int G, int MODE = GAUSS_PLAIN>
 __global__ void gauss_pair_kernel(const GaussParams p) {
-  constexpr bool FUSED = MODE == GAUSS_FUSED, PRE = MODE == GAUSS_PRE;
+  constexpr bool WEIGHTED = MODE == GAUSS_FUSED_W, FUSED = MODE == GAUSS_FUSED || WEIGHTED, PRE = MODE == GAUSS_PRE;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   constexpr int LD_ = G + 1;                 // row pitch
@@ -134,7 +141,7 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
   // Sbar^-1 is needed where logdet Sbar has a gradient
   const bool with_inv = FUSED ? p.kind <= SQFA_GAUSS_HELLINGER : gLD != nullptr;
   const T* ldc = static_cast<const T*>(p.ldc);
-  const T fw = fused_weight<T>(p), feps = fused_eps<T>(p);
+  const T fw0 = fused_weight<T>(p), feps = fused_eps<T>(p);
   T loss_acc = T(0), csum = T(0);   // fused: lane 0 of the group keeps the group's partial sums
   int n_nan = 0, n_inf = 0;
 
@@ -148,6 +155,8 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
   // pre-pass: the single "pair" (i, i), on group 0
   for (int j = PRE ? (grp == 0 ? i : p.nB) : (live ? grp : p.nB); j < p.nB; j += PRE ? p.nB : p.ng) {
     const T* cj = covB + (size_t)j * m * m;
+    T fw = fw0;
+    if constexpr (WEIGHTED) fw = static_cast<const T*>(p.W)[(size_t)i * p.nB + j];   // one address per group: a broadcast read
     if (active) {
       for (int c = 0; c <= r; ++c) a[r * LD_ + c] = T(0.5) * (ci[r * m + c] + cj[r * m + c]);
     }
@@ -372,9 +381,9 @@ template <typename T, int M> struct GradEntries {
 // runs small problems, the host pads large ones to an EXACT size)
 template <typename T, int M, bool EXACT, int MODE = GAUSS_PLAIN>
 __global__ __launch_bounds__(256, ((M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 40 ? 4 : ((M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 140 ? 2 : 1))
-                                   >> ((MODE == GAUSS_FUSED && !EXACT && (M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 140) ? 1 : 0))
+                                   >> (((MODE == GAUSS_FUSED || MODE == GAUSS_FUSED_W) && !EXACT && (M * (M + 1) / 2) * (int)(sizeof(T) / 4) <= 140) ? 1 : 0))
 void gauss_pair_reg_kernel(const GaussParams p) {
-  constexpr bool FUSED = MODE == GAUSS_FUSED, PRE = MODE == GAUSS_PRE;
+  constexpr bool WEIGHTED = MODE == GAUSS_FUSED_W, FUSED = MODE == GAUSS_FUSED || WEIGHTED, PRE = MODE == GAUSS_PRE;
   constexpr int TRI = M * (M + 1) / 2, NACC = TRI + M;
   __shared__ T s_acc[4][NACC | 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -394,7 +403,7 @@ void gauss_pair_reg_kernel(const GaussParams p) {
   // Sbar^-1 is needed where logdet Sbar has a gradient
   const bool with_inv = FUSED ? p.kind <= SQFA_GAUSS_HELLINGER : gLD != nullptr;
   const T* ldc = static_cast<const T*>(p.ldc);
-  const T fw = fused_weight<T>(p), feps = fused_eps<T>(p);
+  const T fw0 = fused_weight<T>(p), feps = fused_eps<T>(p);
   T loss_acc = T(0), csum = T(0);   // fused: per-wave partial sums and counts (wave-uniform: scalar registers)
   int n_nan = 0, n_inf = 0;
 
@@ -471,6 +480,10 @@ void gauss_pair_reg_kernel(const GaussParams p) {
       if (valid) static_cast<T*>(p.ldc)[j] = ld;
       return;
     }
+    // weighted: lane = class j, one coalesced segment of row i of W per round; issued here, behind the factorisation (its
+    // register peak) and ahead of the forward substitution, which covers the load
+    T fw = fw0;
+    if constexpr (WEIGHTED) fw = static_cast<const T*>(p.W)[valid ? (size_t)i * p.nB + j : (size_t)0];
     // ---- z = R^-1 delta, Q = |z|^2 ----
     T q = T(0);
 #pragma unroll
@@ -740,10 +753,11 @@ extern "C" size_t sqfa_gauss_pairwise_workspace_bytes(int n, int m, int dtype) {
   return 3 * align256((size_t)n * 8) + align256((size_t)n * mp * mp * elem);
 }
 
-extern "C" int sqfa_gauss_pairwise_loss(const void* mu, const void* cov, int n, int m, int dtype, int kind, double eps,
-                                        double uniform_weight, void* loss_out, void* gmu_out, void* gcov_out,
-                                        void* dist_out, int* nonfinite_out, void* workspace, size_t workspace_bytes,
-                                        void* stream_) {
+extern "C" int sqfa_gauss_pairwise_loss_weighted(const void* mu, const void* cov, int n, int m, int dtype, int kind,
+                                                 double eps, const void* pair_weights, double uniform_weight,
+                                                 void* loss_out, void* gmu_out, void* gcov_out, void* dist_out,
+                                                 int* nonfinite_out, void* workspace, size_t workspace_bytes,
+                                                 void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (mu == nullptr || cov == nullptr || n < 2 || m < 1) return SQFA_ERR_BAD_ARGUMENT;
   if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
@@ -770,7 +784,18 @@ extern "C" int sqfa_gauss_pairwise_loss(const void* mu, const void* cov, int n, 
     pre.gmuA = pre.gcovA = nullptr;
     if (dispatch_gauss<GAUSS_PRE>(pre, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   }
-  if (dispatch_gauss<GAUSS_FUSED>(p, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
+  p.W = pair_weights;
+  const hipError_t e = pair_weights != nullptr ? dispatch_gauss<GAUSS_FUSED_W>(p, dtype, stream)
+                                               : dispatch_gauss<GAUSS_FUSED>(p, dtype, stream);
+  if (e != hipSuccess) return SQFA_ERR_LAUNCH;
   return launch_pair_loss_finalize(p.loss_part, p.cnt_part, n, dtype, loss_out, nonfinite_out, stream) == hipSuccess
              ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+extern "C" int sqfa_gauss_pairwise_loss(const void* mu, const void* cov, int n, int m, int dtype, int kind, double eps,
+                                        double uniform_weight, void* loss_out, void* gmu_out, void* gcov_out,
+                                        void* dist_out, int* nonfinite_out, void* workspace, size_t workspace_bytes,
+                                        void* stream_) {
+  return sqfa_gauss_pairwise_loss_weighted(mu, cov, n, m, dtype, kind, eps, nullptr, uniform_weight, loss_out, gmu_out,
+                                           gcov_out, dist_out, nonfinite_out, workspace, workspace_bytes, stream_);
 }

@@ -16,6 +16,11 @@
 // d2 = sum diag^2 + 2 sum lower^2 over the group (DPP / row-swap butterfly, group_sum of pair_kernel.hpp), then
 // acc += c diff.  The pair i == j is skipped.  At the end the NS groups of a class are combined through LDS in the order
 // s = 0, 1, ...: one writer per G_i, no atomics, bitwise reproducible.
+// Weighted variant (template parameter WEIGHTED, sqfa_log_euclidean_pairwise_loss_weighted with a weight matrix): w becomes
+// w_ij = W[i n + j].  The TI x TJ block of W that a tile needs travels with the tile -- gathered to registers while the
+// previous tile is consumed (coalesced along j), stored to LDS between the same two barriers -- so the pair loop reads its
+// weight from LDS next to the row of L_j and holds no global load.  Row i weighs every ordered pair (i, j) with its own
+// w_ij and class j weighs the same pair with w_ji: W must be symmetric.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sqfa_hip.h"
@@ -36,6 +41,7 @@ struct LogEucParams {
   int n, m, sqrt_mode;
   double eps, weight;
   float epsf, weightf;  // the same two, rounded once on the host
+  const void* W;        // (n,n) symmetric per-pair weights (WEIGHTED kernels only; `weight` is then unused)
 };
 
 template <typename T> __device__ __forceinline__ T le_weight(const LogEucParams& p);
@@ -75,16 +81,18 @@ struct LogEucCfg {
   static constexpr size_t COMB_BYTES = (size_t)TI * (NS > 1 ? NS - 1 : 1) * ROW_BYTES;   // the combine buffer reuses the tile
   static constexpr size_t BUF_BYTES = TILE_BYTES > COMB_BYTES ? TILE_BYTES : COMB_BYTES;
   static_assert(TI * NS * G == 256, "lane groups must fill the workgroup");
-  static_assert(BUF_BYTES + PITCH * sizeof(int) + 2048 <= 64 * 1024, "LDS per workgroup stays within 64 KiB");
+  static constexpr size_t W_BYTES = (size_t)TI * TJ * sizeof(T);   // weighted variant: the tile's block of pair weights
+  static_assert(BUF_BYTES + W_BYTES + PITCH * sizeof(int) + 2048 <= 64 * 1024, "LDS per workgroup stays within 64 KiB");
 };
 
-template <typename Cfg, typename T>
+template <typename Cfg, typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucParams p) {
   constexpr int G = Cfg::G, ED = Cfg::ED, E = Cfg::E, PITCH = Cfg::PITCH, TI = Cfg::TI, NS = Cfg::NS, TJ = Cfg::TJ;
   __shared__ __align__(16) unsigned char s_buf[Cfg::BUF_BYTES];
   __shared__ int s_map[PITCH];        // slot position -> offset of the entry inside an m x m matrix, -1: padding
   __shared__ double s_loss[TI][NS];
   __shared__ int s_cnt[TI][NS][2];
+  __shared__ T s_w[WEIGHTED ? TI * TJ : 1];   // weights of the current tile: row ti, column jj
   T* tile = reinterpret_cast<T*>(s_buf);
   const int tid = threadIdx.x, n = p.n, m = p.m, mm = m * m;
   const int lane = tid % G, gid = tid / G, ti = gid % TI, s = gid / TI;
@@ -124,8 +132,20 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
   // A tile is gathered from global memory (L2) into registers -- LOADS independent loads per thread, issued back to back --
   // while the previous tile is being consumed, and moved to LDS between two barriers.
   constexpr int LOADS = (TJ * PITCH + 255) / 256;
-  T stage[LOADS];
+  constexpr int WLOADS = WEIGHTED ? (TI * TJ + 255) / 256 : 1;
+  T stage[LOADS], wstage[WLOADS];
+  const T* W = static_cast<const T*>(p.W);
   auto gather = [&](int j0) {
+    if constexpr (WEIGHTED) {
+#pragma unroll
+      for (int u = 0; u < WLOADS; ++u) {
+        const int q = tid + u * 256;
+        const int it = blockIdx.x * TI + q / TJ, j = j0 + q % TJ;
+        const bool valid = q < TI * TJ && it < n && j < n;
+        const T v = W[valid ? (size_t)it * n + j : 0];
+        wstage[u] = valid ? v : T(0);
+      }
+    }
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
       const int q = tid + u * 256;
@@ -143,12 +163,21 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
       const int q = tid + u * 256;
       if (q < TJ * PITCH) tile[q] = stage[u];
     }
+    if constexpr (WEIGHTED) {
+#pragma unroll
+      for (int u = 0; u < WLOADS; ++u) {
+        const int q = tid + u * 256;
+        if (q < TI * TJ) s_w[q] = wstage[u];
+      }
+    }
     __syncthreads();
     if (j0 + TJ < n) gather(j0 + TJ);   // the next tile's loads are in flight during this tile's pairs
 #pragma unroll 1
     for (int jj = s; jj < TJ; jj += NS) {
       const int j = j0 + jj;
       const T* row = tile + jj * PITCH + lane;
+      T wij = w;
+      if constexpr (WEIGHTED) wij = s_w[ti * TJ + jj];
       T diff[E];
       T dd = T(0), od = T(0);
 #pragma unroll
@@ -162,15 +191,15 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
         T D, c;
         if (sqrt_mode) {
           D = le_sqrt(d2 + eps);
-          c = w / D;
+          c = wij / D;
         } else {
           D = d2;
-          c = T(2) * w;
+          c = T(2) * wij;
         }
 #pragma unroll
         for (int e = 0; e < E; ++e) acc[e] += c * diff[e];
         if (j < i) {
-          loss_acc += (double)D;
+          loss_acc += WEIGHTED ? (double)wij * (double)D : (double)D;
           if (D != D) ++n_nan;
           else if (D - D != T(0)) ++n_inf;
         }
@@ -202,7 +231,7 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
       c0 += s_cnt[ti][q][0];
       c1 += s_cnt[ti][q][1];
     }
-    p.loss_part[i] = p.weight * l;
+    p.loss_part[i] = WEIGHTED ? l : p.weight * l;   // weighted: w_ij went into the sum pair by pair
     p.cnt_part[2 * i] = c0;
     p.cnt_part[2 * i + 1] = c1;
     if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? le_sqrt(eps) : T(0);   // as the reference: sqrt(0 + eps)
@@ -225,7 +254,10 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
 template <typename T, int G, int MMAX>
 static hipError_t launch_log_euclidean(const LogEucParams& p, hipStream_t stream) {
   using Cfg = LogEucCfg<T, G, MMAX>;
-  hipLaunchKernelGGL((log_euclidean_pair_kernel<Cfg, T>), dim3((p.n + Cfg::TI - 1) / Cfg::TI), dim3(256), 0, stream, p);
+  if (p.W != nullptr)
+    hipLaunchKernelGGL((log_euclidean_pair_kernel<Cfg, T, true>), dim3((p.n + Cfg::TI - 1) / Cfg::TI), dim3(256), 0, stream, p);
+  else
+    hipLaunchKernelGGL((log_euclidean_pair_kernel<Cfg, T, false>), dim3((p.n + Cfg::TI - 1) / Cfg::TI), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 
@@ -275,9 +307,10 @@ extern "C" size_t sqfa_log_euclidean_workspace_bytes(int n, int m, int dtype) {
   return log_euclidean_layout(n, m, dtype, &w) ? w.total : 0;
 }
 
-extern "C" int sqfa_log_euclidean_pairwise_loss(const void* S, int n, int m, int dtype, int sqrt_mode, double eps,
-                                                double uniform_weight, void* loss_out, void* gradS_out, void* dist_out,
-                                                int* nonfinite_out, void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" int sqfa_log_euclidean_pairwise_loss_weighted(const void* S, int n, int m, int dtype, int sqrt_mode, double eps,
+                                                         const void* pair_weights, double uniform_weight, void* loss_out,
+                                                         void* gradS_out, void* dist_out, int* nonfinite_out,
+                                                         void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (S == nullptr || n < 2 || m < 1) return SQFA_ERR_BAD_ARGUMENT;
   if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
@@ -306,6 +339,7 @@ extern "C" int sqfa_log_euclidean_pairwise_loss(const void* S, int n, int m, int
   p.weight = uniform_weight;
   p.epsf = (float)eps;
   p.weightf = (float)uniform_weight;
+  p.W = pair_weights;
   const hipError_t e = dtype == SQFA_F32 ? dispatch_log_euclidean<float>(p, stream) : dispatch_log_euclidean<double>(p, stream);
   if (e != hipSuccess) return SQFA_ERR_LAUNCH;
   // 3. d loss / d S = Daleckii-Krein backward of the logarithm on G
@@ -317,4 +351,11 @@ extern "C" int sqfa_log_euclidean_pairwise_loss(const void* S, int n, int m, int
   if (launch_pair_loss_finalize(p.loss_part, p.cnt_part, n, dtype, loss_out, nonfinite_out, stream) != hipSuccess)
     return SQFA_ERR_LAUNCH;
   return SQFA_OK;
+}
+
+extern "C" int sqfa_log_euclidean_pairwise_loss(const void* S, int n, int m, int dtype, int sqrt_mode, double eps,
+                                                double uniform_weight, void* loss_out, void* gradS_out, void* dist_out,
+                                                int* nonfinite_out, void* workspace, size_t workspace_bytes, void* stream_) {
+  return sqfa_log_euclidean_pairwise_loss_weighted(S, n, m, dtype, sqrt_mode, eps, nullptr, uniform_weight, loss_out,
+                                                   gradS_out, dist_out, nonfinite_out, workspace, workspace_bytes, stream_);
 }

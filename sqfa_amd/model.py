@@ -69,8 +69,10 @@ def _stats_to_scatter(statistics):
 # What one closure evaluation runs (SecondMomentsSQFA._closure_plan): the method _evaluate_<evaluator> and its static
 # arguments.  scale: the pair kernels' scale, or the SQFA_GAUSS_* kind code; metric: "airm" | "bw" | "gauss" | None;
 # weight: -1 / #pairs; shard, reducer: the pair tiles of a multi-GPU fit; inputs: the single node's (raw filters, scatters,
-# means, parametrization kind, noise).  weight and inputs are None in a plan made without statistics.
-ClosurePlan = collections.namedtuple("ClosurePlan", "evaluator scale sqrt_mode metric weight shard reducer inputs")
+# means, parametrization kind, noise).  weight and inputs are None in a plan made without statistics.  pair_weights: the
+# fit's normalised (C,C) per-pair weights (_native.normalized_pair_weights) that replace `weight`, or None (uniform).
+ClosurePlan = collections.namedtuple("ClosurePlan", "evaluator scale sqrt_mode metric weight shard reducer inputs pair_weights",
+                                     defaults=(None,))
 _NATIVE_DTYPES = (torch.float32, torch.float64)
 
 
@@ -96,6 +98,7 @@ class SecondMomentsSQFA(nn.Module):
         self._add_constraint(constraint)
         self.pair_shard = None   # optional sqfa_amd.parallel.PairShard for multi-GPU fits
         self.class_shard = None  # optional sqfa_amd.parallel.ClassShard: statistics hold local classes only
+        self._pair_weights = None  # the running fit's normalised per-pair weights (set and cleared by fitting_loop)
 
     @staticmethod
     def _noise_matrix(feature_noise, k):
@@ -230,7 +233,8 @@ class SecondMomentsSQFA(nn.Module):
             plan = ClosurePlan("log_euclidean", None, cspec[1], None, None, (0, 1), None, None)
         if plan is None or prepared is None:
             return plan
-        return plan._replace(weight=self._pair_weight(self._n_classes_total(prepared)), inputs=inputs)
+        return plan._replace(weight=self._pair_weight(self._n_classes_total(prepared)), inputs=inputs,
+                             pair_weights=self._pair_weights)
 
     def _fused_closure_loss(self, prepared):
         """(loss, flags) through the fused loss+gradient evaluator of _closure_plan, or None when there is none (the
@@ -242,7 +246,7 @@ class SecondMomentsSQFA(nn.Module):
         """The whole closure as ONE autograd node (_native.FusedClosure)."""
         raw, scatters, means, sphere, noise = plan.inputs
         return _native.FusedClosure.apply(raw, scatters, means, noise, plan.scale, plan.sqrt_mode, plan.weight, plan.shard,
-                                          plan.reducer, sphere, plan.metric)
+                                          plan.reducer, sphere, plan.metric, plan.pair_weights)
 
     def _evaluate_chain(self, plan, prepared):
         """The same loss as a chain of autograd nodes (parametrization -> projection -> noise -> [embedding] ->
@@ -251,18 +255,18 @@ class SecondMomentsSQFA(nn.Module):
         if self.class_shard is not None:
             S = self.class_shard.gather(S)
         return _native.PairwiseLoss.apply(S, plan.scale, distances.EPSILON, plan.sqrt_mode, plan.weight, plan.shard,
-                                          plan.reducer, plan.metric)
+                                          plan.reducer, plan.metric, plan.pair_weights)
 
     def _evaluate_gauss(self, plan, prepared):
         """parametrization -> projection -> noise -> _native.GaussPairwiseLoss (one fused pass over the class pairs)."""
         stats = self._feature_statistics(prepared, True)
         return _native.GaussPairwiseLoss.apply(stats["means"], stats["covariances"], int(plan.scale), distances.EPSILON,
-                                               plan.weight)
+                                               plan.weight, plan.pair_weights)
 
     def _evaluate_log_euclidean(self, plan, prepared):
         """parametrization -> projection (native where it applies) -> noise -> _native.LogEuclideanPairwiseLoss."""
         return _native.LogEuclideanPairwiseLoss.apply(self._feature_scatters(prepared, True), plan.sqrt_mode,
-                                                      distances.EPSILON, plan.weight)
+                                                      distances.EPSILON, plan.weight, plan.pair_weights)
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once
@@ -318,17 +322,19 @@ class SecondMomentsSQFA(nn.Module):
             register_parametrization(self, "filters", FixedFilters(n_row_fixed=n_row_fixed))
 
     def fit(self, X=None, y=None, data_statistics=None, max_epochs=300, lr=0.1, estimator="empirical",
-            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, **kwargs):
+            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, pair_weights=None, **kwargs):
         """Fit the filters with LBFGS (reference: model.py:270-414).  Either ``X, y`` or
         ``data_statistics``; ``pairwise=True`` learns the filters two at a time, holding the
-        earlier ones fixed.  Extra keyword arguments go to torch.optim.LBFGS."""
+        earlier ones fixed.  ``pair_weights``: optional symmetric, non-negative (C,C) weights W of the class pairs; the
+        loss becomes -sum_{i>j} W_ij D_ij / sum_{i>j} W_ij (the diagonal is ignored; every stage of a pairwise fit uses the
+        same weights).  Extra keyword arguments go to torch.optim.LBFGS."""
         if data_statistics is None:
             if X is None or y is None:
                 raise ValueError("Either data_statistics or X and y must be provided.")
             data_statistics = class_statistics(X, y, estimator=estimator)
         _check_statistics(data_statistics)
         loop = dict(max_epochs=max_epochs, lr=lr, show_progress=show_progress, return_loss=True,
-                    atol=atol, **kwargs)
+                    atol=atol, pair_weights=pair_weights, **kwargs)
         if not pairwise:
             loss, elapsed = fitting_loop(model=self, data_statistics=data_statistics, **loop)
         else:
@@ -413,8 +419,9 @@ class SQFA(SecondMomentsSQFA):
         return distances.embed_gaussian(self._feature_statistics(prepared, True))
 
     def fit(self, X=None, y=None, data_statistics=None, max_epochs=300, lr=0.1, estimator="empirical",
-            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, **kwargs):
-        """Fit with LBFGS (reference: model.py:548-630); ``data_statistics`` must be a dict."""
+            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, pair_weights=None, **kwargs):
+        """Fit with LBFGS (reference: model.py:548-630); ``data_statistics`` must be a dict.  ``pair_weights`` as in
+        SecondMomentsSQFA.fit."""
         if data_statistics is None:
             if X is None or y is None:
                 raise ValueError("Either data_statistics or X and y must be provided.")
@@ -422,5 +429,6 @@ class SQFA(SecondMomentsSQFA):
         else:
             _check_statistics(data_statistics, needs_dict=True)
         out = super().fit(data_statistics=data_statistics, max_epochs=max_epochs, lr=lr, estimator=estimator,
-                          pairwise=pairwise, show_progress=show_progress, return_loss=True, atol=atol, **kwargs)
+                          pairwise=pairwise, show_progress=show_progress, return_loss=True, atol=atol,
+                          pair_weights=pair_weights, **kwargs)
         return out if return_loss else None

@@ -94,12 +94,22 @@ size_t sqfa_airm_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int s
  *                        metric of the MEAN class (class_factor_mean_kernel) instead of the plain inner product: 0.2-0.8
  *                        fewer sweeps (-8 % at m = 16 / 17) for classes that share a dominant covariance, as real class
  *                        statistics do; +1-3 % on classes scattered around a multiple of I (BASELINE's synthetic
- *                        generator), hence opt-in.  0 (default) / -1 = off.  Every shard of a job passes the same value. */
+ *                        generator), hence opt-in.  0 (default) / -1 = off.  Every shard of a job passes the same value.
+ *   launch_policy        which launches a call is made of; the results are bit-identical whatever the value (tests, A/B
+ *                        timing).  0 (default) = every fused launch that applies, -1 = the separate launches throughout
+ *                        (Cholesky, class factor pass, pair tiles, slab reduction), > 0 = a mask of SQFA_LAUNCH_* bits: only
+ *                        those fused launches.  SQFA_LAUNCH_FUSED_PROLOGUE: when the class factor pass runs in the plain
+ *                        metric on a register row with m <= 24, the A side's Cholesky factor, inverse, slab slot table and
+ *                        factor pass are ONE launch (class_prologue_kernel).  SQFA_LAUNCH_FUSED_REDUCTION is reserved: no call
+ *                        interprets it, the slab is always reduced by finalize_kernel. */
+#define SQFA_LAUNCH_FUSED_PROLOGUE  1
+#define SQFA_LAUNCH_FUSED_REDUCTION 2
 typedef struct sqfa_airm_options {
   int geometry_policy;
   int class_factor_policy;
   unsigned long long *sweep_counter;
   int mean_metric_policy;
+  int launch_policy;
 } sqfa_airm_options;
 
 /*

@@ -24,7 +24,8 @@ STATUS_TEXT = {
 class AirmOptions(ctypes.Structure):
     """sqfa_airm_options (include/sqfa_hip.h): per-call policies of sqfa_airm_pairwise_opt."""
     _fields_ = [("geometry_policy", ctypes.c_int), ("class_factor_policy", ctypes.c_int),
-                ("sweep_counter", ctypes.c_void_p), ("mean_metric_policy", ctypes.c_int)]
+                ("sweep_counter", ctypes.c_void_p), ("mean_metric_policy", ctypes.c_int),
+                ("launch_policy", ctypes.c_int)]
 
 
 _PAIRWISE_ARGS = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -56,7 +56,9 @@ def _workspace(query, *args):
 #   sweep_counter None, or an int64 CUDA tensor of two elements {sum of Jacobi sweeps, wave rounds} the kernel adds to
 #   mean_metric   1 the factor pass works in the metric of the mean class where it can (opt-in: pays for classes that share a
 #                 dominant covariance, loses 1-3 % on BASELINE's synthetic generator); 0 (default) plain inner product
-POLICY = {"geometry": 0, "class_factor": 0, "sweep_counter": None, "mean_metric": 0}
+#   launch        0 every fused launch that applies (default), -1 the separate launches throughout, 1 the fused class prologue
+#                 only (a mask of the SQFA_LAUNCH_* bits); bit-identical results whatever the value
+POLICY = {"geometry": 0, "class_factor": 0, "sweep_counter": None, "mean_metric": 0, "launch": 0}
 
 
 class policies:
@@ -82,7 +84,8 @@ class policies:
 def _options():
     cnt = POLICY["sweep_counter"]
     return _lib.AirmOptions(int(POLICY["geometry"]), int(POLICY["class_factor"]),
-                            ctypes.c_void_p(cnt.data_ptr()) if cnt is not None else None, int(POLICY["mean_metric"]))
+                            ctypes.c_void_p(cnt.data_ptr()) if cnt is not None else None, int(POLICY["mean_metric"]),
+                            int(POLICY["launch"]))
 
 
 def hip_pair_backend(A, B, *, scale, eps, sqrt_mode, weights, uniform_weight, shard,

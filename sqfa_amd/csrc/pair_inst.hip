@@ -26,6 +26,9 @@ hipError_t SQFA_CAT(launch_pair2d_bw_, SQFA_TAG, SQFA_MR)(const PairParams& p, h
 hipError_t SQFA_CAT(launch_factor2d_, SQFA_TAG, SQFA_MR)(const PairParams& p, hipStream_t stream) {
   return launch_class_factors<PairCfg2D<SQFA_T, SQFA_MR, SQFA_G, SQFA_CPL, SQFA_TJ, SQFA_WAVES, SQFA_RS>>(p, stream);
 }
+hipError_t SQFA_CAT(launch_prologue2d_, SQFA_TAG, SQFA_MR)(const PairParams& p, const void* S, void* Linv, hipStream_t stream) {
+  return launch_class_prologue<PairCfg2D<SQFA_T, SQFA_MR, SQFA_G, SQFA_CPL, SQFA_TJ, SQFA_WAVES, SQFA_RS>>(p, S, Linv, stream);
+}
 hipError_t SQFA_CAT(launch_classeig2d_, SQFA_TAG, SQFA_MR)(const void* LT, int n, int m, double* U, double* lam, hipStream_t stream) {
   return launch_class_eig<PairCfg2D<SQFA_T, SQFA_MR, SQFA_G, SQFA_CPL, SQFA_TJ, SQFA_WAVES, SQFA_RS>>(LT, n, m, U, lam, stream);
 }
@@ -46,6 +49,10 @@ hipError_t SQFA_CAT(launch_pair_bw_, SQFA_TAG, SQFA_MR)(const PairParams& p, hip
 }
 hipError_t SQFA_CAT(launch_factor_, SQFA_TAG, SQFA_MR)(const PairParams& p, hipStream_t stream) {
   return launch_class_factors<PairCfg<SQFA_T, SQFA_MR, SQFA_G, SQFA_CPL, SQFA_TJ, SQFA_WAVES>>(p, stream);
+}
+// the fused class prologue (K0 + K0b of the A side in one launch): depends on (T, MR) only as well
+hipError_t SQFA_CAT(launch_prologue_, SQFA_TAG, SQFA_MR)(const PairParams& p, const void* S, void* Linv, hipStream_t stream) {
+  return launch_class_prologue<PairCfg<SQFA_T, SQFA_MR, SQFA_G, SQFA_CPL, SQFA_TJ, SQFA_WAVES>>(p, S, Linv, stream);
 }
 // per-class eigen-decomposition (spd_log / spd_sqrt): depends on (T, MR) only, not on the pair geometry of this row
 hipError_t SQFA_CAT(launch_classeig_, SQFA_TAG, SQFA_MR)(const void* LT, int n, int m, double* U, double* lam, hipStream_t stream) {

@@ -143,6 +143,26 @@ __device__ inline void write_row_start_table(const PairParams& pp, int TI, int* 
   if (threadIdx.x == 0) row_start[pp.nbi] = base;
 }
 
+// The same table written by ONE wave (the fused class prologue: a wave that would otherwise idle), integer prefix sums over
+// the lanes: the same numbers.
+__device__ inline void write_row_start_table_wave(const PairParams& pp, int TI, int* row_start, int lane) {
+  int base = 0;
+  for (int b0 = 0; b0 < pp.nbi; b0 += 64) {
+    const int bi = b0 + lane;
+    int cnt = 0, first;
+    if (bi < pp.nbi)
+      cnt = shard_tiles_in_row(bi, tiles_in_row(bi, pp.nbj, TI, pp.tj, pp.self_mode), pp.shard_index, pp.shard_count, &first);
+    int incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    if (bi < pp.nbi) row_start[bi] = base + incl - cnt;
+    base += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) row_start[pp.nbi] = base;
+}
+
 __host__ __device__ constexpr int ilog2(int v);
 __host__ __device__ constexpr int pow2ceil(int v) {
   int p = 1;
@@ -2022,6 +2042,226 @@ hipError_t launch_class_factors(const PairParams& p, hipStream_t stream) {
     }
     hipLaunchKernelGGL((class_factor_kernel<FC>), dim3(blocks), dim3(64), 0, stream,
                        static_cast<T*>(const_cast<void*>(p.LT)), p.nA, Cfg::FACTOR_SWEEPS);
+    return hipGetLastError();
+  }
+}
+
+// ---- fused class prologue: K0 and K0b of the A side in ONE launch ------------------------------------------------------
+// 1/sqrt(x) in double without the IEEE sqrt/divide sequences: hardware estimate + 2 Newton steps
+__device__ __forceinline__ double fast_rsqrt(double x) {
+  double y = __builtin_amdgcn_rsq(x);
+  y = y * (1.5 - 0.5 * x * y * y);
+  y = y * (1.5 - 0.5 * x * y * y);
+  return y;
+}
+
+// What cholesky_kernel (sqfa_api.hip) followed by class_factor_kernel compute for the A classes of a call, bit for bit, without
+// the second launch and without storing the triangular factor only to load it again: LT is written once, already orthogonalised.
+// Rows up to MR = 24 only (kPrologueMaxDim): class_factor_kernel sweeps them with 16 lanes per class.
+// A workgroup is the PPW = 4 classes that class_factor_kernel packs into one wave (the __any that ends its sweeps is taken
+// over exactly them).  Wave w factorises class blockIdx.x * PPW + w on its own -- program order and wave-level fences between
+// the pivots, no workgroup barrier -- and leaves L (double) in LDS.  After the one barrier, wave 0 rounds the factors to the I/O
+// type, as the store and reload between the two launches did, and runs class_jacobi_sweeps on all PPW classes; the other waves,
+// which would idle meanwhile, compute and store the inverses and (block 0) the slab slot table: neither is on the critical path.
+//   Cholesky: the same right-looking elimination on the unscaled columns; the update is elementwise, so each lane keeps its
+//             entries (column lane % CW, rows lane / CW + k 64 / CW) in registers and only column k and the pivot travel
+//             through LDS: one LDS round trip per pivot.
+//   Inverse:  cholesky_kernel's split of the inner sum over 4 lanes per column and its two xor adds, 16 columns of a class at
+//             a time, by diagonals with the partial results in registers (see there).
+// Bit-identity with the two launches rests on the same expressions compiling to the same instructions in both places: the
+// elimination update and the Newton steps are written as cholesky_kernel writes them; the inverse's inner sum is an explicit
+// fma here, which is what hipcc's default contraction (-ffp-contract=fast) makes of cholesky_kernel's `acc += a * b`.
+// tests/test_gpu_launch_policy.py compares the two paths bit for bit and would catch a compiler that decides otherwise.
+constexpr int kPrologueMaxDim = 24;
+template <typename Tio, int MR>
+__global__ __launch_bounds__(256) void class_prologue_kernel(
+    const Tio* __restrict__ S, int m, int nA, Tio* __restrict__ LT, Tio* __restrict__ Linv, int* __restrict__ row_start,
+    const PairParams pp, int TI, int max_sweeps) {
+  using FC = FactorCfg<Tio, MR>;
+#if SQFA_FACTOR_F64   // the sweeps' arithmetic type, as in class_factor_kernel
+  using T = double;
+#else
+  using T = Tio;
+#endif
+  using R = Real<T>;
+  constexpr int G = FC::G, CPL = FC::CPL, PPW = FC::PPW, P = MR + 1;
+  static_assert(MR <= kPrologueMaxDim && PPW == 4, "four classes per workgroup, one wave each");
+  constexpr int CLS_DOUBLES = MR * P + 2 * MR;
+  __shared__ double lds_prologue[PPW * CLS_DOUBLES];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  auto wave_sync = [] {  // LDS traffic of one wave is in program order: only the compiler has to be told
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  };
+  {
+    const int cls = blockIdx.x * PPW + wave;
+    double* a = lds_prologue + (size_t)wave * CLS_DOUBLES;  // a[r * P + k]: L, lower triangle
+    double* rd = a + MR * P;                                 // 1 / L[k][k]
+    double* colb = rd + MR;                                  // column k of the elimination step in flight
+    if (cls < nA) {
+      constexpr int CW = MR <= 16 ? 16 : 32, RPW = 64 / CW, NR = (MR + RPW - 1) / RPW;
+      const int c = lane % CW, rb = lane / CW;
+      const Tio* s = S + (size_t)cls * m * m;
+      double v[NR];
+#pragma unroll
+      for (int i = 0; i < NR; ++i) {
+        const int r = rb + i * RPW;
+        v[i] = (r < m && c <= r) ? (double)s[(size_t)r * m + c] : 0.0;
+      }
+      const int cc = c < MR ? c : 0;
+      for (int k = 0; k < m; ++k) {
+        if (c == k) {
+#pragma unroll
+          for (int i = 0; i < NR; ++i) {
+            const int r = rb + i * RPW;
+            if (r < MR) colb[r] = v[i];
+          }
+        }
+        wave_sync();
+        const double akk = colb[k];
+        // a non-positive or NaN pivot poisons the trailing block: NaN here and everywhere downstream
+        double rk = __builtin_amdgcn_rcp(akk);
+        rk = rk * (2.0 - akk * rk);
+        rk = rk * (2.0 - akk * rk);
+        if (!(akk > 0.0)) rk = __builtin_nan("");
+        const double ack = colb[cc];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          const int r = rb + i * RPW;
+          const double ark = colb[r < MR ? r : 0];
+          if (c > k && c <= r && r < m) v[i] -= ark * ack * rk;
+        }
+        wave_sync();
+      }
+#pragma unroll
+      for (int i = 0; i < NR; ++i) {
+        const int r = rb + i * RPW;
+        if (r == c && r < m) rd[r] = fast_rsqrt(v[i]);
+      }
+      wave_sync();
+      {
+        const double rdc = rd[c < m ? c : 0];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          const int r = rb + i * RPW;
+          if (r < m && c <= r) a[r * P + c] = v[i] * rdc;  // r == c: akk * rs = sqrt(akk)
+        }
+      }
+      wave_sync();
+    }
+  }
+  __syncthreads();
+  if (wave != 0) {
+    // the waves that would idle while wave 0 sweeps: the slab slot table (block 0) and the inverses -- each wave its own
+    // class, wave 1 that of wave 0 as well -- off the critical path
+    if (row_start != nullptr && blockIdx.x == 0 && wave == PPW - 1) write_row_start_table_wave(pp, TI, row_start, lane);
+    if (Linv == nullptr) return;
+    for (int q = 0; q < (wave == 1 ? 2 : 1); ++q) {
+      const int slot = q == 0 ? wave : 0;
+      const int cls = blockIdx.x * PPW + slot;
+      if (cls >= nA) continue;
+      const double* a = lds_prologue + (size_t)slot * CLS_DOUBLES;
+      const double* rd = a + MR * P;
+      // inverse X = L^-1 (self mode only: nobody reads it otherwise).  cholesky_kernel's arithmetic -- 4 lanes per column, lane
+      // `part` sums the terms k = col + part, col + part + 4, ... in ascending order, then the two xor adds -- evaluated by
+      // DIAGONALS: step d yields X[col + d][col] of 16 columns at once (columns are independent), so the X values a lane
+      // needs are its quad's own earlier results and stay in registers (xk[j] = X[col + part + 4 j][col], static indices);
+      // L comes from LDS through loads that depend on nothing, and X goes straight to Linv.
+      {
+        Tio* li = Linv + (size_t)cls * (MR * MR);  // row-major MR x MR (the packed layout starts at MR = 32)
+        // everything but the lower triangle of the m x m block: zeros and the identity padding
+        for (int idx = lane; idx < MR * MR; idx += 64) {
+          const int r = idx / MR, k = idx % MR;
+          if (r < m && k <= r) continue;
+          li[idx] = r == k ? Tio(1) : Tio(0);
+        }
+        constexpr int NX = (MR + 3) / 4;
+        for (int cb = 0; cb < m; cb += 16) {
+          const int col = cb + (lane >> 2), part = lane & 3;
+          double xk[NX];
+#pragma unroll
+          for (int j = 0; j < NX; ++j) xk[j] = 0.0;
+#pragma unroll
+          for (int d = 0; d < MR; ++d) {
+            if (d >= m - cb) break;
+            const int r = col + d;
+            const bool live = r < m;
+            const int rr = live ? r : 0;
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; 4 * j < d; ++j) {  // k = col + part + 4 j < r
+              const int k = col + part + 4 * j;
+              const double f = __builtin_fma(a[rr * P + (k < MR ? k : 0)], xk[j], acc);
+              acc = part + 4 * j < d ? f : acc;
+            }
+            acc += lane_xor<1>(acc, 0);
+            acc += lane_xor<2>(acc, 0);
+            // the quad's lanes hold the same sum up to the order of its operands: all continue with lane 0's
+            const double xv = dpp_mov<0x00>(((d == 0 ? 1.0 : 0.0) - acc) * rd[rr]);
+            if ((d & 3) == part) xk[d >> 2] = xv;
+            if (part == 0 && live) li[r * MR + col] = (Tio)xv;
+          }
+        }
+      }
+    }
+    return;
+  }
+  // K0b: one lane group per class, slot c of lane g is column c * G + g (class_factor_kernel); lane groups past the last
+  // class sweep a copy of the last class, as they do there
+  const int g = lane % G;
+  const int cls = blockIdx.x * PPW + lane / G;
+  const int slot = (cls < nA ? cls : nA - 1) - blockIdx.x * PPW;
+  const double* a = lds_prologue + (size_t)slot * CLS_DOUBLES;
+  T x[CPL][MR];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    const int col = c * G + g;
+#pragma unroll
+    for (int k = 0; k < MR; ++k) {
+      // LT[col * MR + k] = L[k][col], identity padded, rounded to the I/O type
+      double w = col == k ? 1.0 : 0.0;
+      if (col < m && k < m) w = k >= col ? a[k * P + col] : 0.0;
+      x[c][k] = col < MR ? (T)(Tio)w : T(0);
+    }
+  }
+  T D[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) D[c] = T(1);
+  class_jacobi_sweeps<T, MR, G, CPL>(x, D, max_sweeps);
+  if (cls < nA) {
+    Tio* lt = LT + (size_t)cls * (MR * MR);
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int col = c * G + g;
+      if (col < MR) {
+        const T dc = R::sqrt_(D[c]);
+        Tio* dst = lt + (size_t)col * MR;
+#pragma unroll
+        for (int r = 0; r < MR; ++r) dst[r] = (Tio)(x[c][r] * dc);
+      }
+    }
+  }
+}
+
+// Rows that take the fused prologue: those with a factor pass whose classes sweep four to a wave (m <= 24).  The wider rows
+// keep the two launches: a version of the kernel that covered them was measured at the c4 pair stage (C=1000, m=32) at
+// 5.74 -> 5.78 ms per step, the pair kernel itself 5.55 -> 5.59 ms on bit-identical factors (profiles/pair_step_overhead.txt,
+// section 5) -- a loss that is not understood, against 6 us the prologue itself saved there -- and was withdrawn.
+template <typename Cfg> constexpr bool has_class_prologue() { return Cfg::DENSE_FACTOR && Cfg::MR <= kPrologueMaxDim; }
+
+// The fused prologue for the A classes S of a call (Linv: self mode, or nullptr).  The caller has decided that the class factor
+// pass runs (launch_class_factors' rule) in the plain metric; rows without has_class_prologue have no such kernel.
+template <typename Cfg>
+hipError_t launch_class_prologue(const PairParams& p, const void* S, void* Linv, hipStream_t stream) {
+  if constexpr (!has_class_prologue<Cfg>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using T = typename Cfg::type;
+    using FC = FactorCfg<T, Cfg::MR>;
+    const int blocks = (p.nA + FC::PPW - 1) / FC::PPW;
+    hipLaunchKernelGGL((class_prologue_kernel<T, Cfg::MR>), dim3(blocks), dim3(256), 0, stream, static_cast<const T*>(S), p.m, p.nA,
+                       static_cast<T*>(const_cast<void*>(p.LT)), static_cast<T*>(Linv), p.row_start, p, Cfg::TI, Cfg::FACTOR_SWEEPS);
     return hipGetLastError();
   }
 }

@@ -22,34 +22,40 @@ namespace sqfa {
   hipError_t launch_pair_f32_##MR(const PairParams&, hipStream_t);   \
   hipError_t launch_pair_bw_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor_f32_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_prologue_f32_##MR(const PairParams&, const void*, void*, hipStream_t); \
   hipError_t launch_classeig_f32_##MR(const void*, int, int, double*, double*, hipStream_t);
 #define SQFA_DECL_F64(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f64_##MR(const PairParams&, hipStream_t);   \
   hipError_t launch_pair_bw_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor_f64_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_prologue_f64_##MR(const PairParams&, const void*, void*, hipStream_t); \
   hipError_t launch_classeig_f64_##MR(const void*, int, int, double*, double*, hipStream_t);
 SQFA_CONFIGS_F32(SQFA_DECL_F32)
 SQFA_CONFIGS_F64(SQFA_DECL_F64)
 #define SQFA_DECL_F32S(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f32s_##MR(const PairParams&, hipStream_t);  \
   hipError_t launch_pair_bw_f32s_##MR(const PairParams&, hipStream_t); \
-  hipError_t launch_factor_f32s_##MR(const PairParams&, hipStream_t);
+  hipError_t launch_factor_f32s_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_prologue_f32s_##MR(const PairParams&, const void*, void*, hipStream_t);
 SQFA_CONFIGS_F32_SMALL(SQFA_DECL_F32S)
 #define SQFA_DECL_F64S(T, MR, G, CPL, TJ, WV) \
   hipError_t launch_pair_f64s_##MR(const PairParams&, hipStream_t);  \
   hipError_t launch_pair_bw_f64s_##MR(const PairParams&, hipStream_t); \
-  hipError_t launch_factor_f64s_##MR(const PairParams&, hipStream_t);
+  hipError_t launch_factor_f64s_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_prologue_f64s_##MR(const PairParams&, const void*, void*, hipStream_t);
 SQFA_CONFIGS_F64_SMALL(SQFA_DECL_F64S)
 
 #define SQFA_DECL2D_F32(T, MR, GC, CPL, TJ, WV, RS) \
   hipError_t launch_pair2d_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_pair2d_bw_f32_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor2d_f32_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_prologue2d_f32_##MR(const PairParams&, const void*, void*, hipStream_t); \
   hipError_t launch_classeig2d_f32_##MR(const void*, int, int, double*, double*, hipStream_t);
 #define SQFA_DECL2D_F64(T, MR, GC, CPL, TJ, WV, RS) \
   hipError_t launch_pair2d_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_pair2d_bw_f64_##MR(const PairParams&, hipStream_t); \
   hipError_t launch_factor2d_f64_##MR(const PairParams&, hipStream_t); \
+  hipError_t launch_prologue2d_f64_##MR(const PairParams&, const void*, void*, hipStream_t); \
   hipError_t launch_classeig2d_f64_##MR(const void*, int, int, double*, double*, hipStream_t);
 SQFA_CONFIGS2D_F32(SQFA_DECL2D_F32)
 SQFA_CONFIGS2D_F64(SQFA_DECL2D_F64)
@@ -60,15 +66,16 @@ struct Geometry {
   hipError_t (*factor)(const PairParams&, hipStream_t);  // K0b, the class factor pass
   hipError_t (*eig)(const void*, int, int, double*, double*, hipStream_t);  // per-class eigen-decomposition (regular rows)
   hipError_t (*launch_bw)(const PairParams&, hipStream_t);  // the row's Bures-Wasserstein tile kernel
+  hipError_t (*prologue)(const PairParams&, const void*, void*, hipStream_t);  // K0 + K0b of the A side in one launch (class_prologue_kernel); NULL: the row has none (no factor pass, or m > 24)
   bool mean_metric;       // the row's factor pass runs in the metric of the mean class (Cfg::MEAN_METRIC)
   long factor_min_pairs;  // Cfg::FACTOR_MIN_PAIRS: launches with fewer pairs per shard skip the factor pass
 };
 // One row of the table: the numbers come from the configuration type (PairCfg or PairCfg2D), the launchers by name.
 template <typename Cfg>
 static Geometry make_geometry(decltype(Geometry::launch) launch, decltype(Geometry::factor) factor, decltype(Geometry::eig) eig,
-                              decltype(Geometry::launch_bw) launch_bw) {
+                              decltype(Geometry::launch_bw) launch_bw, decltype(Geometry::prologue) prologue) {
   return Geometry{sizeof(typename Cfg::type) == 4 ? SQFA_F32 : SQFA_F64, Cfg::MR, Cfg::TJ, Cfg::TI, Cfg::WAVES, launch, factor, eig,
-                  launch_bw, Cfg::MEAN_METRIC, Cfg::FACTOR_MIN_PAIRS};
+                  launch_bw, has_class_prologue<Cfg>() ? prologue : nullptr, Cfg::MEAN_METRIC, Cfg::FACTOR_MIN_PAIRS};
 }
 
 // The geometry table: every whole-column row (pair_kernel.hpp) and every 2-D row (pair_kernel_2d.hpp: GC column lanes x 2
@@ -91,17 +98,17 @@ static bool find_geometry(int m, int dtype, long pairs, Geometry* out, int geome
     if (g.dtype == dtype && g.MR == best.MR && (geometry_mode > 0 || pairs < max_pairs)) best = g;
   };
 #define SQFA_ROW_F32(T, MR, G, CPL, TJ, WV) \
-  consider(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f32_##MR, launch_factor_f32_##MR, launch_classeig_f32_##MR, launch_pair_bw_f32_##MR));
+  consider(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f32_##MR, launch_factor_f32_##MR, launch_classeig_f32_##MR, launch_pair_bw_f32_##MR, launch_prologue_f32_##MR));
 #define SQFA_ROW_F64(T, MR, G, CPL, TJ, WV) \
-  consider(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f64_##MR, launch_factor_f64_##MR, launch_classeig_f64_##MR, launch_pair_bw_f64_##MR));
+  consider(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f64_##MR, launch_factor_f64_##MR, launch_classeig_f64_##MR, launch_pair_bw_f64_##MR, launch_prologue_f64_##MR));
 #define SQFA_ROW2D_F32(T, MR, GC, CPL, TJ, WV, RS) \
-  consider(make_geometry<PairCfg2D<T, MR, GC, CPL, TJ, WV, RS>>(launch_pair2d_f32_##MR, launch_factor2d_f32_##MR, launch_classeig2d_f32_##MR, launch_pair2d_bw_f32_##MR));
+  consider(make_geometry<PairCfg2D<T, MR, GC, CPL, TJ, WV, RS>>(launch_pair2d_f32_##MR, launch_factor2d_f32_##MR, launch_classeig2d_f32_##MR, launch_pair2d_bw_f32_##MR, launch_prologue2d_f32_##MR));
 #define SQFA_ROW2D_F64(T, MR, GC, CPL, TJ, WV, RS) \
-  consider(make_geometry<PairCfg2D<T, MR, GC, CPL, TJ, WV, RS>>(launch_pair2d_f64_##MR, launch_factor2d_f64_##MR, launch_classeig2d_f64_##MR, launch_pair2d_bw_f64_##MR));
+  consider(make_geometry<PairCfg2D<T, MR, GC, CPL, TJ, WV, RS>>(launch_pair2d_f64_##MR, launch_factor2d_f64_##MR, launch_classeig2d_f64_##MR, launch_pair2d_bw_f64_##MR, launch_prologue2d_f64_##MR));
 #define SQFA_ROW_F32S(T, MR, G, CPL, TJ, WV) \
-  consider_small(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f32s_##MR, launch_factor_f32s_##MR, nullptr, launch_pair_bw_f32s_##MR), small_launch_max_pairs(MR));
+  consider_small(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f32s_##MR, launch_factor_f32s_##MR, nullptr, launch_pair_bw_f32s_##MR, launch_prologue_f32s_##MR), small_launch_max_pairs(MR));
 #define SQFA_ROW_F64S(T, MR, G, CPL, TJ, WV) \
-  consider_small(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f64s_##MR, launch_factor_f64s_##MR, nullptr, launch_pair_bw_f64s_##MR), small_launch_max_pairs_f64(MR));
+  consider_small(make_geometry<PairCfg<T, MR, G, CPL, TJ, WV>>(launch_pair_f64s_##MR, launch_factor_f64s_##MR, nullptr, launch_pair_bw_f64s_##MR, launch_prologue_f64s_##MR), small_launch_max_pairs_f64(MR));
   SQFA_CONFIGS_F32(SQFA_ROW_F32)
   SQFA_CONFIGS_F64(SQFA_ROW_F64)
   SQFA_CONFIGS2D_F32(SQFA_ROW2D_F32)
@@ -315,13 +322,7 @@ static bool make_plan(int nA, int nB, int m, int dtype, int shard_count, int geo
 //   per pivot column (one LDS round trip per entry and pivot instead of a serial row loop).
 //   Inverse: X = L^-1 row by row; row r needs rows < r, columns are independent; the inner
 //   sum runs over k in parallel chunks of 4 lanes per column.
-// 1/sqrt(x) in double without the IEEE sqrt/divide sequences: hardware estimate + 2 Newton steps
-__device__ __forceinline__ double fast_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = y * (1.5 - 0.5 * x * y * y);
-  y = y * (1.5 - 0.5 * x * y * y);
-  return y;
-}
+// (fast_rsqrt, 1/sqrt(x) in double from the hardware estimate and two Newton steps: pair_kernel.hpp, shared with the fused prologue)
 
 // Partial sums of the class matrices for the mean class of the mean-metric factor pass: block b adds the classes b, b + P,
 // b + 2P, ... (P = gridDim.x) entry by entry in that order -- fixed association, bitwise reproducible.  out[b][m*m] doubles.
@@ -1067,6 +1068,14 @@ size_t sqfa_airm_workspace_bytes(int nA, int nB, int m, int dtype) {
   return std::max(regular.w.total, small.w.total);
 }
 
+// One call = dependent launches on the caller's stream:
+//   prologue  the class factors and the slab slot table.  Register rows up to m = 24 whose class factor pass runs in the plain
+//             metric: class_prologue_kernel, ONE launch for the A side (K0 + K0b fused; pair_kernel.hpp).  Otherwise K0 cholesky_kernel
+//             (LDS path: cholesky_lds_kernel) and, where the pass runs, K0b class_factor_kernel / class_factor_mean_kernel (with
+//             mean_partial_kernel in front).  Cross mode: one more cholesky_kernel launch for the B side (L^-1 only).
+//   K1        pair_tile_kernel (pair_lds_kernel): every tile writes its partial gradients, loss and flags to the slab
+//   K2        finalize_kernel: fixed-order reduction of the slab, loss, flags, diagonals
+// sqfa_airm_options::launch_policy = -1 keeps K0 and K0b apart on every call; the results are bit-identical either way.
 static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, int dtype, double scale,
                          double eps, int sqrt_mode, const void* pair_weights, double uniform_weight,
                          int shard_index, int shard_count, void* loss_out, void* gradA_out,
@@ -1100,12 +1109,28 @@ static int pairwise_impl(const void* A, int nA, const void* B, int nB, int m, in
     else hipLaunchKernelGGL(mean_partial_kernel<double>, dim3(n_parts), dim3(256), 0, stream, static_cast<const double*>(A), nA, m, mean_parts);
     p.mean_linv = mean_linv;
   }
-  // the A-side launch also writes the slab slot table and carries the mean block
-  hipError_t e = launch_factors(pl, p, stream, A, nA, ws + pl.w.off_lt, pl.self_mode ? ws + pl.w.off_linv : nullptr, p.row_start,
-                                want_mean ? mean_parts : nullptr, n_parts, mean_linv);
-  if (!pl.self_mode && e == hipSuccess) e = launch_factors(pl, p, stream, B, nB, nullptr, ws + pl.w.off_linv, nullptr);
-  if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, pl.lds ? "cholesky_lds_kernel" : "cholesky_kernel", e);
-  if (pl.g.factor != nullptr) {  // K0b: orthogonalise the columns of each A-side factor (same stream: after the Cholesky launches)
+  // Will K0b run in the plain metric on a register row that has the fused prologue (m <= 24)?  Then the A side takes it (class_prologue_kernel:
+  // factor, inverse, slot table and the factor pass's sweeps in one launch, bit-identical to the two it replaces) unless
+  // launch_policy asks for the separate launches.  The rule is launch_class_factors' own.
+  const int launch_policy = options ? options->launch_policy : 0;
+  const bool fused_prologue = (launch_policy == 0 || (launch_policy > 0 && (launch_policy & SQFA_LAUNCH_FUSED_PROLOGUE))) && !pl.lds &&
+                              pl.g.prologue != nullptr && !want_mean && p.factor_mode >= 0 &&
+                              (p.factor_mode > 0 || pair_count(nA, nB, shard_count) >= pl.g.factor_min_pairs);
+  hipError_t e;
+  if (fused_prologue) {
+    e = pl.g.prologue(p, A, pl.self_mode ? ws + pl.w.off_linv : nullptr, stream);
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "class_prologue_kernel", e);
+  } else {
+    // the A-side launch also writes the slab slot table and carries the mean block
+    e = launch_factors(pl, p, stream, A, nA, ws + pl.w.off_lt, pl.self_mode ? ws + pl.w.off_linv : nullptr, p.row_start,
+                       want_mean ? mean_parts : nullptr, n_parts, mean_linv);
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, pl.lds ? "cholesky_lds_kernel" : "cholesky_kernel", e);
+  }
+  if (!pl.self_mode) {  // the B side stores L^-1 only and has no sweeps: cholesky_kernel on every path
+    e = launch_factors(pl, p, stream, B, nB, nullptr, ws + pl.w.off_linv, nullptr);
+    if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, pl.lds ? "cholesky_lds_kernel" : "cholesky_kernel", e);
+  }
+  if (!fused_prologue && pl.g.factor != nullptr) {  // K0b: orthogonalise the columns of each A-side factor (same stream: after the Cholesky launches)
     e = pl.g.factor(p, stream);
     if (e != hipSuccess) return fail(SQFA_ERR_LAUNCH, "class_factor_kernel", e);
   }

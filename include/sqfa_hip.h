@@ -290,8 +290,13 @@ int sqfa_sphere_backward(const void *X, const void *norms, int K, int D, int dty
  * triangular solves and four (history x n) products in six launches, sqfa_amd/_lbfgs.py).
  *   S, Y (h, n): ring buffers of steps and gradient differences; SY (h, h): SY[i][j] = s_i . y_j; h <= 128
  *   sqfa_lbfgs_push        writes (s, y) into ring row `slot` and refreshes row and column `slot` of SY
- *   sqfa_lbfgs_direction   d_out (n) = -H g for the k pairs listed (HOST array `slots`, chronological order);
- *                          H_diag: device scalar (initial Hessian scale) or NULL = 1
+ *   sqfa_lbfgs_direction   d_out (n) = -H g for the k pairs listed (HOST array `slots`, chronological order, no ring
+ *                          row twice: SQFA_ERR_BAD_ARGUMENT); H_diag: device scalar (initial Hessian scale) or NULL = 1.
+ *                          Guarantee: d_out depends only on rows `slots` of S and Y and on the entries SY[a][b] with a
+ *                          and b both in `slots`; every other row and entry may hold anything, NaN included (stale
+ *                          pairs of a ring that has not filled up or was reset), and d_out is bitwise the same.
+ *                          Both calls write nothing but their outputs (row `slot` of S and Y, row and column `slot` of
+ *                          SY; d_out) and `work`.
  *   work                   scratch of sqfa_lbfgs_work_elems(h, n) elements of the dtype, shared by both calls
  *                          (partial dot products, solve vectors, one n-vector)
  */

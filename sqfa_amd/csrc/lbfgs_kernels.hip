@@ -1,5 +1,6 @@
 // lbfgs_kernels.hip -- the L-BFGS search direction d = -H g in compact form, for optimizer state that
-// lives on the device (parameters > 8192 elements: the c3, c4, c5 shapes).
+// lives on the device: every fit without a line search, at every parameter size (sqfa_amd/_optim.py,
+// HOST_SIDE_LBFGS_MAX_NUMEL_COMPACT = 0), from a single filter of a few dozen elements to the c5 shape.
 //
 // The reference optimises with torch.optim.LBFGS (src/sqfa/_optim.py:78-82), whose two-loop recursion is
 // ~4 x history tiny vector operations per iteration; sqfa_amd/_lbfgs.py restates it as two triangular
@@ -406,8 +407,12 @@ extern "C" int sqfa_lbfgs_direction(const void* S, const void* Y, const void* SY
   if (S == nullptr || Y == nullptr || SY == nullptr || slots == nullptr || g == nullptr || d_out == nullptr ||
       work == nullptr || h < 1 || h > LB_MAX_HISTORY || n < 1 || k < 1 || k > h)
     return SQFA_ERR_BAD_ARGUMENT;
-  for (int i = 0; i < k; ++i)
-    if (slots[i] < 0 || slots[i] >= h) return SQFA_ERR_BAD_ARGUMENT;
+  bool seen[LB_MAX_HISTORY] = {};
+  for (int i = 0; i < k; ++i) {
+    // a ring row listed twice would have two threads of lb_solve write one s_inv entry: a silently wrong triangle
+    if (slots[i] < 0 || slots[i] >= h || seen[slots[i]]) return SQFA_ERR_BAD_ARGUMENT;
+    seen[slots[i]] = true;
+  }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (dtype == SQFA_F32)
     return direction_impl(static_cast<const float*>(S), static_cast<const float*>(Y), static_cast<const float*>(SY), h, n,

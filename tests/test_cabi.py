@@ -112,6 +112,8 @@ def test_argument_validation_of_the_round2_entry_points():
     assert lib.sqfa_lbfgs_push(fake, fake, fake, 10, 10, 10, fake, fake, fake, 0, z) == -1          # slot out of range
     slots = (ctypes.c_int * 2)(0, 11)
     assert lib.sqfa_lbfgs_direction(fake, fake, fake, 10, 10, slots, 2, fake, z, fake, fake, 0, z) == -1   # bad slot
+    slots = (ctypes.c_int * 3)(4, 7, 4)
+    assert lib.sqfa_lbfgs_direction(fake, fake, fake, 10, 10, slots, 3, fake, z, fake, fake, 0, z) == -1   # a ring row twice
     # per-shard workspace: never more than the any-shard bound, and decreasing with the shard's share
     any_shards = lib.sqfa_airm_workspace_bytes(1000, 0, 16, 0)
     one, eight = lib.sqfa_airm_workspace_bytes_sharded(1000, 0, 16, 0, 1, 0), lib.sqfa_airm_workspace_bytes_sharded(1000, 0, 16, 0, 8, 0)

@@ -465,6 +465,55 @@ int sqfa_orthogonal_forward(const void *X, const void *base, int K, int D, int d
 int sqfa_orthogonal_backward(const void *X, const void *base, const void *gF, int K, int D, int dtype,
                              void *gX_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Class statistics from labelled points -- class_statistics of the reference (src/sqfa/statistics.py:8-124: per class a
+ * boolean mask, the mean, the centred X_c^T X_c / (n_c - 1), optional OAS shrinkage, and cov + mu mu^T, inside a Python
+ * loop) -- as a segmented, centred SYRK on the exact f32 / f64 MFMA, and the same statistics accumulated over batches.
+ *   points (N,D) row-major, dtype; any D >= 1 (16-byte loads where D % (16 / element size) == 0 and the base is
+ *   16-byte aligned, one element per load otherwise: same results bit for bit)
+ *   row_index (N) int64 or NULL: row k of class c is points[row_index[class_start[c] + k]] -- the indices of a stable
+ *   sort of the labels, so no sorted copy of the points is made; NULL = the rows are already grouped by class
+ *   class_start (C+1) int64: exclusive cumulative sum of the class sizes, class_start[C] = N.  The sizes are read on
+ *   the device only; the launch geometry depends on C and D alone.  N = 0 is valid (every class empty).
+ *   means_out (C,D), cov_out (C,D,D), second_out (C,D,D) or NULL: dtype.
+ *   estimator  SQFA_COV_EMPIRICAL  cov = sum (x - mu)(x - mu)^T / (n_c - 1), second = cov + mu mu^T from the same registers
+ *              SQFA_COV_OAS        the same shrunk towards tr/D I (Chen et al. 2010, rho clamped at 1; statistics.py:57-94)
+ *              SQFA_COV_SCATTER    cov_out = the raw centred sum, no division; second_out is not written
+ *   An empty class gives NaN means and NaN matrices, a class of one point a finite mean and a NaN covariance (0/0), as
+ *   the reference's expressions do.  Rows are centred in the dtype, the means are summed in double.
+ * One workgroup per (class, 64 x 64 tile of the lower block triangle); an off-diagonal tile is stored as computed and
+ * transposed, so every (D,D) output is EXACTLY symmetric.  No split over rows, no atomics, every sum in a fixed order:
+ * results are bitwise reproducible.  Nothing is allocated, synchronised or read back; capturable in a HIP graph.
+ *   workspace: sqfa_class_moments_workspace_bytes(C, D, dtype) bytes for any of the three calls (0 = not supported:
+ *   dtype, C < 1, D < 1, C > 65535, or more than 2^31 - 1 (class, tile) workgroups).
+ *
+ * sqfa_class_moments_update: the batched merge of Chan, Golub and LeVeque.  counts (C) FLOAT64, means (C,D) and
+ *   m2 (C,D,D) dtype are the running state, read and written (start from zeros).  With mu_b, M2_b the mean and centred
+ *   sum of the batch's rows of a class (computed as above), delta = mu_b - means and n = counts + n_b:
+ *       m2 += M2_b + (counts n_b / n) delta delta^T;   means += delta n_b / n;   counts = n
+ *   (counts = 0: means = mu_b, m2 += M2_b).  A class with no row in the batch is left untouched, bit for bit.  No raw
+ *   second moments are formed anywhere (sum x x^T - n mu mu^T cancels in float32).  m2 stays exactly symmetric.
+ * sqfa_class_moments_finalize: statistics from such a state: cov_out = m2 / (counts - 1) (SQFA_COV_EMPIRICAL) or its OAS
+ *   shrinkage (SQFA_COV_OAS), second_out (or NULL) = cov + means means^T; counts < 1 gives NaN matrices.
+ * Return SQFA_ERR_BAD_ARGUMENT (null pointers -- points may be NULL only when N = 0 --, N < 0, C < 1, D < 1, dtype,
+ * estimator), SQFA_ERR_UNSUPPORTED_M (the grid limits above), SQFA_ERR_WORKSPACE; every check runs before the first HIP call.
+ */
+#define SQFA_COV_EMPIRICAL 0
+#define SQFA_COV_OAS       1
+#define SQFA_COV_SCATTER   2
+size_t sqfa_class_moments_workspace_bytes(int C, int D, int dtype);
+int sqfa_class_moments(const void *points, long long N, int D, const long long *row_index,
+                       const long long *class_start, int C, int dtype, int estimator,
+                       void *means_out, void *cov_out, void *second_out,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_class_moments_update(const void *points, long long N, int D, const long long *row_index,
+                              const long long *class_start, int C, int dtype,
+                              double *counts, void *means, void *m2,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_class_moments_finalize(const double *counts, const void *means, const void *m2, int C, int D, int dtype,
+                                int estimator, void *cov_out, void *second_out,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 /* Introspection (benchmarks / development; not needed by a reference-side binding).
  *
  * sqfa_airm_profile(1): every following sqfa_airm_pairwise call brackets its pair tile kernel

@@ -582,6 +582,77 @@ def spd_function(M, kind):
 
 
 # ------------------------------------------------------------------------------------------
+# class statistics from labelled points (class_moments_kernel.hip)
+
+COV_EMPIRICAL, COV_OAS, COV_SCATTER = 0, 1, 2
+
+
+def class_moments_supported(points):
+    return points.is_cuda and points.dim() == 2 and points.dtype in (torch.float32, torch.float64) and points.shape[1] >= 1
+
+
+def grouped_rows(labels, n_classes):
+    """(order, class_start) of integer labels on their device: the indices of a stable sort and the exclusive cumulative
+    class sizes (C+1, int64) -- what sqfa_class_moments gathers rows by.  No host read."""
+    order = torch.sort(labels, stable=True).indices
+    class_start = torch.zeros(n_classes + 1, dtype=torch.int64, device=labels.device)
+    class_start[1:] = torch.cumsum(torch.bincount(labels, minlength=n_classes), 0)
+    return order, class_start
+
+
+def class_moments(points, order, class_start, C, estimator, want_second=True):
+    """sqfa_class_moments on the current stream: (means (C,D), covariances (C,D,D), second moments or None) of the rows
+    `points[order]` grouped by `class_start` (order None: already grouped).  estimator: COV_EMPIRICAL / COV_OAS / COV_SCATTER."""
+    lib = _lib.load()
+    if not class_moments_supported(points):
+        raise RuntimeError("sqfa_amd's class statistics kernels take (N, D) float32 / float64 points on the GPU")
+    points = points.detach().contiguous()
+    N, D = points.shape
+    code = _dtype_code(points)
+    dev, dt = points.device, points.dtype
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(lib.sqfa_class_moments_workspace_bytes, C, D, code)
+        means = torch.empty((C, D), dtype=dt, device=dev)
+        cov = torch.empty((C, D, D), dtype=dt, device=dev)
+        second = torch.empty((C, D, D), dtype=dt, device=dev) if want_second and estimator != COV_SCATTER else None
+        _lib.check(lib.sqfa_class_moments(_ptr(points), N, D, _ptr(order), _ptr(class_start), C, code, int(estimator),
+                                          _ptr(means), _ptr(cov), _ptr(second), _ptr(ws), nbytes, stream),
+                   "sqfa_class_moments")
+    return means, cov, second
+
+
+def class_moments_update(points, order, class_start, C, counts, means, m2):
+    """sqfa_class_moments_update on the current stream: merges the batch `points[order]` grouped by `class_start` into the
+    running counts (C, float64), means (C,D) and m2 (C,D,D), in place."""
+    lib = _lib.load()
+    if not class_moments_supported(points) or points.dtype != means.dtype:
+        raise RuntimeError("sqfa_amd's class statistics kernels take (N, D) float32 / float64 points on the GPU")
+    points = points.detach().contiguous()
+    N, D = points.shape
+    code = _dtype_code(points)
+    with _on_stream(points.device) as stream:
+        ws, nbytes = _workspace(lib.sqfa_class_moments_workspace_bytes, C, D, code)
+        _lib.check(lib.sqfa_class_moments_update(_ptr(points), N, D, _ptr(order), _ptr(class_start), C, code,
+                                                 _ptr(counts), _ptr(means), _ptr(m2), _ptr(ws), nbytes, stream),
+                   "sqfa_class_moments_update")
+
+
+def class_moments_finalize(counts, means, m2, estimator, want_second=True):
+    """sqfa_class_moments_finalize: (covariances, second moments or None) from an accumulator's state."""
+    lib = _lib.load()
+    C, D = means.shape
+    code = _dtype_code(means)
+    with _on_stream(means.device) as stream:
+        ws, nbytes = _workspace(lib.sqfa_class_moments_workspace_bytes, C, D, code)
+        cov = torch.empty_like(m2)
+        second = torch.empty_like(m2) if want_second else None
+        _lib.check(lib.sqfa_class_moments_finalize(_ptr(counts), _ptr(means), _ptr(m2), C, D, code, int(estimator),
+                                                   _ptr(cov), _ptr(second), _ptr(ws), nbytes, stream),
+                   "sqfa_class_moments_finalize")
+    return cov, second
+
+
+# ------------------------------------------------------------------------------------------
 # projection of the class scatter matrices (the HBM-bound stage around the pair kernel)
 
 

@@ -1,11 +1,17 @@
 """Class statistics and PCA initialisation (reference: src/sqfa/statistics.py).
 
-Runs once per fit, before the hot path; stays in PyTorch-ROCm as BASELINE.json's north_star
-prescribes, but allocates on the input's device (the reference allocates on the CPU only).
+Runs once per fit, before the hot path, on the input's device (the reference allocates on the CPU only).
+float32 / float64 points on the GPU go through the native segmented SYRK (sqfa_class_moments: no sorted or padded
+copy of the points, exactly symmetric outputs); CPU tensors and other dtypes keep the batched torch expression.
+ClassStatisticsAccumulator builds the same statistics from batches and merges partial results.
 """
 import torch
 
-__all__ = ["class_statistics", "oas_covariance", "sample_covariance", "pca", "pca_from_scatter"]
+__all__ = ["class_statistics", "ClassStatisticsAccumulator", "oas_covariance", "sample_covariance", "pca",
+           "pca_from_scatter"]
+
+# float32 / float64 points on the GPU take the native kernels; False keeps the batched torch expression everywhere
+NATIVE_CLASS_STATISTICS = True
 
 
 def __dir__():
@@ -52,6 +58,13 @@ def class_statistics(points, labels, estimator="empirical"):
         raise ValueError("estimator must be 'empirical' or 'oas'")
     labels = labels.to(points.device).long()   # the reference accepts float labels too (it compares with ==)
     n_classes = int(labels.max()) + 1
+    if NATIVE_CLASS_STATISTICS and _native_applies(points):
+        # the class count above is the only host read: sizes and offsets stay on the device
+        from . import _native
+        order, class_start = _native.grouped_rows(labels, n_classes)
+        code = _native.COV_OAS if estimator == "oas" else _native.COV_EMPIRICAL
+        means, covs, second = _native.class_moments(points, order, class_start, n_classes, code, True)
+        return {"means": means, "covariances": covs, "second_moments": second}
     d = points.shape[-1]
     order = torch.sort(labels, stable=True).indices
     counts_dev = torch.bincount(labels, minlength=n_classes)
@@ -78,6 +91,116 @@ def class_statistics(points, labels, estimator="empirical"):
         covs[cls] = c
     second = covs + means[:, :, None] * means[:, None, :]
     return {"means": means, "covariances": covs, "second_moments": second}
+
+
+def _native_applies(points):
+    return points.is_cuda and points.dim() == 2 and points.dtype in (torch.float32, torch.float64) and points.shape[1] >= 1
+
+
+def _oas_shrink(S, n):
+    """Batched OAS shrinkage of (G,D,D) sample covariances of n (G) points each (Chen et al. 2010, as oas_covariance)."""
+    d = S.shape[-1]
+    tr = torch.diagonal(S, dim1=1, dim2=2).sum(dim=1)
+    tr2 = (S * S).sum(dim=(1, 2))
+    rho = ((1 - 2 / d) * tr2 + tr * tr) / ((n + 1 - 2 / d) * (tr2 - tr * tr / d))
+    rho = torch.clamp(rho, max=1.0)
+    eye = torch.eye(d, dtype=S.dtype, device=S.device)
+    return (1 - rho)[:, None, None] * S + (rho * tr / d)[:, None, None] * eye
+
+
+class ClassStatisticsAccumulator:
+    """Class statistics built from batches: running count, mean and centred sum M2 = sum (x - mu)(x - mu)^T per class,
+    merged batch by batch with the pairwise update of Chan, Golub and LeVeque (no raw second moments: sum x x^T - n mu mu^T
+    cancels in float32).  ``update`` is native on the GPU (sqfa_class_moments_update) and the same formulas in torch on the
+    CPU; ``merge`` joins the partial statistics of several loaders or ranks; ``finalize`` returns what
+    ``class_statistics`` returns, and after one ``update`` with all the data equals it to rounding."""
+
+    def __init__(self, n_classes, n_dim, dtype=torch.float32, device=None):
+        if n_classes < 1 or n_dim < 1:
+            raise ValueError("n_classes and n_dim must be positive")
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError("ClassStatisticsAccumulator supports float32 and float64")
+        self.n_classes, self.n_dim, self.dtype = int(n_classes), int(n_dim), dtype
+        self.device = torch.device("cpu" if device is None else device)
+        self._counts = torch.zeros(self.n_classes, dtype=torch.float64, device=self.device)
+        self._means = torch.zeros(self.n_classes, self.n_dim, dtype=dtype, device=self.device)
+        self._m2 = torch.zeros(self.n_classes, self.n_dim, self.n_dim, dtype=dtype, device=self.device)
+
+    @property
+    def counts(self):
+        """Points seen per class (int64)."""
+        return self._counts.round().long()
+
+    def update(self, points, labels):
+        """Merge a batch: points (n, n_dim), labels (n) in 0..n_classes-1 (float labels accepted, as class_statistics)."""
+        points = points.to(device=self.device, dtype=self.dtype)
+        labels = labels.to(self.device).long()
+        if points.dim() != 2 or points.shape[1] != self.n_dim or labels.shape != points.shape[:1]:
+            raise ValueError("points must be (n, n_dim) and labels (n)")
+        if labels.numel() == 0:
+            return self
+        if int(labels.min()) < 0 or int(labels.max()) >= self.n_classes:
+            raise ValueError(f"labels must lie in 0..{self.n_classes - 1}")
+        if points.is_cuda:
+            from . import _native
+            order, class_start = _native.grouped_rows(labels, self.n_classes)
+            _native.class_moments_update(points, order, class_start, self.n_classes, self._counts, self._means, self._m2)
+            return self
+        order = torch.sort(labels, stable=True).indices
+        present, sizes = torch.unique_consecutive(labels[order], return_counts=True)
+        pos = 0
+        for c, n_b in zip(present.tolist(), sizes.tolist()):
+            rows = points[order[pos:pos + n_b]]
+            pos += n_b
+            mean_b = rows.double().sum(dim=0).div(n_b).to(self.dtype)
+            centred = rows - mean_b
+            self._merge_class(c, float(n_b), mean_b, centred.T @ centred)
+        return self
+
+    def _merge_class(self, c, n_b, mean_b, m2_b):
+        n_a = float(self._counts[c])
+        if n_a == 0:
+            self._means[c] = mean_b
+            self._m2[c] += m2_b
+        else:
+            delta = mean_b - self._means[c]
+            self._m2[c] += m2_b + (n_a * n_b / (n_a + n_b)) * (delta[:, None] * delta[None, :])
+            self._means[c] += delta * (n_b / (n_a + n_b))
+        self._counts[c] = n_a + n_b
+
+    def merge(self, other):
+        """Merge another accumulator's statistics into this one (elementwise over the classes)."""
+        if (other.n_classes, other.n_dim, other.dtype) != (self.n_classes, self.n_dim, self.dtype):
+            raise ValueError("accumulators must agree in n_classes, n_dim and dtype")
+        n_a, n_b = self._counts, other._counts.to(self.device)
+        mean_b, m2_b = other._means.to(self.device), other._m2.to(self.device)
+        n = n_a + n_b
+        safe = n.clamp(min=1.0)
+        delta = torch.where((n_a > 0)[:, None], mean_b - self._means, torch.zeros_like(mean_b))
+        w = (n_a * n_b / safe).to(self.dtype)
+        self._m2 += m2_b + w[:, None, None] * (delta[:, :, None] * delta[:, None, :])
+        moved = self._means + delta * (n_b / safe).to(self.dtype)[:, None]
+        self._means = torch.where((n_b > 0)[:, None], torch.where((n_a > 0)[:, None], moved, mean_b), self._means)
+        self._counts = n
+        return self
+
+    def finalize(self, estimator="empirical"):
+        """{'means', 'covariances', 'second_moments'} as class_statistics returns them; a class never seen gives NaN."""
+        if estimator not in ("empirical", "oas"):
+            raise ValueError("estimator must be 'empirical' or 'oas'")
+        nan = torch.full((), float("nan"), dtype=self.dtype, device=self.device)
+        means = torch.where((self._counts > 0)[:, None], self._means, nan)
+        if self._m2.is_cuda:
+            from . import _native
+            code = _native.COV_OAS if estimator == "oas" else _native.COV_EMPIRICAL
+            covs, second = _native.class_moments_finalize(self._counts, means, self._m2, code, True)
+            return {"means": means, "covariances": covs, "second_moments": second}
+        n = self._counts.to(self.dtype)
+        covs = torch.where((self._counts > 0)[:, None, None], self._m2 / (n - 1)[:, None, None], nan)
+        if estimator == "oas":
+            covs = _oas_shrink(covs, n)
+        second = covs + means[:, :, None] * means[:, None, :]
+        return {"means": means, "covariances": covs, "second_moments": second}
 
 
 def _batched_moments(sorted_points, starts, counts, n_max, estimator):

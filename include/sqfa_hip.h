@@ -514,6 +514,53 @@ int sqfa_class_moments_finalize(const double *counts, const void *means, const v
                                 int estimator, void *cov_out, void *second_out,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Feature moments from labelled points, with nothing of size (C,D,D): per closure evaluation they replace the class
+ * statistics of the reference (src/sqfa/statistics.py:8-124) followed by transform_scatters (src/sqfa/model.py:172-188,
+ * conjugate_matrix src/sqfa/linalg.py:19-45), through  F cov_c F^T = cov(F x | c)  and  F mu_c = mean(F x | c)
+ * (empirical estimator).  points, row_index, class_start as for sqfa_class_moments; any D >= 1 (16-byte loads where
+ * D % (16 / element size) == 0 and points, means and F are 16-byte aligned, one element per load otherwise: the same bits).
+ *   sqfa_class_means   means_out (C,D) alone: the kernel sqfa_class_moments runs (sums in double), the same bits as its
+ *                      means_out; an empty class gives NaN.  C <= 65535 (SQFA_ERR_UNSUPPORTED_M).
+ *   row_class (N) int64: the class of GROUPED row g, i.e. the sorted labels (labels[row_index]); values in 0..C-1.
+ *   sqfa_class_feature_moments   F (K,D), K <= 64.  Outputs, all in the dtype:
+ *       zc_out (N,K)       F (x - mu_class), the row centred in D-space in the dtype BEFORE the product, in GROUPED order
+ *                          (row g belongs to points[row_index[g]]); kept by the caller for the backward call
+ *       means_f_out (C,K)  F mu_c
+ *       cov_f_out (C,K,K)  sum_{i in c} zc_i zc_i^T / (n_c - 1), plus `noise` on the diagonal
+ *       second_f_out (C,K,K) or NULL   cov_f_out + means_f means_f^T
+ *     Both matrices equal their transposes bit for bit.  An empty class gives NaN means and matrices, a class of one point
+ *     a finite mean and NaN matrices, as sqfa_class_moments.
+ *   sqfa_class_feature_moments_backward   G (C, ldg, ldg block, top-left K x K used, row pitch ldg; NOT assumed symmetric)
+ *     = dL/dcov_f, g_means (C,K) or NULL = dL/dmeans_f (a caller that used second_f folds its gradient G2 in first:
+ *     G += G2, g_means += (G2 + G2^T) means_f).  With w_i = (G_c + G_c^T) zc_i / (n_c - 1):
+ *         dL/dF = sum_i w_i (x_i - mu_class)^T + sum_c g_c mu_c^T = sum_p partial_out[p]
+ *     partial_out (n_groups,K,D), 1 <= n_groups <= 65535: the layout sqfa_feature_scatters_backward writes and
+ *     sqfa_sphere_backward sums.  The mean term IS folded in here (its rows are shared out over the groups like the
+ *     points); the sum over the groups is left to the caller.  Classes with n_c < 2 contribute nothing through G, empty
+ *     classes nothing through g_means (NaN entries of G, g_means or means there are never read into the result).
+ *   workspace: sqfa_class_feature_moments_workspace_bytes(N, C, D, K, dtype) bytes for either call (0 = not supported:
+ *   dtype, N < 0, C < 1, D < 1, K < 1, K > 64, C > 65535, or a grid beyond 2^31 - 1 workgroups).
+ * Class sizes are read on the device only; every grid is a function of (N, C, D, K, n_groups); no atomics, every sum in
+ * a fixed order (bitwise reproducible); nothing is allocated, synchronised or read back; capturable in a HIP graph.
+ * Return SQFA_ERR_BAD_ARGUMENT (null pointers -- points, row_class and zc may be NULL only when N = 0 --, N < 0, C < 1,
+ * D < 1, K < 1, dtype, ldg < K, n_groups), SQFA_ERR_UNSUPPORTED_M (K > 64 and the limits above), SQFA_ERR_WORKSPACE, in
+ * this order; every check runs before the first HIP call.
+ */
+int sqfa_class_means(const void *points, long long N, int D, const long long *row_index,
+                     const long long *class_start, int C, int dtype, void *means_out, void *stream);
+size_t sqfa_class_feature_moments_workspace_bytes(long long N, int C, int D, int K, int dtype);
+int sqfa_class_feature_moments(const void *points, long long N, int D, const long long *row_index,
+                               const long long *row_class, const long long *class_start, int C,
+                               const void *means, const void *F, int K, int dtype, double noise,
+                               void *zc_out, void *means_f_out, void *cov_f_out, void *second_f_out,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_class_feature_moments_backward(const void *points, long long N, int D, const long long *row_index,
+                                        const long long *row_class, const long long *class_start, int C,
+                                        const void *means, const void *zc, const void *G, int ldg,
+                                        const void *g_means, int K, int dtype, int n_groups, void *partial_out,
+                                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* Introspection (benchmarks / development; not needed by a reference-side binding).
  *
  * sqfa_airm_profile(1): every following sqfa_airm_pairwise call brackets its pair tile kernel

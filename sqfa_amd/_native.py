@@ -653,6 +653,115 @@ def class_moments_finalize(counts, means, m2, estimator, want_second=True):
 
 
 # ------------------------------------------------------------------------------------------
+# feature moments straight from the labelled points (class_points_kernel.hip): nothing of size (C,D,D)
+
+POINT_MAX_FILTERS = 64
+
+
+def class_means(points, order, class_start, C):
+    """sqfa_class_means on the current stream: the (C,D) class means of `points[order]` grouped by `class_start`, the same
+    bits as class_moments' means."""
+    lib = _lib.load()
+    if not class_moments_supported(points) or not points.is_contiguous():
+        raise RuntimeError("sqfa_amd's class statistics kernels take contiguous (N, D) float32 / float64 points on the GPU")
+    N, D = points.shape
+    with _on_stream(points.device) as stream:
+        means = torch.empty((C, D), dtype=points.dtype, device=points.device)
+        _lib.check(lib.sqfa_class_means(_ptr(points), N, D, _ptr(order), _ptr(class_start), C, _dtype_code(points),
+                                        _ptr(means), stream), "sqfa_class_means")
+    return means
+
+
+def class_feature_moments_supported(points, filters):
+    """Contiguous float32 / float64 (N,D) points on the GPU and (K,D) filters of the same dtype and device, K <= 64."""
+    return bool(class_moments_supported(points) and points.is_contiguous() and filters.dim() == 2
+                and filters.device == points.device and filters.dtype == points.dtype
+                and filters.shape[1] == points.shape[1] and 1 <= filters.shape[0] <= POINT_MAX_FILTERS)
+
+
+def point_backward_groups(N, D):
+    """Row groups of sqfa_class_feature_moments_backward: groups x 64-column stripes of ~1024 workgroups (four per CU), at
+    most 64 groups (the (groups, K, D) partial sums are read again by the sum over the groups) and no group below one
+    chunk of 32 rows."""
+    stripes = (D + 63) // 64
+    return max(1, min(64, -(-1024 // stripes), -(-max(N, 1) // 32)))
+
+
+def class_feature_moments(cp, F, second_moments, noise):
+    """sqfa_class_feature_moments on the current stream for a statistics.ClassPoints `cp` and contiguous filters F (K,D):
+    (zc (N,K) in grouped order, means_f (C,K), cov_f (C,K,K), second_f (C,K,K) or None)."""
+    lib = _lib.load()
+    X = cp.points
+    N, D = X.shape
+    K, C = F.shape[0], cp.n_classes
+    code = _dtype_code(X)
+    dev, dt = X.device, X.dtype
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(lib.sqfa_class_feature_moments_workspace_bytes, N, C, D, K, code)
+        zc = torch.empty((N, K), dtype=dt, device=dev)
+        means_f = torch.empty((C, K), dtype=dt, device=dev)
+        cov_f = torch.empty((C, K, K), dtype=dt, device=dev)
+        second_f = torch.empty((C, K, K), dtype=dt, device=dev) if second_moments else None
+        _lib.check(lib.sqfa_class_feature_moments(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class), _ptr(cp.class_start), C,
+                                                  _ptr(cp.means), _ptr(F), K, code, float(noise), _ptr(zc), _ptr(means_f),
+                                                  _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream),
+                   "sqfa_class_feature_moments")
+    return zc, means_f, cov_f, second_f
+
+
+def class_feature_moments_backward(cp, zc, G, g_means):
+    """sqfa_class_feature_moments_backward on the current stream: the (n_groups, K, D) partial sums of dL/dF for
+    G = dL/dcov_f (C,K,K) and g_means = dL/dmeans_f (C,K) or None."""
+    lib = _lib.load()
+    X = cp.points
+    N, D = X.shape
+    K, C = zc.shape[1], cp.n_classes
+    code = _dtype_code(X)
+    G = G.detach().contiguous()
+    g_means = g_means.detach().contiguous() if g_means is not None else None
+    groups = point_backward_groups(N, D)
+    with _on_stream(X.device) as stream:
+        ws, nbytes = _workspace(lib.sqfa_class_feature_moments_workspace_bytes, N, C, D, K, code)
+        partial = torch.empty((groups, K, D), dtype=X.dtype, device=X.device)
+        _lib.check(lib.sqfa_class_feature_moments_backward(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
+                                                           _ptr(cp.class_start), C, _ptr(cp.means), _ptr(zc), _ptr(G), K,
+                                                           _ptr(g_means), K, code, groups, _ptr(partial), _ptr(ws), nbytes,
+                                                           stream), "sqfa_class_feature_moments_backward")
+    return partial
+
+
+class ClassFeatureMoments(torch.autograd.Function):
+    """(means_f (C,K), cov_f (C,K,K)[, second_f (C,K,K)]) of the projected points F x, per class, from a
+    statistics.ClassPoints: F mu_c, cov(F x | c) (+ noise on the diagonal) and their second moment, equal to F mu_c,
+    F cov_c F^T and F (cov_c + mu_c mu_c^T) F^T of the dense statistics without forming them (replaces class_statistics
+    + transform_scatters of the reference, src/sqfa/statistics.py:8-124, src/sqfa/model.py:172-188).  The backward
+    returns dL/dF only; it needs the centred features (N,K) and the points, read once more."""
+
+    @staticmethod
+    def forward(ctx, filters, class_points, second_moments, noise):
+        F = filters.detach().contiguous()
+        zc, means_f, cov_f, second_f = class_feature_moments(class_points, F, second_moments, noise)
+        ctx.save_for_backward(zc, means_f)
+        ctx.class_points = class_points
+        ctx.second = bool(second_moments)
+        return (means_f, cov_f, second_f) if second_moments else (means_f, cov_f)
+
+    @staticmethod
+    def backward(ctx, g_means, g_cov, g_second=None):
+        zc, means_f = ctx.saved_tensors
+        G = g_cov
+        if ctx.second:
+            # second = cov + m m^T: its gradient goes to the covariance as it is and to the means through the product
+            # (elementwise, not a batched GEMM: a first BLAS call inside a graph capture allocates its own workspace of
+            # tens of MB in the graph's pool)
+            G = G + g_second
+            sym = g_second + g_second.transpose(1, 2)
+            g_means = g_means + (sym * means_f.unsqueeze(1)).sum(dim=-1)
+        partial = class_feature_moments_backward(ctx.class_points, zc, G, g_means)
+        return partial.sum(dim=0), None, None, None
+
+
+# ------------------------------------------------------------------------------------------
 # projection of the class scatter matrices (the HBM-bound stage around the pair kernel)
 
 

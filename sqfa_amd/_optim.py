@@ -169,6 +169,8 @@ class GraphRunner:
 
 
 def _n_classes(data_statistics):
+    if hasattr(data_statistics, "n_classes"):   # statistics.ClassPoints
+        return data_statistics.n_classes
     if isinstance(data_statistics, dict):
         return data_statistics["means"].shape[0]
     return data_statistics.shape[0]

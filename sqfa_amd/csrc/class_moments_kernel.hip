@@ -524,6 +524,25 @@ extern "C" int sqfa_class_moments(const void* points, long long N, int D, const 
   return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }
 
+// the means alone (class_mean_kernel as sqfa_class_moments launches it: the same bits)
+extern "C" int sqfa_class_means(const void* points, long long N, int D, const long long* row_index,
+                                const long long* class_start, int C, int dtype, void* means_out, void* stream_) {
+  using namespace sqfa;
+  if (N < 0 || C < 1 || D < 1 || (points == nullptr && N > 0) || class_start == nullptr || means_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  if (C > 65535) return SQFA_ERR_UNSUPPORTED_M;   // classes in grid.y
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const dim3 grid((D + CM_MEAN_COLS - 1) / CM_MEAN_COLS, C);
+  if (dtype == SQFA_F32)
+    class_mean_kernel<float><<<grid, CM_THREADS, 0, stream>>>(static_cast<const float*>(points), D, row_index, class_start,
+                                                              static_cast<float*>(means_out));
+  else
+    class_mean_kernel<double><<<grid, CM_THREADS, 0, stream>>>(static_cast<const double*>(points), D, row_index, class_start,
+                                                               static_cast<double*>(means_out));
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
 extern "C" int sqfa_class_moments_update(const void* points, long long N, int D, const long long* row_index,
                                          const long long* class_start, int C, int dtype, double* counts, void* means,
                                          void* m2, void* workspace, size_t workspace_bytes, void* stream_) {

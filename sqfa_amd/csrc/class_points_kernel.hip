@@ -1,0 +1,545 @@
+// class_points_kernel.hip -- the class moments of the PROJECTED points, straight from the labelled points: what a
+// closure needs of class_statistics (reference src/sqfa/statistics.py:8-124) followed by F cov_c F^T / F mu_c
+// (transform_scatters, src/sqfa/model.py:172-188; conjugate_matrix, src/sqfa/linalg.py:19-45) without any (C,D,D)
+// tensor:  F cov_c F^T = cov(F x | c),  F mu_c = mean(F x | c).  X is read once forward and once backward.
+//
+//   points (N,D) row-major; row_index (N) int64 or NULL and class_start (C+1) int64 as in class_moments_kernel.hip;
+//   row_class (N) int64: the class of GROUPED row g (the sorted labels); means (C,D): sqfa_class_means.
+//   zc (N,K): the centred features F (x - mu_class) in GROUPED order (row g belongs to points[row_index[g]]).
+//
+// Launches (caller's stream; nothing allocated, synchronised or read back; no atomics, every sum in a fixed order, every
+// output element one writer: bitwise reproducible; every grid a function of (N, C, D, K) and n_groups alone):
+//   class_project_kernel     A: one workgroup (4 waves) per 64 grouped rows.  Chunks of DC columns (64 float / 32 double)
+//                            of x - mu (centred in the dtype BEFORE the product, the mean row of each row's own class)
+//                            and of F are staged in LDS as [row][col]; wave w accumulates rows 16w..16w+15 x K on the exact
+//                            MFMA (A[i][k] = xc[i][k], B[k][j] = F[j][k]); the next chunk's global loads are in flight
+//                            during the MFMAs.  Pitch DC + 2: see CP_PITCH_A.
+//   class_gram_kernel        B1: workgroup (class, split s): the raw Gram sum z z^T of the s-th share of the class's rows,
+//                            16 x 16 tiles of the LOWER block triangle only, each written as computed and mirrored
+//   class_feature_finish_kernel  B2: per class m = F mu (lane-strided sums, fixed shuffle tree), S = sum_s partial_s / (n - 1)
+//                            in the order s = 0, 1, ..., noise on the diagonal, second = S + m m^T.  (i,j) and (j,i) are the
+//                            same product chain, so S and second equal their transposes bit for bit.
+//   class_weights_kernel     C: w_g = (G_c + G_c^T) z_g / (n_c - 1) per grouped row (zeros for n_c < 2), and, when the
+//                            gradient of the feature means is given, C more "virtual rows" w_{N+c} = g_c (zeros for an
+//                            empty class) whose point is the class mean itself
+//   class_backward_kernel    D: workgroup (64-column stripe q, group p): sum over the virtual rows of group p of
+//                            w_v (x_v - mu)^T (virtual rows >= N: w_v mu_c^T), 32 rows per chunk staged as [row][col],
+//                            A[i][k] = w[k][i], B[k][j] = xc[k][j]; writes partial[p] (K, stripe).  The sum over p is the
+//                            caller's (partial.sum(0) or sqfa_sphere_backward), as for sqfa_feature_scatters_backward.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+
+#include "../../include/sqfa_hip.h"
+#include "proj_traits.hpp"
+
+namespace sqfa {
+
+constexpr int CP_THREADS = 256;
+constexpr int CP_KMAX = 64;        // filters
+constexpr int CP_ROWS = 64;        // B: grouped rows per workgroup of kernel A
+constexpr int CP_CHUNK = 32;       // rows per chunk of kernel D
+constexpr int CP_STRIPE = 64;      // columns per workgroup of kernel D
+constexpr int CP_GRAM_ROWS = 64;   // rows per chunk of kernel B1
+constexpr int CP_MAX_SPLIT = 32;
+// Tiles read with the ROW on the lane (kernel A: address (l & 15) * pitch + k + (l >> 4)): the 32 lanes of one LDS lane
+// group are rows 0..15 x two consecutive k.  With pitch = 2 mod 32 elements they fall on banks 2 i + q (float) or on the
+// bank pairs 4 i + 2 q, + 1 of the 64 (double, ds_read_b64): all distinct.
+template <typename T> struct CpA {
+  static constexpr int DC = 256 / (int)sizeof(T);   // columns per chunk: 64 float, 32 double
+  static constexpr int PITCH = DC + 2;
+};
+// Tiles read with the COLUMN on the lane (kernels B1, D: address (k + (l >> 4)) * pitch + (l & 15)): rows k and k + 1 of
+// one lane group must land on disjoint halves of the banks: pitch = 16 mod 32 elements, as class_moments_kernel.hip.
+constexpr int CP_PITCH = 80;
+
+__device__ __forceinline__ size_t cp_row(const long long* __restrict__ row_index, long long g) {
+  return (size_t)(row_index != nullptr ? row_index[g] : g);
+}
+
+// A ROWS x COLS tile of rows given by pointer (sX[r], NULL = a row of zeros) minus, when CENTRE, the rows sM[r] (NULL = no
+// centring), through registers into LDS as [row][col].  VEC: 16-byte loads (D % VW == 0, aligned bases); otherwise one
+// element per load; the LDS image is the same.  Only the first rows_used rows (a multiple of RPP or more) are touched.
+template <typename T, bool VEC, int ROWS, int COLS, int PITCH, bool CENTRE> struct TileLoad {
+  using Tr = ProjTraits<T>;
+  static constexpr int VW = VEC ? Tr::VW : 1;
+  static constexpr int LPR = COLS / VW;              // threads across one row
+  static constexpr int RPP = CP_THREADS / LPR;       // rows per pass
+  static constexpr int PASSES = ROWS / RPP;
+  static constexpr int PER = PASSES * VW;
+  static_assert(CP_THREADS % LPR == 0 && ROWS % RPP == 0 && PASSES >= 1, "tile shape");
+  T x[PER], m[CENTRE ? PER : 1];
+
+  __device__ __forceinline__ void load(const T* const* sX, const T* const* sM, int D, int c0, int rows_used) {
+    const int col = c0 + (threadIdx.x % LPR) * VW, r0 = threadIdx.x / LPR;
+    const bool in = col < D;   // VEC: D % VW == 0, so a vector is inside or outside as a whole
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      if (p * RPP < rows_used) {
+        const int r = r0 + p * RPP;
+        const T* xp = in ? sX[r] : nullptr;
+        const T* mp = nullptr;
+        if constexpr (CENTRE) mp = in ? sM[r] : nullptr;
+        if constexpr (VEC) {
+          typename Tr::Vec xv = {}, mv = {};
+          if (xp != nullptr) xv = *reinterpret_cast<const typename Tr::Vec*>(xp + col);
+          if (mp != nullptr) mv = *reinterpret_cast<const typename Tr::Vec*>(mp + col);
+#pragma unroll
+          for (int e = 0; e < VW; ++e) {
+            x[p * VW + e] = xv[e];
+            if constexpr (CENTRE) m[p * VW + e] = mv[e];
+          }
+        } else {
+          x[p] = xp != nullptr ? xp[col] : (T)0;
+          if constexpr (CENTRE) m[p] = mp != nullptr ? mp[col] : (T)0;
+        }
+      }
+    }
+  }
+
+  // centred in the dtype; rows without a pointer and columns past D are exact zeros
+  __device__ __forceinline__ void store(T* s, int rows_used) const {
+    const int lc = (threadIdx.x % LPR) * VW, r0 = threadIdx.x / LPR;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      if (p * RPP < rows_used) {
+        const int r = r0 + p * RPP;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+          if constexpr (CENTRE)
+            s[r * PITCH + lc + e] = x[p * VW + e] - m[p * VW + e];
+          else
+            s[r * PITCH + lc + e] = x[p * VW + e];
+        }
+      }
+    }
+  }
+};
+
+// ---- A: zc = (x - mu_class) F^T ------------------------------------------------------------------------------------------
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(CP_THREADS) void class_project_kernel(const T* __restrict__ points, long long N, int D,
+                                                                   const long long* __restrict__ row_index,
+                                                                   const long long* __restrict__ row_class,
+                                                                   const T* __restrict__ means, const T* __restrict__ F,
+                                                                   int K, T* __restrict__ zc) {
+  using Tr = ProjTraits<T>;
+  constexpr int DC = CpA<T>::DC, PA = CpA<T>::PITCH;
+  __shared__ T sXt[CP_ROWS * PA], sFt[CP_KMAX * PA];
+  __shared__ const T* sXp[CP_ROWS];
+  __shared__ const T* sMp[CP_ROWS];
+  __shared__ const T* sFp[CP_KMAX];
+  const int tid = threadIdx.x, l = tid & 63, wave = tid >> 6, q = l >> 4;
+  const long long g0 = (long long)blockIdx.x * CP_ROWS;
+  const int KB = (K + 15) / 16, frows = KB * 16;
+  if (tid < CP_ROWS) {
+    const long long g = g0 + tid;
+    const T* xp = nullptr;
+    const T* mp = nullptr;
+    if (g < N) {
+      xp = points + cp_row(row_index, g) * (size_t)D;
+      mp = means + (size_t)row_class[g] * D;
+    }
+    sXp[tid] = xp;
+    sMp[tid] = mp;
+    sFp[tid] = tid < K ? F + (size_t)tid * D : nullptr;
+  }
+  __syncthreads();
+  TileLoad<T, VEC, CP_ROWS, DC, PA, true> ldX;
+  TileLoad<T, VEC, CP_KMAX, DC, PA, false> ldF;
+  typename Tr::Acc acc[4] = {};
+  ldX.load(sXp, sMp, D, 0, CP_ROWS);
+  ldF.load(sFp, nullptr, D, 0, frows);
+  for (int c0 = 0; c0 < D; c0 += DC) {
+    __syncthreads();   // the previous chunk has been consumed
+    ldX.store(sXt, CP_ROWS);
+    ldF.store(sFt, frows);
+    __syncthreads();
+    if (c0 + DC < D) {
+      ldX.load(sXp, sMp, D, c0 + DC, CP_ROWS);
+      ldF.load(sFp, nullptr, D, c0 + DC, frows);
+    }
+#pragma unroll
+    for (int kk = 0; kk < DC; kk += 4) {
+      const T a = sXt[(wave * 16 + (l & 15)) * PA + kk + q];
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb)
+        if (jb < KB) acc[jb] = Tr::mfma(a, sFt[(jb * 16 + (l & 15)) * PA + kk + q], acc[jb]);
+    }
+  }
+#pragma unroll
+  for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const long long g = g0 + wave * 16 + Tr::acc_row(q, reg);
+      const int col = jb * 16 + (l & 15);
+      if (jb < KB && g < N && col < K) zc[(size_t)g * K + col] = acc[jb][reg];
+    }
+}
+
+// ---- B1: the raw Gram sum of a share of one class's rows ---------------------------------------------------------------
+
+// tile t of the lower block triangle -> (ti >= tj), row-major over the triangle (at most 10 tiles)
+__device__ __forceinline__ void cp_tile_of(int t, int* ti, int* tj) {
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  *ti = i;
+  *tj = t - i * (i + 1) / 2;
+}
+
+template <typename T>
+__global__ __launch_bounds__(CP_THREADS) void class_gram_kernel(const T* __restrict__ zc,
+                                                                const long long* __restrict__ class_start, int K,
+                                                                int split, T* __restrict__ partial) {
+  using Tr = ProjTraits<T>;
+  __shared__ T sZ[CP_GRAM_ROWS * CP_PITCH];
+  constexpr int PER = CP_GRAM_ROWS * CP_KMAX / CP_THREADS;   // 16
+  const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, l = tid & 63, wave = tid >> 6, q = l >> 4;
+  const long long start = class_start[c], n = class_start[c + 1] - start;
+  const long long per = (n + split - 1) / split;
+  const long long lo = (long long)s * per < n ? (long long)s * per : n, hi = lo + per < n ? lo + per : n;
+  const long long rows = hi - lo;
+  const int KB = (K + 15) / 16, ntile = KB * (KB + 1) / 2, chunk_elems = CP_GRAM_ROWS * K;
+  const T* __restrict__ src = zc + (size_t)(start + lo) * K;   // the share's rows are contiguous: zc is in grouped order
+  const long long total = rows * K;
+  for (int i = tid; i < CP_GRAM_ROWS * CP_PITCH; i += CP_THREADS) sZ[i] = (T)0;   // columns K.. stay zero
+  int ti[3], tj[3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u) cp_tile_of(wave + 4 * u < ntile ? wave + 4 * u : 0, &ti[u], &tj[u]);
+  typename Tr::Acc acc[3] = {};
+  T v[PER];
+  auto load = [&](long long k0) {
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+      const int idx = tid + p * CP_THREADS;
+      const long long at = k0 * K + idx;
+      v[p] = (idx < chunk_elems && at < total) ? src[at] : (T)0;
+    }
+  };
+  if (rows > 0) load(0);
+  for (long long k0 = 0; k0 < rows; k0 += CP_GRAM_ROWS) {
+    __syncthreads();   // the previous chunk has been consumed (first pass: the zero fill is done)
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+      const int idx = tid + p * CP_THREADS;
+      if (idx < chunk_elems) sZ[(idx / K) * CP_PITCH + idx % K] = v[p];
+    }
+    __syncthreads();
+    if (k0 + CP_GRAM_ROWS < rows) load(k0 + CP_GRAM_ROWS);
+#pragma unroll
+    for (int kk = 0; kk < CP_GRAM_ROWS; kk += 4) {
+#pragma unroll
+      for (int u = 0; u < 3; ++u)
+        if (wave + 4 * u < ntile)
+          acc[u] = Tr::mfma(sZ[(kk + q) * CP_PITCH + ti[u] * 16 + (l & 15)], sZ[(kk + q) * CP_PITCH + tj[u] * 16 + (l & 15)],
+                            acc[u]);
+    }
+  }
+  T* out = partial + ((size_t)c * split + s) * K * K;
+#pragma unroll
+  for (int u = 0; u < 3; ++u)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int i = ti[u] * 16 + Tr::acc_row(q, reg), j = tj[u] * 16 + (l & 15);
+      if (wave + 4 * u < ntile && i < K && j < K) {
+        out[i * K + j] = acc[u][reg];
+        if (ti[u] != tj[u]) out[j * K + i] = acc[u][reg];   // the mirrored tile from the same values
+      }
+    }
+}
+
+// ---- B2: feature means, covariance and second moment of one class --------------------------------------------------------
+
+template <typename T>
+__global__ __launch_bounds__(CP_THREADS) void class_feature_finish_kernel(const T* __restrict__ partial,
+                                                                          const long long* __restrict__ class_start,
+                                                                          const T* __restrict__ means,
+                                                                          const T* __restrict__ F, int D, int K, int split,
+                                                                          T noise, T* __restrict__ means_f,
+                                                                          T* __restrict__ cov_f, T* __restrict__ second_f) {
+  __shared__ T sM[CP_KMAX];
+  const int c = blockIdx.x, tid = threadIdx.x, l = tid & 63, wave = tid >> 6;
+  const double n = (double)(class_start[c + 1] - class_start[c]);
+  const T* __restrict__ mu = means + (size_t)c * D;   // NaN for an empty class: so are m and everything below
+  for (int k = wave; k < K; k += CP_THREADS / 64) {
+    const T* __restrict__ f = F + (size_t)k * D;
+    T s = (T)0;
+    for (int d = l; d < D; d += 64) s += f[d] * mu[d];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+    if (l == 0) {
+      sM[k] = s;
+      means_f[(size_t)c * K + k] = s;
+    }
+  }
+  __syncthreads();
+  const T* __restrict__ p = partial + (size_t)c * split * K * K;
+  for (int e = tid; e < K * K; e += CP_THREADS) {
+    T sum = p[e];
+    for (int s = 1; s < split; ++s) sum += p[(size_t)s * K * K + e];
+    T S = n < 1.0 ? (T)NAN : sum / (T)(n - 1.0);   // n = 1: 0/0 = NaN, as sqfa_class_moments
+    const int i = e / K, j = e % K;
+    if (i == j) S += noise;
+    cov_f[(size_t)c * K * K + e] = S;
+    if (second_f != nullptr) {
+      const T mm = sM[i] * sM[j];
+      second_f[(size_t)c * K * K + e] = S + mm;
+    }
+  }
+}
+
+// ---- C: the backward weights of every virtual row -------------------------------------------------------------------------
+
+template <typename T>
+__global__ __launch_bounds__(CP_THREADS) void class_weights_kernel(const T* __restrict__ zc, long long N,
+                                                                   const long long* __restrict__ row_class,
+                                                                   const long long* __restrict__ class_start,
+                                                                   const T* __restrict__ G, int ldg,
+                                                                   const T* __restrict__ g_means, long long V, int K,
+                                                                   T* __restrict__ w) {
+  const long long e = (long long)blockIdx.x * CP_THREADS + threadIdx.x;
+  if (e >= V * K) return;
+  const long long v = e / K;
+  const int a = (int)(e % K);
+  T out = (T)0;
+  if (v < N) {
+    const long long c = row_class[v], n = class_start[c + 1] - class_start[c];
+    if (n >= 2) {   // a class of one point has no covariance: it contributes nothing
+      const T* __restrict__ Gc = G + (size_t)c * ldg * ldg;
+      const T* __restrict__ z = zc + (size_t)v * K;
+      T s = (T)0;
+      for (int b = 0; b < K; ++b) s += (Gc[a * ldg + b] + Gc[b * ldg + a]) * z[b];
+      out = s / (T)(n - 1);
+    }
+  } else {
+    const long long c = v - N;
+    if (class_start[c + 1] - class_start[c] >= 1) out = g_means[(size_t)c * K + a];
+  }
+  w[e] = out;
+}
+
+// ---- D: partial[p] = sum over the virtual rows of group p of w (x - mu)^T ------------------------------------------------
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(CP_THREADS) void class_backward_kernel(const T* __restrict__ points, long long N, int D,
+                                                                    const long long* __restrict__ row_index,
+                                                                    const long long* __restrict__ row_class,
+                                                                    const long long* __restrict__ class_start,
+                                                                    const T* __restrict__ means, const T* __restrict__ w,
+                                                                    int K, long long V, long long rows_per_group,
+                                                                    T* __restrict__ partial) {
+  using Tr = ProjTraits<T>;
+  __shared__ T sXt[CP_CHUNK * CP_PITCH], sWt[CP_CHUNK * CP_PITCH];
+  __shared__ const T* sXp[2][CP_CHUNK];
+  __shared__ const T* sMp[2][CP_CHUNK];
+  constexpr int PER_W = CP_CHUNK * CP_KMAX / CP_THREADS;   // 8
+  const int tid = threadIdx.x, l = tid & 63, wave = tid >> 6, q = l >> 4;
+  const int c0 = blockIdx.x * CP_STRIPE, grp = blockIdx.y;
+  const int KB = (K + 15) / 16, chunk_elems = CP_CHUNK * K;
+  const long long v_lo = (long long)grp * rows_per_group < V ? (long long)grp * rows_per_group : V;
+  const long long v_hi = v_lo + rows_per_group < V ? v_lo + rows_per_group : V;
+  const long long w_end = v_hi * K;
+
+  // the pointers of the rows v0 .. v0+31: a point and its class mean, or (v >= N) the mean of class v - N uncentred
+  auto fill = [&](int buf, long long v0) {
+    if (tid < CP_CHUNK) {
+      const long long v = v0 + tid;
+      const T* xp = nullptr;
+      const T* mp = nullptr;
+      if (v < v_hi) {
+        if (v < N) {
+          xp = points + cp_row(row_index, v) * (size_t)D;
+          mp = means + (size_t)row_class[v] * D;
+        } else if (class_start[v - N + 1] - class_start[v - N] >= 1) {   // an empty class's mean is NaN: a row of zeros
+          xp = means + (size_t)(v - N) * D;
+        }
+      }
+      sXp[buf][tid] = xp;
+      sMp[buf][tid] = mp;
+    }
+  };
+  T wv[PER_W];
+  auto load_w = [&](long long v0) {
+#pragma unroll
+    for (int p = 0; p < PER_W; ++p) {
+      const int idx = tid + p * CP_THREADS;
+      const long long at = v0 * K + idx;
+      wv[p] = (idx < chunk_elems && at < w_end) ? w[at] : (T)0;
+    }
+  };
+
+  for (int i = tid; i < CP_CHUNK * CP_PITCH; i += CP_THREADS) sWt[i] = (T)0;   // columns K.. stay zero
+  fill(0, v_lo);
+  __syncthreads();
+  TileLoad<T, VEC, CP_CHUNK, CP_STRIPE, CP_PITCH, true> ld;
+  typename Tr::Acc acc[4] = {};
+  if (v_lo < v_hi) {
+    ld.load(sXp[0], sMp[0], D, c0, CP_CHUNK);
+    load_w(v_lo);
+    fill(1, v_lo + CP_CHUNK);
+  }
+  int it = 0;
+  for (long long v0 = v_lo; v0 < v_hi; v0 += CP_CHUNK, ++it) {
+    __syncthreads();   // the previous chunk has been consumed; the pointers of the next one are visible
+    ld.store(sXt, CP_CHUNK);
+#pragma unroll
+    for (int p = 0; p < PER_W; ++p) {
+      const int idx = tid + p * CP_THREADS;
+      if (idx < chunk_elems) sWt[(idx / K) * CP_PITCH + idx % K] = wv[p];
+    }
+    __syncthreads();
+    if (v0 + CP_CHUNK < v_hi) {
+      ld.load(sXp[(it + 1) & 1], sMp[(it + 1) & 1], D, c0, CP_CHUNK);
+      load_w(v0 + CP_CHUNK);
+      fill(it & 1, v0 + 2 * CP_CHUNK);   // read last by the loads of this chunk, issued before the barriers above
+    }
+#pragma unroll
+    for (int kk = 0; kk < CP_CHUNK; kk += 4) {
+      const T b = sXt[(kk + q) * CP_PITCH + wave * 16 + (l & 15)];
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb)
+        if (jb < KB) acc[jb] = Tr::mfma(sWt[(kk + q) * CP_PITCH + jb * 16 + (l & 15)], b, acc[jb]);
+    }
+  }
+  T* out = partial + (size_t)grp * K * D;
+  const int d = c0 + wave * 16 + (l & 15);
+#pragma unroll
+  for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int k = jb * 16 + Tr::acc_row(q, reg);
+      if (jb < KB && k < K && d < D) out[(size_t)k * D + d] = acc[jb][reg];
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+
+struct CpLayout {
+  int split;          // shares of a class in kernel B1
+  size_t total;       // max(forward: Gram partials, backward: weights of the N + C virtual rows)
+};
+
+static bool cp_layout(long long N, int C, int D, int K, int dtype, CpLayout* w) {
+  if (N < 0 || C < 1 || D < 1 || K < 1 || K > CP_KMAX || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
+  if (C > 65535) return false;   // as the class statistics: classes in grid.y of the mean kernel
+  const long long V = N + C;
+  if ((N + CP_ROWS - 1) / CP_ROWS > (long long)INT_MAX || (V * K + CP_THREADS - 1) / CP_THREADS > (long long)INT_MAX) return false;
+  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
+  // a class of average size in shares of ~256 rows, and at least ~256 workgroups, but no share below 64 rows
+  const long long avg = N / C;
+  long long split = (avg + 255) / 256, fill = (256 + C - 1) / C, cap = (avg + 63) / 64;
+  if (split < fill) split = fill;
+  if (split > cap) split = cap;
+  if (split > CP_MAX_SPLIT) split = CP_MAX_SPLIT;
+  if (split < 1) split = 1;
+  w->split = (int)split;
+  const size_t fwd = (size_t)C * split * K * K * esz, bwd = (size_t)V * K * esz;
+  w->total = fwd > bwd ? fwd : bwd;
+  return true;
+}
+
+template <typename T> static bool cp_vec(const void* points, const void* means, const void* F, int D) {
+  return (D % ProjTraits<T>::VW) == 0 &&
+         ((reinterpret_cast<size_t>(points) | reinterpret_cast<size_t>(means) | reinterpret_cast<size_t>(F)) & 15) == 0;
+}
+
+template <typename T>
+static void run_feature_moments(const T* points, long long N, int D, const long long* row_index, const long long* row_class,
+                                const long long* class_start, int C, const T* means, const T* F, int K, double noise,
+                                T* zc, T* means_f, T* cov_f, T* second_f, char* ws, const CpLayout& w, hipStream_t stream) {
+  T* partial = reinterpret_cast<T*>(ws);
+  if (N > 0) {
+    const unsigned grid = (unsigned)((N + CP_ROWS - 1) / CP_ROWS);
+    if (cp_vec<T>(points, means, F, D))
+      class_project_kernel<T, true><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, means, F, K, zc);
+    else
+      class_project_kernel<T, false><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, means, F, K, zc);
+  }
+  class_gram_kernel<T><<<dim3(C, w.split), CP_THREADS, 0, stream>>>(zc, class_start, K, w.split, partial);
+  class_feature_finish_kernel<T><<<C, CP_THREADS, 0, stream>>>(partial, class_start, means, F, D, K, w.split, (T)noise,
+                                                               means_f, cov_f, second_f);
+}
+
+template <typename T>
+static void run_feature_backward(const T* points, long long N, int D, const long long* row_index, const long long* row_class,
+                                 const long long* class_start, int C, const T* means, const T* zc, const T* G, int ldg,
+                                 const T* g_means, int K, int n_groups, T* partial_out, char* ws, hipStream_t stream) {
+  T* wbuf = reinterpret_cast<T*>(ws);
+  const long long V = N + (g_means != nullptr ? C : 0);
+  if (V > 0)
+    class_weights_kernel<T><<<(unsigned)((V * K + CP_THREADS - 1) / CP_THREADS), CP_THREADS, 0, stream>>>(
+        zc, N, row_class, class_start, G, ldg, g_means, V, K, wbuf);
+  long long per = (V + n_groups - 1) / n_groups;
+  per = (per + CP_CHUNK - 1) / CP_CHUNK * CP_CHUNK;
+  const dim3 grid((D + CP_STRIPE - 1) / CP_STRIPE, n_groups);
+  if (cp_vec<T>(points, means, nullptr, D))
+    class_backward_kernel<T, true><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, class_start, means,
+                                                                    wbuf, K, V, per, partial_out);
+  else
+    class_backward_kernel<T, false><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, class_start, means,
+                                                                     wbuf, K, V, per, partial_out);
+}
+
+}  // namespace sqfa
+
+extern "C" size_t sqfa_class_feature_moments_workspace_bytes(long long N, int C, int D, int K, int dtype) {
+  sqfa::CpLayout w;
+  if (!sqfa::cp_layout(N, C, D, K, dtype, &w)) return 0;
+  return w.total < 16 ? 16 : w.total;
+}
+
+extern "C" int sqfa_class_feature_moments(const void* points, long long N, int D, const long long* row_index,
+                                          const long long* row_class, const long long* class_start, int C,
+                                          const void* means, const void* F, int K, int dtype, double noise, void* zc_out,
+                                          void* means_f_out, void* cov_f_out, void* second_f_out, void* workspace,
+                                          size_t workspace_bytes, void* stream_) {
+  using namespace sqfa;
+  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc_out == nullptr)) ||
+      class_start == nullptr || means == nullptr || F == nullptr || means_f_out == nullptr || cov_f_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CpLayout w;
+  if (!cp_layout(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  if (dtype == SQFA_F32)
+    run_feature_moments(static_cast<const float*>(points), N, D, row_index, row_class, class_start, C,
+                        static_cast<const float*>(means), static_cast<const float*>(F), K, noise, static_cast<float*>(zc_out),
+                        static_cast<float*>(means_f_out), static_cast<float*>(cov_f_out), static_cast<float*>(second_f_out),
+                        ws, w, stream);
+  else
+    run_feature_moments(static_cast<const double*>(points), N, D, row_index, row_class, class_start, C,
+                        static_cast<const double*>(means), static_cast<const double*>(F), K, noise,
+                        static_cast<double*>(zc_out), static_cast<double*>(means_f_out), static_cast<double*>(cov_f_out),
+                        static_cast<double*>(second_f_out), ws, w, stream);
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+extern "C" int sqfa_class_feature_moments_backward(const void* points, long long N, int D, const long long* row_index,
+                                                   const long long* row_class, const long long* class_start, int C,
+                                                   const void* means, const void* zc, const void* G, int ldg,
+                                                   const void* g_means, int K, int dtype, int n_groups, void* partial_out,
+                                                   void* workspace, size_t workspace_bytes, void* stream_) {
+  using namespace sqfa;
+  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc == nullptr)) ||
+      class_start == nullptr || means == nullptr || G == nullptr || ldg < K || n_groups < 1 || n_groups > 65535 ||
+      partial_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CpLayout w;
+  if (!cp_layout(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  if (dtype == SQFA_F32)
+    run_feature_backward(static_cast<const float*>(points), N, D, row_index, row_class, class_start, C,
+                         static_cast<const float*>(means), static_cast<const float*>(zc), static_cast<const float*>(G), ldg,
+                         static_cast<const float*>(g_means), K, n_groups, static_cast<float*>(partial_out), ws, stream);
+  else
+    run_feature_backward(static_cast<const double*>(points), N, D, row_index, row_class, class_start, C,
+                         static_cast<const double*>(means), static_cast<const double*>(zc), static_cast<const double*>(G),
+                         ldg, static_cast<const double*>(g_means), K, n_groups, static_cast<double*>(partial_out), ws, stream);
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}

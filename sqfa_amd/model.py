@@ -15,7 +15,7 @@ from ._memo import TensorMemo
 from ._optim import fitting_loop
 from .constraints import FixedFilters, Identity, Orthogonal, Sphere, orthogonal
 from .linalg import conjugate_matrix
-from .statistics import class_statistics, pca, pca_from_scatter
+from .statistics import ClassPoints, class_statistics, pca, pca_from_scatter
 
 __all__ = ["SecondMomentsSQFA", "SQFA"]
 
@@ -29,7 +29,10 @@ _DICT_KEYS = {"means", "covariances"}
 
 def _check_statistics(data_statistics, needs_dict=False):
     """Accept a (C,D,D) tensor-like or a dict with 'means' and 'covariances'
-    (reference: model.py:56-94; same exception types)."""
+    (reference: model.py:56-94; same exception types), or the labelled points themselves (statistics.ClassPoints), which
+    stand for both forms."""
+    if isinstance(data_statistics, ClassPoints):
+        return
     if isinstance(data_statistics, dict):
         missing = _DICT_KEYS - set(data_statistics.keys())
         if missing:
@@ -46,6 +49,25 @@ def _check_statistics(data_statistics, needs_dict=False):
         raise TypeError(
             "`data_statistics` must be a dictionary with 'means' and 'covariances' when `needs_dict` is True."
         )
+
+
+def _statistics_from_points(model, X, y, estimator, statistics):
+    """What fit(X=, y=) hands to the fitting loop: the dense class statistics ("dense", the default) or the labelled
+    points themselves ("points": statistics.ClassPoints, nothing of size (C,D,D) is formed)."""
+    if statistics == "dense":
+        return class_statistics(X, y, estimator=estimator)
+    if statistics != "points":
+        raise ValueError("statistics must be 'dense' or 'points'")
+    if estimator != "empirical":
+        raise ValueError("statistics='points' supports estimator='empirical' only: OAS shrinkage needs tr(S_c^2) of "
+                         "every class in data space; use statistics='dense' for it")
+    _refuse_sharded_points(model)
+    return ClassPoints(X, y)
+
+
+def _refuse_sharded_points(model):
+    if model.class_shard is not None:
+        raise NotImplementedError("class_shard works on dense class statistics only: points cannot be sharded over classes")
 
 
 _scatters = TensorMemo(max_entries=4)   # (cov, mu) -> second moments; a handful of live statistics at most (C*D*D values each)
@@ -122,7 +144,10 @@ class SecondMomentsSQFA(nn.Module):
 
     # ------------------------------------------------------------------ distances
     def _feature_scatters(self, data_statistics, regularized):
-        S = self.transform_scatters(_stats_to_scatter(data_statistics))
+        if isinstance(data_statistics, ClassPoints):   # second moments of the projected points: no (C,D,D) statistics
+            S = data_statistics.feature_statistics(self.filters, second_moments=True)["second_moments"]
+        else:
+            S = self.transform_scatters(_stats_to_scatter(data_statistics))
         if regularized:
             S = S + self.noise_mat[None]
         return S
@@ -138,6 +163,9 @@ class SecondMomentsSQFA(nn.Module):
         # a dict is reduced to second moments once instead of inside every closure; symmetric float32 GPU
         # statistics of many classes are also packed once into their lower block triangle: every closure then streams
         # ~52 % of the bytes (sqfa_project_scatters_packed; _native.prepare_packed decides and keeps the packed copy)
+        if isinstance(data_statistics, ClassPoints):
+            _refuse_sharded_points(self)
+            return data_statistics
         scatters = _stats_to_scatter(data_statistics)
         _native.prepare_packed(scatters, self.filters.shape[0])
         return scatters
@@ -213,7 +241,11 @@ class SecondMomentsSQFA(nn.Module):
             # bhattacharyya / hellinger / mahalanobis[_sq]: single process, <= GAUSS_MAX_DIM filters, a dict of float32/64 GPU statistics
             if sharded or nm.shape[0] > _native.GAUSS_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
                 return None
-            if prepared is not None:
+            if isinstance(prepared, ClassPoints):   # feature means and covariances of the points' dtype, on their device
+                if not (prepared.points.is_cuda and prepared.n_classes >= 2
+                        and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
+                    return None
+            elif prepared is not None:
                 if not isinstance(prepared, dict):
                     return None
                 mu, cov = prepared["means"], prepared["covariances"]
@@ -226,7 +258,11 @@ class SecondMomentsSQFA(nn.Module):
             # log_euclidean[_sq]: single process, within the per-class SPD functions' limit, a (C,D,D) float32/64 GPU tensor
             if sharded or nm.shape[0] > _native.SPD_FUNCTION_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
                 return None
-            if prepared is not None and not (
+            if isinstance(prepared, ClassPoints):
+                if not (prepared.points.is_cuda and prepared.n_classes >= 2
+                        and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
+                    return None
+            elif prepared is not None and not (
                     torch.is_tensor(prepared) and prepared.dim() == 3 and prepared.is_cuda and prepared.shape[0] >= 2
                     and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
                 return None
@@ -292,6 +328,8 @@ class SecondMomentsSQFA(nn.Module):
     def _n_classes_total(self, prepared):
         if self.class_shard is not None:
             return self.class_shard.n_classes
+        if isinstance(prepared, ClassPoints):
+            return prepared.n_classes
         return prepared["means"].shape[0] if isinstance(prepared, dict) else prepared.shape[0]
 
     # ------------------------------------------------------------------ fitting
@@ -300,6 +338,9 @@ class SecondMomentsSQFA(nn.Module):
         (reference: model.py:239-268)."""
         if X is None and data_statistics is None:
             raise ValueError("Either X or data_statistics must be provided.")
+        if isinstance(data_statistics, ClassPoints):
+            raise TypeError("fit_pca takes the points themselves as X= (or dense data_statistics), not a ClassPoints: "
+                            "call fit_pca(X=class_points.points)")
         k = self.filters.shape[0]
         if data_statistics is None:
             components = pca(X, k)
@@ -322,16 +363,20 @@ class SecondMomentsSQFA(nn.Module):
             register_parametrization(self, "filters", FixedFilters(n_row_fixed=n_row_fixed))
 
     def fit(self, X=None, y=None, data_statistics=None, max_epochs=300, lr=0.1, estimator="empirical",
-            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, pair_weights=None, **kwargs):
+            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, pair_weights=None, statistics="dense",
+            **kwargs):
         """Fit the filters with LBFGS (reference: model.py:270-414).  Either ``X, y`` or
         ``data_statistics``; ``pairwise=True`` learns the filters two at a time, holding the
         earlier ones fixed.  ``pair_weights``: optional symmetric, non-negative (C,C) weights W of the class pairs; the
         loss becomes -sum_{i>j} W_ij D_ij / sum_{i>j} W_ij (the diagonal is ignored; every stage of a pairwise fit uses the
-        same weights).  Extra keyword arguments go to torch.optim.LBFGS."""
+        same weights).  ``statistics`` (with ``X, y``): "dense" (default) builds the (C,D,D) class statistics once;
+        "points" keeps the labelled points (statistics.ClassPoints, also accepted as ``data_statistics``) and every closure
+        computes the class moments of the projected points: nothing of size (C,D,D) is formed (empirical estimator only).
+        Extra keyword arguments go to torch.optim.LBFGS."""
         if data_statistics is None:
             if X is None or y is None:
                 raise ValueError("Either data_statistics or X and y must be provided.")
-            data_statistics = class_statistics(X, y, estimator=estimator)
+            data_statistics = _statistics_from_points(self, X, y, estimator, statistics)
         _check_statistics(data_statistics)
         loop = dict(max_epochs=max_epochs, lr=lr, show_progress=show_progress, return_loss=True,
                     atol=atol, pair_weights=pair_weights, **kwargs)
@@ -396,6 +441,10 @@ class SQFA(SecondMomentsSQFA):
         )
 
     def _feature_statistics(self, data_statistics, regularized):
+        if isinstance(data_statistics, ClassPoints):   # means and covariances of the projected points
+            stats = data_statistics.feature_statistics(self.filters)
+            cov = stats["covariances"] + self.noise_mat[None] if regularized else stats["covariances"]
+            return {"means": stats["means"], "covariances": cov}
         cov = self.transform_scatters(data_statistics["covariances"])
         if regularized:
             cov = cov + self.noise_mat[None]
@@ -404,12 +453,15 @@ class SQFA(SecondMomentsSQFA):
     def get_class_distances(self, data_statistics, regularized=False):
         """(C,C) pairwise distances between the class feature Gaussians
         (reference: model.py:508-546)."""
-        if not isinstance(data_statistics, dict):
+        if not isinstance(data_statistics, (dict, ClassPoints)):
             raise TypeError("data_statistics must be a dictionary with 'means' and 'covariances' keys.")
         stats = self._feature_statistics(data_statistics, regularized)
         return self.distance_fun(stats, stats)
 
     def _prepare_statistics(self, data_statistics):
+        if isinstance(data_statistics, ClassPoints):
+            _refuse_sharded_points(self)
+            return data_statistics
         if not isinstance(data_statistics, dict):
             raise TypeError("data_statistics must be a dictionary with 'means' and 'covariances' keys.")
         _native.prepare_packed(data_statistics["covariances"], self.filters.shape[0])   # see SecondMomentsSQFA._prepare_statistics
@@ -419,13 +471,14 @@ class SQFA(SecondMomentsSQFA):
         return distances.embed_gaussian(self._feature_statistics(prepared, True))
 
     def fit(self, X=None, y=None, data_statistics=None, max_epochs=300, lr=0.1, estimator="empirical",
-            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, pair_weights=None, **kwargs):
-        """Fit with LBFGS (reference: model.py:548-630); ``data_statistics`` must be a dict.  ``pair_weights`` as in
-        SecondMomentsSQFA.fit."""
+            pairwise=False, show_progress=True, return_loss=False, atol=1e-6, pair_weights=None, statistics="dense",
+            **kwargs):
+        """Fit with LBFGS (reference: model.py:548-630); ``data_statistics`` must be a dict or a ClassPoints.  ``pair_weights``
+        and ``statistics`` as in SecondMomentsSQFA.fit."""
         if data_statistics is None:
             if X is None or y is None:
                 raise ValueError("Either data_statistics or X and y must be provided.")
-            data_statistics = class_statistics(X, y, estimator=estimator)
+            data_statistics = _statistics_from_points(self, X, y, estimator, statistics)
         else:
             _check_statistics(data_statistics, needs_dict=True)
         out = super().fit(data_statistics=data_statistics, max_epochs=max_epochs, lr=lr, estimator=estimator,

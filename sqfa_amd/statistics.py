@@ -4,14 +4,18 @@ Runs once per fit, before the hot path, on the input's device (the reference all
 float32 / float64 points on the GPU go through the native segmented SYRK (sqfa_class_moments: no sorted or padded
 copy of the points, exactly symmetric outputs); CPU tensors and other dtypes keep the batched torch expression.
 ClassStatisticsAccumulator builds the same statistics from batches and merges partial results.
+ClassPoints keeps the labelled points themselves as the statistics of a fit: every closure computes the class moments of
+the projected points (sqfa_class_feature_moments) and nothing of size (C,D,D) is ever formed.
 """
 import torch
 
-__all__ = ["class_statistics", "ClassStatisticsAccumulator", "oas_covariance", "sample_covariance", "pca",
+__all__ = ["class_statistics", "ClassStatisticsAccumulator", "ClassPoints", "oas_covariance", "sample_covariance", "pca",
            "pca_from_scatter"]
 
 # float32 / float64 points on the GPU take the native kernels; False keeps the batched torch expression everywhere
 NATIVE_CLASS_STATISTICS = True
+# ClassPoints on float32 / float64 GPU points takes the native kernels; False keeps its torch expression everywhere
+NATIVE_CLASS_POINTS = True
 
 
 def __dir__():
@@ -201,6 +205,107 @@ class ClassStatisticsAccumulator:
             covs = _oas_shrink(covs, n)
         second = covs + means[:, :, None] * means[:, None, :]
         return {"means": means, "covariances": covs, "second_moments": second}
+
+
+class ClassPoints:
+    """Labelled points kept as the statistics of a fit: the closure then computes the class moments of the PROJECTED
+    points,  F cov_c F^T = cov(F x | c)  and  F mu_c = mean(F x | c)  (empirical estimator), reading the (N,D) points once
+    forward and once backward instead of (C,D,D) statistics that may be many times larger -- or not fit at all.
+
+    Holds ``points`` as given (no sorted copy), ``order`` (the indices of a stable sort of the labels), ``class_start``
+    (C+1), ``row_class`` (the sorted labels), ``means`` (C,D), ``counts`` (C), ``n_classes``, ``n_dim``.  The class count
+    is the only host read (none when ``n_classes`` is given).  An empty class has NaN means and feature moments, a class
+    of one point a NaN covariance, as ``class_statistics`` gives them.  float32 / float64 points on the GPU go through the
+    native kernels (sqfa_class_means, sqfa_class_feature_moments); CPU tensors, other dtypes, more than 64 filters and
+    NATIVE_CLASS_POINTS = False evaluate the same formulas as a torch expression."""
+
+    def __init__(self, points, labels, n_classes=None):
+        if not torch.is_tensor(points) or points.dim() != 2 or not points.is_floating_point():
+            raise TypeError("points must be a floating-point tensor of shape (n_points, n_dim)")
+        labels = torch.as_tensor(labels).to(points.device).long()   # float labels too, as class_statistics
+        if labels.shape != points.shape[:1]:
+            raise ValueError("labels must have shape (n_points,)")
+        if labels.numel() == 0:
+            raise ValueError("ClassPoints needs at least one point")
+        C = int(labels.max()) + 1 if n_classes is None else int(n_classes)
+        if C < 1:
+            raise ValueError("n_classes must be positive")
+        self.points = points.detach().contiguous()
+        self.labels = labels
+        self.n_classes, self.n_dim = C, points.shape[1]
+        self.counts = torch.bincount(labels, minlength=C)   # refuses negative labels itself
+        if self.counts.shape[0] != C:
+            raise ValueError(f"labels must lie in 0..{C - 1}")
+        self.order = torch.sort(labels, stable=True).indices
+        self.class_start = torch.zeros(C + 1, dtype=torch.int64, device=labels.device)
+        self.class_start[1:] = torch.cumsum(self.counts, 0)
+        self.row_class = labels[self.order]
+        if NATIVE_CLASS_POINTS and _native_applies(self.points):
+            from . import _native
+            self.means = _native.class_means(self.points, self.order, self.class_start, C)
+        else:
+            sums = torch.zeros(C, self.n_dim, dtype=torch.float64, device=points.device)
+            sums.index_add_(0, labels, self.points.double())
+            self.means = (sums / self.counts.double()[:, None]).to(points.dtype)   # 0/0 = NaN for an empty class
+
+    @property
+    def dtype(self):
+        return self.points.dtype
+
+    @property
+    def device(self):
+        return self.points.device
+
+    def feature_statistics(self, filters, second_moments=False, noise=0.0):
+        """{'means' (C,K), 'covariances' (C,K,K)[, 'second_moments' (C,K,K)]} of the projected points, differentiable in
+        `filters` (K,D); `noise` is added to the diagonal of the matrices."""
+        if NATIVE_CLASS_POINTS and _native_applies(self.points):
+            from . import _native
+            if _native.class_feature_moments_supported(self.points, filters):
+                out = _native.ClassFeatureMoments.apply(filters, self, bool(second_moments), float(noise))
+                stats = {"means": out[0], "covariances": out[1]}
+                if second_moments:
+                    stats["second_moments"] = out[2]
+                return stats
+        return self._torch_feature_statistics(filters, second_moments, noise)
+
+    # rows of outer products z z^T formed at a time by the torch expression
+    _OUTER_ELEMENTS = 1 << 24
+
+    def _torch_feature_statistics(self, filters, second_moments, noise):
+        """The same formulas in torch: gather the class means, centre in D-space, project, index_add_ the outer products."""
+        dtype = torch.promote_types(self.points.dtype, filters.dtype)
+        F = filters.to(dtype)
+        K, C = F.shape[0], self.n_classes
+        means = self.means.to(dtype)
+        centred = self.points.to(dtype) - means[self.labels]
+        z = centred @ F.T
+        gram = torch.zeros(C, K, K, dtype=dtype, device=z.device)
+        step = max(1, self._OUTER_ELEMENTS // (K * K))
+        for r0 in range(0, z.shape[0], step):
+            zb = z[r0:r0 + step]
+            gram = torch.index_add(gram, 0, self.labels[r0:r0 + step], zb[:, :, None] * zb[:, None, :])
+        nan = torch.full((), float("nan"), dtype=dtype, device=z.device)
+        # NaN where class_statistics has it (no covariance below two points, no mean of no point), placed by `where` so that
+        # the gradient of the other classes stays finite
+        denom = (self.counts - 1).clamp(min=1).to(dtype)
+        cov = torch.where((self.counts >= 2)[:, None, None], gram / denom[:, None, None], nan)
+        if noise:
+            cov = cov + noise * torch.eye(K, dtype=dtype, device=z.device)
+        present = (self.counts > 0)[:, None]
+        m = torch.where(present, torch.where(present, means, torch.zeros_like(means)) @ F.T, nan)
+        stats = {"means": m, "covariances": cov}
+        if second_moments:
+            stats["second_moments"] = cov + m[:, :, None] * m[:, None, :]
+        return stats
+
+    def class_statistics(self, estimator="empirical"):
+        """The dense {'means', 'covariances', 'second_moments'} of the same points (for comparison: (C,D,D) tensors)."""
+        stats = class_statistics(self.points, self.labels, estimator=estimator)
+        missing = self.n_classes - stats["means"].shape[0]   # classes beyond the largest label: empty
+        if missing > 0:
+            stats = {k: torch.cat([v, v.new_full((missing,) + tuple(v.shape[1:]), float("nan"))]) for k, v in stats.items()}
+        return stats
 
 
 def _batched_moments(sorted_points, starts, counts, n_max, estimator):

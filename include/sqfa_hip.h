@@ -495,6 +495,12 @@ int sqfa_orthogonal_backward(const void *X, const void *base, const void *gF, in
  *   second moments are formed anywhere (sum x x^T - n mu mu^T cancels in float32).  m2 stays exactly symmetric.
  * sqfa_class_moments_finalize: statistics from such a state: cov_out = m2 / (counts - 1) (SQFA_COV_EMPIRICAL) or its OAS
  *   shrinkage (SQFA_COV_OAS), second_out (or NULL) = cov + means means^T; counts < 1 gives NaN matrices.
+ * sqfa_class_shrinkage: the OAS coefficients alone, measured from the points with NOTHING of size (D,D) written: the
+ *   SYRK of sqfa_class_moments(SQFA_COV_OAS) in a measuring mode (same grid, chunk walk, MFMA, s = v / (n_c - 1) rounded
+ *   to the dtype, per-tile tr S and sum S o S in double) and a finish kernel that sums the partials in the same order and
+ *   forms rho by the same expression.  means (C,D) in: sqfa_class_means.  keep_out (C) = (T)(1 - rho_c) and shift_out (C)
+ *   = (T)(rho_c tr S_c / D), dtype: the very bits SQFA_COV_OAS applies, OAS(S_c) = keep_c S_c + shift_c I.  rho_out (C)
+ *   FLOAT64 or NULL.  A class below two points gets NaN in all three.  Workspace as above (the partials are all it uses).
  * Return SQFA_ERR_BAD_ARGUMENT (null pointers -- points may be NULL only when N = 0 --, N < 0, C < 1, D < 1, dtype,
  * estimator), SQFA_ERR_UNSUPPORTED_M (the grid limits above), SQFA_ERR_WORKSPACE; every check runs before the first HIP call.
  */
@@ -513,6 +519,10 @@ int sqfa_class_moments_update(const void *points, long long N, int D, const long
 int sqfa_class_moments_finalize(const double *counts, const void *means, const void *m2, int C, int D, int dtype,
                                 int estimator, void *cov_out, void *second_out,
                                 void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_class_shrinkage(const void *points, long long N, int D, const long long *row_index,
+                         const long long *class_start, int C, int dtype, const void *means,
+                         void *keep_out, void *shift_out, double *rho_out,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Feature moments from labelled points, with nothing of size (C,D,D): per closure evaluation they replace the class
@@ -546,6 +556,19 @@ int sqfa_class_moments_finalize(const double *counts, const void *means, const v
  * Return SQFA_ERR_BAD_ARGUMENT (null pointers -- points, row_class and zc may be NULL only when N = 0 --, N < 0, C < 1,
  * D < 1, K < 1, dtype, ldg < K, n_groups), SQFA_ERR_UNSUPPORTED_M (K > 64 and the limits above), SQFA_ERR_WORKSPACE, in
  * this order; every check runs before the first HIP call.
+ *
+ * The shrunk entries: the same moments of OAS-shrunk class covariances, OAS(S_c) = keep_c S_c + shift_c I with keep, shift
+ * (C) in the dtype from sqfa_class_shrinkage, through  F OAS(S_c) F^T = keep_c F S_c F^T + shift_c F F^T:
+ *   sqfa_class_feature_moments_shrunk   cov_f_out = keep_c sum zc_i zc_i^T / (n_c - 1) + shift_c F F^T + noise I; F F^T (K,K)
+ *     is formed once per call (one launch more), every element in one fixed order, so both matrices stay exactly symmetric.
+ *     Same NaN pattern (keep and shift of a class below two points are NaN already).
+ *   sqfa_class_feature_moments_shrunk_backward   takes F (K,D) as well:
+ *         dL/dF = sum_i keep_c w_i (x_i - mu_class)^T + H F + sum_c g_c mu_c^T,   H = sum_{c: n_c >= 2} shift_c (G_c + G_c^T)
+ *     H F through K more virtual rows (the filters, weighted by the columns of H), H by one launch more, the classes
+ *     summed in a fixed order and those with n_c < 2 left out by select: NaN in their G, keep and shift never reaches the
+ *     result.  A class with n_c >= 2 and NaN coefficients (zero variance, D = 1) gives NaN, as the dense statistics do.
+ *   workspace: sqfa_class_feature_moments_shrunk_workspace_bytes (the query above plus K more weight rows and one (K,K)
+ *   block; 0 where that one is 0).  Checks, return codes and their order as above; keep and shift must not be NULL.
  */
 int sqfa_class_means(const void *points, long long N, int D, const long long *row_index,
                      const long long *class_start, int C, int dtype, void *means_out, void *stream);
@@ -560,6 +583,19 @@ int sqfa_class_feature_moments_backward(const void *points, long long N, int D, 
                                         const void *means, const void *zc, const void *G, int ldg,
                                         const void *g_means, int K, int dtype, int n_groups, void *partial_out,
                                         void *workspace, size_t workspace_bytes, void *stream);
+size_t sqfa_class_feature_moments_shrunk_workspace_bytes(long long N, int C, int D, int K, int dtype);
+int sqfa_class_feature_moments_shrunk(const void *points, long long N, int D, const long long *row_index,
+                                      const long long *row_class, const long long *class_start, int C,
+                                      const void *means, const void *F, int K, int dtype, double noise,
+                                      const void *keep, const void *shift,
+                                      void *zc_out, void *means_f_out, void *cov_f_out, void *second_f_out,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_class_feature_moments_shrunk_backward(const void *points, long long N, int D, const long long *row_index,
+                                               const long long *row_class, const long long *class_start, int C,
+                                               const void *means, const void *F, const void *zc, const void *G, int ldg,
+                                               const void *g_means, const void *keep, const void *shift,
+                                               int K, int dtype, int n_groups, void *partial_out,
+                                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* Introspection (benchmarks / development; not needed by a reference-side binding).
  *

@@ -672,6 +672,27 @@ def class_means(points, order, class_start, C):
     return means
 
 
+def class_shrinkage(points, order, class_start, means, C):
+    """sqfa_class_shrinkage on the current stream: (keep (C), shift (C) in the dtype, rho (C) float64) of the OAS shrinkage
+    OAS(S_c) = keep_c S_c + shift_c I of the classes of `points[order]` grouped by `class_start`, from the points and their
+    `means` (class_means) alone: the bits class_moments(COV_OAS) applies, with nothing of size (D,D) written."""
+    lib = _lib.load()
+    if not class_moments_supported(points) or not points.is_contiguous():
+        raise RuntimeError("sqfa_amd's class statistics kernels take contiguous (N, D) float32 / float64 points on the GPU")
+    N, D = points.shape
+    code = _dtype_code(points)
+    dev, dt = points.device, points.dtype
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(lib.sqfa_class_moments_workspace_bytes, C, D, code)
+        keep = torch.empty(C, dtype=dt, device=dev)
+        shift = torch.empty(C, dtype=dt, device=dev)
+        rho = torch.empty(C, dtype=torch.float64, device=dev)
+        _lib.check(lib.sqfa_class_shrinkage(_ptr(points), N, D, _ptr(order), _ptr(class_start), C, code, _ptr(means),
+                                            _ptr(keep), _ptr(shift), _ptr(rho), _ptr(ws), nbytes, stream),
+                   "sqfa_class_shrinkage")
+    return keep, shift, rho
+
+
 def class_feature_moments_supported(points, filters):
     """Contiguous float32 / float64 (N,D) points on the GPU and (K,D) filters of the same dtype and device, K <= 64."""
     return bool(class_moments_supported(points) and points.is_contiguous() and filters.dim() == 2
@@ -689,29 +710,40 @@ def point_backward_groups(N, D):
 
 def class_feature_moments(cp, F, second_moments, noise):
     """sqfa_class_feature_moments on the current stream for a statistics.ClassPoints `cp` and contiguous filters F (K,D):
-    (zc (N,K) in grouped order, means_f (C,K), cov_f (C,K,K), second_f (C,K,K) or None)."""
+    (zc (N,K) in grouped order, means_f (C,K), cov_f (C,K,K), second_f (C,K,K) or None).  A `cp` with shrinkage
+    coefficients (estimator="oas") goes through sqfa_class_feature_moments_shrunk."""
     lib = _lib.load()
     X = cp.points
     N, D = X.shape
     K, C = F.shape[0], cp.n_classes
     code = _dtype_code(X)
     dev, dt = X.device, X.dtype
+    keep, shift = getattr(cp, "shrink_keep", None), getattr(cp, "shrink_shift", None)
+    query = lib.sqfa_class_feature_moments_workspace_bytes if keep is None else lib.sqfa_class_feature_moments_shrunk_workspace_bytes
     with _on_stream(dev) as stream:
-        ws, nbytes = _workspace(lib.sqfa_class_feature_moments_workspace_bytes, N, C, D, K, code)
+        ws, nbytes = _workspace(query, N, C, D, K, code)
         zc = torch.empty((N, K), dtype=dt, device=dev)
         means_f = torch.empty((C, K), dtype=dt, device=dev)
         cov_f = torch.empty((C, K, K), dtype=dt, device=dev)
         second_f = torch.empty((C, K, K), dtype=dt, device=dev) if second_moments else None
-        _lib.check(lib.sqfa_class_feature_moments(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class), _ptr(cp.class_start), C,
-                                                  _ptr(cp.means), _ptr(F), K, code, float(noise), _ptr(zc), _ptr(means_f),
-                                                  _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream),
-                   "sqfa_class_feature_moments")
+        if keep is None:
+            _lib.check(lib.sqfa_class_feature_moments(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class), _ptr(cp.class_start), C,
+                                                      _ptr(cp.means), _ptr(F), K, code, float(noise), _ptr(zc), _ptr(means_f),
+                                                      _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream),
+                       "sqfa_class_feature_moments")
+        else:
+            _lib.check(lib.sqfa_class_feature_moments_shrunk(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
+                                                             _ptr(cp.class_start), C, _ptr(cp.means), _ptr(F), K, code,
+                                                             float(noise), _ptr(keep), _ptr(shift), _ptr(zc), _ptr(means_f),
+                                                             _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream),
+                       "sqfa_class_feature_moments_shrunk")
     return zc, means_f, cov_f, second_f
 
 
-def class_feature_moments_backward(cp, zc, G, g_means):
+def class_feature_moments_backward(cp, zc, G, g_means, F=None):
     """sqfa_class_feature_moments_backward on the current stream: the (n_groups, K, D) partial sums of dL/dF for
-    G = dL/dcov_f (C,K,K) and g_means = dL/dmeans_f (C,K) or None."""
+    G = dL/dcov_f (C,K,K) and g_means = dL/dmeans_f (C,K) or None.  A `cp` with shrinkage coefficients needs the contiguous
+    filters F (K,D) of the forward call as well (sqfa_class_feature_moments_shrunk_backward)."""
     lib = _lib.load()
     X = cp.points
     N, D = X.shape
@@ -720,13 +752,25 @@ def class_feature_moments_backward(cp, zc, G, g_means):
     G = G.detach().contiguous()
     g_means = g_means.detach().contiguous() if g_means is not None else None
     groups = point_backward_groups(N, D)
+    keep, shift = getattr(cp, "shrink_keep", None), getattr(cp, "shrink_shift", None)
+    if keep is not None and F is None:
+        raise ValueError("the backward of shrunk feature moments needs the filters")
+    query = lib.sqfa_class_feature_moments_workspace_bytes if keep is None else lib.sqfa_class_feature_moments_shrunk_workspace_bytes
     with _on_stream(X.device) as stream:
-        ws, nbytes = _workspace(lib.sqfa_class_feature_moments_workspace_bytes, N, C, D, K, code)
+        ws, nbytes = _workspace(query, N, C, D, K, code)
         partial = torch.empty((groups, K, D), dtype=X.dtype, device=X.device)
-        _lib.check(lib.sqfa_class_feature_moments_backward(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
-                                                           _ptr(cp.class_start), C, _ptr(cp.means), _ptr(zc), _ptr(G), K,
-                                                           _ptr(g_means), K, code, groups, _ptr(partial), _ptr(ws), nbytes,
-                                                           stream), "sqfa_class_feature_moments_backward")
+        if keep is None:
+            _lib.check(lib.sqfa_class_feature_moments_backward(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
+                                                               _ptr(cp.class_start), C, _ptr(cp.means), _ptr(zc), _ptr(G), K,
+                                                               _ptr(g_means), K, code, groups, _ptr(partial), _ptr(ws), nbytes,
+                                                               stream), "sqfa_class_feature_moments_backward")
+        else:
+            _lib.check(lib.sqfa_class_feature_moments_shrunk_backward(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
+                                                                      _ptr(cp.class_start), C, _ptr(cp.means), _ptr(F),
+                                                                      _ptr(zc), _ptr(G), K, _ptr(g_means), _ptr(keep),
+                                                                      _ptr(shift), K, code, groups, _ptr(partial), _ptr(ws),
+                                                                      nbytes, stream),
+                       "sqfa_class_feature_moments_shrunk_backward")
     return partial
 
 
@@ -735,20 +779,22 @@ class ClassFeatureMoments(torch.autograd.Function):
     statistics.ClassPoints: F mu_c, cov(F x | c) (+ noise on the diagonal) and their second moment, equal to F mu_c,
     F cov_c F^T and F (cov_c + mu_c mu_c^T) F^T of the dense statistics without forming them (replaces class_statistics
     + transform_scatters of the reference, src/sqfa/statistics.py:8-124, src/sqfa/model.py:172-188).  The backward
-    returns dL/dF only; it needs the centred features (N,K) and the points, read once more."""
+    returns dL/dF only; it needs the centred features (N,K) and the points, read once more.  A ClassPoints with
+    estimator="oas" gives the same moments of the shrunk covariances keep_c cov_c + shift_c I (the shrunk entries)."""
 
     @staticmethod
     def forward(ctx, filters, class_points, second_moments, noise):
         F = filters.detach().contiguous()
         zc, means_f, cov_f, second_f = class_feature_moments(class_points, F, second_moments, noise)
-        ctx.save_for_backward(zc, means_f)
+        shrunk = getattr(class_points, "shrink_keep", None) is not None
+        ctx.save_for_backward(zc, means_f, *((F,) if shrunk else ()))   # shrunk: the backward adds H F
         ctx.class_points = class_points
         ctx.second = bool(second_moments)
         return (means_f, cov_f, second_f) if second_moments else (means_f, cov_f)
 
     @staticmethod
     def backward(ctx, g_means, g_cov, g_second=None):
-        zc, means_f = ctx.saved_tensors
+        zc, means_f, *filters = ctx.saved_tensors
         G = g_cov
         if ctx.second:
             # second = cov + m m^T: its gradient goes to the covariance as it is and to the means through the product
@@ -757,7 +803,7 @@ class ClassFeatureMoments(torch.autograd.Function):
             G = G + g_second
             sym = g_second + g_second.transpose(1, 2)
             g_means = g_means + (sym * means_f.unsqueeze(1)).sum(dim=-1)
-        partial = class_feature_moments_backward(ctx.class_points, zc, G, g_means)
+        partial = class_feature_moments_backward(ctx.class_points, zc, G, g_means, *filters)
         return partial.sum(dim=0), None, None, None
 
 

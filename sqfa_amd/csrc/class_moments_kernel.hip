@@ -25,6 +25,9 @@
 //   class_oas_finish_kernel  sums the per-(class, tile) partials of tr S and sum S o S in a fixed order, forms rho
 //                            (Chen et al. 2010, clamp at 1) in double, rewrites the class as (1-rho) S + rho tr/D I and
 //                            writes the second moment in the same pass
+//   class_shrinkage_finish_kernel  sqfa_class_shrinkage: the SYRK in its measuring mode (CM_MEASURE: the same chunk walk, MFMA,
+//                            s = v / (n - 1) and per-tile partials, and NO store of anything of size (D,D)), then the same
+//                            sum of the partials and the same rho, written as keep = 1 - rho and shift = rho tr / D per class
 //   class_mean_merge_kernel  accumulate mode, after the SYRK (whose epilogue needs the old mean): means, counts
 //   class_finalize_kernel    accumulator -> statistics: the epilogue above applied to tiles of M2
 // LDS rows have a pitch of 80 elements: the 16 lanes of k and of k+1 that one MFMA operand read puts in one lane group
@@ -48,7 +51,7 @@ constexpr int CM_PER_THREAD = CM_TILE * CM_KC / CM_THREADS;   // staged elements
 constexpr int CM_MEAN_COLS = 32;
 constexpr int CM_MEAN_LANES = 8;
 
-enum { CM_EMPIRICAL = SQFA_COV_EMPIRICAL, CM_OAS = SQFA_COV_OAS, CM_SCATTER = SQFA_COV_SCATTER, CM_ACCUMULATE = 3 };
+enum { CM_EMPIRICAL = SQFA_COV_EMPIRICAL, CM_OAS = SQFA_COV_OAS, CM_SCATTER = SQFA_COV_SCATTER, CM_ACCUMULATE = 3, CM_MEASURE = 4 };
 
 __host__ __device__ inline int cm_tiles(int D) { return (D + CM_TILE - 1) / CM_TILE; }
 __host__ __device__ inline size_t cm_tri_tiles(int D) { return (size_t)cm_tiles(D) * (cm_tiles(D) + 1) / 2; }
@@ -105,9 +108,9 @@ template <typename T> struct TileOut {
   int D, i0, j0;       // tile origin: rows i0.., columns j0.. (i0 >= j0)
   double n;            // class size (CM_ACCUMULATE: unused)
   T w;                 // CM_ACCUMULATE: n_a n_b / (n_a + n_b)
-  T* cov;              // this class's (D,D) output (CM_ACCUMULATE: M2, read and written)
+  T* cov;              // this class's (D,D) output (CM_ACCUMULATE: M2, read and written; CM_MEASURE: never touched)
   T* second;           // or NULL
-  double* partial;     // CM_OAS: this tile's {tr S, sum S o S}
+  double* partial;     // CM_OAS, CM_MEASURE: this tile's {tr S, sum S o S}
 };
 
 // One element: v = raw centred sum at (gi, gj); a, b = mean_i, mean_j; da, db = delta_i, delta_j.  Every product is
@@ -126,8 +129,8 @@ __device__ __forceinline__ void cm_emit(const TileOut<T>& o, T v, int gi, int gj
     return;
   }
   const T s = o.n < 1.0 ? (T)NAN : v / (T)(o.n - 1.0);   // n = 1: 0/0 = NaN; n = 0: NaN like the mean
-  o.cov[at] = s;
-  if (o.mode == CM_OAS) {
+  if (o.mode != CM_MEASURE) o.cov[at] = s;
+  if (o.mode == CM_OAS || o.mode == CM_MEASURE) {
     if (gi == gj) *tr += (double)s;
     *sq += weight * (double)s * (double)s;
   } else if (o.second != nullptr) {
@@ -148,14 +151,14 @@ __device__ __forceinline__ void tile_epilogue(const TileOut<T>& o, const T* sT, 
     const int r = idx / CM_TILE, cc = idx % CM_TILE, gi = o.i0 + r, gj = o.j0 + cc;
     if (gi < o.D && gj < o.D) cm_emit(o, sT[r * CM_TPITCH + cc], gi, gj, sMuI[r], sMuJ[cc], sDI[r], sDJ[cc], diag ? 1.0 : 2.0, &tr, &sq);
   }
-  if (!diag) {
+  if (!diag && o.mode != CM_MEASURE) {
     double tr2 = 0.0, sq2 = 0.0;   // the mirrored copy is not counted again
     for (int idx = tid; idx < CM_TILE * CM_TILE; idx += CM_THREADS) {
       const int r = idx / CM_TILE, cc = idx % CM_TILE, gj = o.j0 + r, gi = o.i0 + cc;
       if (gi < o.D && gj < o.D) cm_emit(o, sT[cc * CM_TPITCH + r], gj, gi, sMuJ[r], sMuI[cc], sDJ[r], sDI[cc], 0.0, &tr2, &sq2);
     }
   }
-  if (o.mode == CM_OAS) {   // workgroup sum in a fixed order
+  if (o.mode == CM_OAS || o.mode == CM_MEASURE) {   // workgroup sum in a fixed order
     for (int off = 32; off > 0; off >>= 1) {
       tr += __shfl_down(tr, off);
       sq += __shfl_down(sq, off);
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(CM_THREADS) void class_syrk_kernel(const T* __restr
   o.j0 = j0;
   o.n = (double)n;
   o.w = (T)0;
-  o.cov = out + (size_t)c * D * D;
+  o.cov = out != nullptr ? out + (size_t)c * D * D : nullptr;
   o.second = second != nullptr ? second + (size_t)c * D * D : nullptr;
   o.partial = partials != nullptr ? partials + 2 * ((size_t)c * ntri + t) : nullptr;
   double n_a = 0.0;
@@ -356,17 +359,13 @@ __global__ __launch_bounds__(CM_THREADS) void class_finalize_kernel(const double
   tile_epilogue(o, sT, sMuI, sMuJ, sZero, sZero, sRed);
 }
 
+// The OAS coefficients of one class from its per-tile partials, by the whole workgroup: the sums in a fixed order, rho
+// (Chen et al. 2010, clamp at 1) in double, keep = 1 - rho and shift = rho tr / D rounded to the dtype.  The one place
+// where they are formed: the dense statistics and sqfa_class_shrinkage get the same bits.
 template <typename T>
-__global__ __launch_bounds__(CM_THREADS) void class_oas_finish_kernel(const double* __restrict__ partials,
-                                                                      const long long* __restrict__ class_start,
-                                                                      const double* __restrict__ counts,
-                                                                      const T* __restrict__ means, int D, T* cov,
-                                                                      T* second) {
-  __shared__ double sTr[CM_THREADS], sSq[CM_THREADS];
-  const int ntri = (int)cm_tri_tiles(D);
-  const int c = blockIdx.y, tid = threadIdx.x;
-  const double n = class_start != nullptr ? (double)(class_start[c + 1] - class_start[c]) : counts[c];
-  const double* p = partials + 2 * (size_t)c * ntri;
+__device__ __forceinline__ void cm_oas_coefficients(const double* __restrict__ p, int ntri, double n, int D, double* sTr,
+                                                    double* sSq, T* keep, T* shift, double* rho_out) {
+  const int tid = threadIdx.x;
   double tr = 0.0, sq = 0.0;
   for (int t = tid; t < ntri; t += CM_THREADS) {
     tr += p[2 * t];
@@ -386,7 +385,24 @@ __global__ __launch_bounds__(CM_THREADS) void class_oas_finish_kernel(const doub
   const double tr2 = sSq[0], d = (double)D;
   double rho = ((1.0 - 2.0 / d) * tr2 + tr * tr) / ((n + 1.0 - 2.0 / d) * (tr2 - tr * tr / d));
   if (rho > 1.0) rho = 1.0;   // NaN stays NaN, as torch.clamp keeps it
-  const T keep = (T)(1.0 - rho), shift = (T)(rho * tr / d);
+  *keep = (T)(1.0 - rho);
+  *shift = (T)(rho * tr / d);
+  *rho_out = rho;
+}
+
+template <typename T>
+__global__ __launch_bounds__(CM_THREADS) void class_oas_finish_kernel(const double* __restrict__ partials,
+                                                                      const long long* __restrict__ class_start,
+                                                                      const double* __restrict__ counts,
+                                                                      const T* __restrict__ means, int D, T* cov,
+                                                                      T* second) {
+  __shared__ double sTr[CM_THREADS], sSq[CM_THREADS];
+  const int ntri = (int)cm_tri_tiles(D);
+  const int c = blockIdx.y, tid = threadIdx.x;
+  const double n = class_start != nullptr ? (double)(class_start[c + 1] - class_start[c]) : counts[c];
+  T keep, shift;
+  double rho;
+  cm_oas_coefficients<T>(partials + 2 * (size_t)c * ntri, ntri, n, D, sTr, sSq, &keep, &shift, &rho);
   T* S = cov + (size_t)c * D * D;
   T* M = second != nullptr ? second + (size_t)c * D * D : nullptr;
   const T* mu = means + (size_t)c * D;
@@ -400,6 +416,28 @@ __global__ __launch_bounds__(CM_THREADS) void class_oas_finish_kernel(const doub
       const T ab = mu[i] * mu[j];
       M[e] = s + ab;
     }
+  }
+}
+
+// sqfa_class_shrinkage: one workgroup per class; a class below two points has no covariance to shrink: NaN throughout
+template <typename T>
+__global__ __launch_bounds__(CM_THREADS) void class_shrinkage_finish_kernel(const double* __restrict__ partials,
+                                                                            const long long* __restrict__ class_start,
+                                                                            int D, T* __restrict__ keep_out,
+                                                                            T* __restrict__ shift_out,
+                                                                            double* __restrict__ rho_out) {
+  __shared__ double sTr[CM_THREADS], sSq[CM_THREADS];
+  const int ntri = (int)cm_tri_tiles(D);
+  const int c = blockIdx.x;
+  const double n = (double)(class_start[c + 1] - class_start[c]);
+  T keep, shift;
+  double rho;
+  cm_oas_coefficients<T>(partials + 2 * (size_t)c * ntri, ntri, n, D, sTr, sSq, &keep, &shift, &rho);
+  if (threadIdx.x == 0) {
+    const bool some = n >= 2.0;
+    keep_out[c] = some ? keep : (T)NAN;
+    shift_out[c] = some ? shift : (T)NAN;
+    if (rho_out != nullptr) rho_out[c] = some ? rho : (double)NAN;
   }
 }
 
@@ -540,6 +578,35 @@ extern "C" int sqfa_class_means(const void* points, long long N, int D, const lo
   else
     class_mean_kernel<double><<<grid, CM_THREADS, 0, stream>>>(static_cast<const double*>(points), D, row_index, class_start,
                                                                static_cast<double*>(means_out));
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+// keep = 1 - rho and shift = rho tr / D of the OAS shrinkage, measured from the points: the SYRK without its stores
+extern "C" int sqfa_class_shrinkage(const void* points, long long N, int D, const long long* row_index,
+                                    const long long* class_start, int C, int dtype, const void* means, void* keep_out,
+                                    void* shift_out, double* rho_out, void* workspace, size_t workspace_bytes,
+                                    void* stream_) {
+  using namespace sqfa;
+  if (N < 0 || C < 1 || D < 1 || (points == nullptr && N > 0) || class_start == nullptr || means == nullptr ||
+      keep_out == nullptr || shift_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CmLayout w;
+  if (!cm_layout(C, D, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  double* partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + w.partials_off);
+  if (dtype == SQFA_F32) {
+    launch_syrk<float>(static_cast<const float*>(points), D, row_index, class_start, C, static_cast<const float*>(means),
+                       CM_MEASURE, nullptr, nullptr, partials, nullptr, nullptr, stream);
+    class_shrinkage_finish_kernel<float><<<C, CM_THREADS, 0, stream>>>(partials, class_start, D, static_cast<float*>(keep_out),
+                                                                       static_cast<float*>(shift_out), rho_out);
+  } else {
+    launch_syrk<double>(static_cast<const double*>(points), D, row_index, class_start, C, static_cast<const double*>(means),
+                        CM_MEASURE, nullptr, nullptr, partials, nullptr, nullptr, stream);
+    class_shrinkage_finish_kernel<double><<<C, CM_THREADS, 0, stream>>>(partials, class_start, D, static_cast<double*>(keep_out),
+                                                                        static_cast<double*>(shift_out), rho_out);
+  }
   return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }
 

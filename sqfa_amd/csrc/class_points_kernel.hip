@@ -26,6 +26,15 @@
 //                            w_v (x_v - mu)^T (virtual rows >= N: w_v mu_c^T), 32 rows per chunk staged as [row][col],
 //                            A[i][k] = w[k][i], B[k][j] = xc[k][j]; writes partial[p] (K, stripe).  The sum over p is the
 //                            caller's (partial.sum(0) or sqfa_sphere_backward), as for sqfa_feature_scatters_backward.
+// The shrunk entries (OAS: cov_c -> keep_c cov_c + shift_c I, the coefficients from sqfa_class_shrinkage) add one launch
+// to each direction and run the kernels above with the coefficients:
+//   filter_gram_kernel       forward, before B2: F F^T (K,K) once per call, one wave per element of the lower triangle
+//                            (lane-strided sum over d, fixed shuffle tree), written at (i,j) and (j,i).  B2 then forms
+//                            keep_c S + shift_c F F^T before the noise.
+//   class_shrink_sum_kernel  backward, before C: H = sum over the classes with n_c >= 2 of shift_c (G_c + G_c^T), one
+//                            workgroup per element (class-strided sums per thread, then a fixed tree).  C scales w_g by
+//                            keep_c and appends K more virtual rows w_{N+C+k} = H[:,k] whose "point" in D is F[k,:]
+//                            uncentred: D adds H F.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -250,6 +259,29 @@ __global__ __launch_bounds__(CP_THREADS) void class_gram_kernel(const T* __restr
     }
 }
 
+// ---- shrunk forward: F F^T, once per call -------------------------------------------------------------------------------------
+
+// wave (i, j <= i) of the lower triangle: sum_d F[i][d] F[j][d], lane-strided, fixed shuffle tree; one value, two stores
+template <typename T>
+__global__ __launch_bounds__(CP_THREADS) void filter_gram_kernel(const T* __restrict__ F, int D, int K,
+                                                                 T* __restrict__ fft) {
+  const int l = threadIdx.x & 63;
+  const int t = blockIdx.x * (CP_THREADS / 64) + (threadIdx.x >> 6);   // wave-uniform
+  if (t >= K * (K + 1) / 2) return;
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  const int j = t - i * (i + 1) / 2;
+  const T* __restrict__ fi = F + (size_t)i * D;
+  const T* __restrict__ fj = F + (size_t)j * D;
+  T s = (T)0;
+  for (int d = l; d < D; d += 64) s += fi[d] * fj[d];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+  if (l == 0) {
+    fft[i * K + j] = s;
+    fft[j * K + i] = s;
+  }
+}
+
 // ---- B2: feature means, covariance and second moment of one class --------------------------------------------------------
 
 template <typename T>
@@ -258,7 +290,10 @@ __global__ __launch_bounds__(CP_THREADS) void class_feature_finish_kernel(const 
                                                                           const T* __restrict__ means,
                                                                           const T* __restrict__ F, int D, int K, int split,
                                                                           T noise, T* __restrict__ means_f,
-                                                                          T* __restrict__ cov_f, T* __restrict__ second_f) {
+                                                                          T* __restrict__ cov_f, T* __restrict__ second_f,
+                                                                          const T* __restrict__ keep,
+                                                                          const T* __restrict__ shift,
+                                                                          const T* __restrict__ fft) {
   __shared__ T sM[CP_KMAX];
   const int c = blockIdx.x, tid = threadIdx.x, l = tid & 63, wave = tid >> 6;
   const double n = (double)(class_start[c + 1] - class_start[c]);
@@ -280,6 +315,10 @@ __global__ __launch_bounds__(CP_THREADS) void class_feature_finish_kernel(const 
     for (int s = 1; s < split; ++s) sum += p[(size_t)s * K * K + e];
     T S = n < 1.0 ? (T)NAN : sum / (T)(n - 1.0);   // n = 1: 0/0 = NaN, as sqfa_class_moments
     const int i = e / K, j = e % K;
+    if (keep != nullptr) {   // shrunk: the same chain at (i,j) and (j,i), fft symmetric bit for bit
+      const T kept = keep[c] * S, shifted = shift[c] * fft[e];
+      S = kept + shifted;
+    }
     if (i == j) S += noise;
     cov_f[(size_t)c * K * K + e] = S;
     if (second_f != nullptr) {
@@ -297,7 +336,9 @@ __global__ __launch_bounds__(CP_THREADS) void class_weights_kernel(const T* __re
                                                                    const long long* __restrict__ class_start,
                                                                    const T* __restrict__ G, int ldg,
                                                                    const T* __restrict__ g_means, long long V, int K,
-                                                                   T* __restrict__ w) {
+                                                                   T* __restrict__ w, int C,
+                                                                   const T* __restrict__ keep,
+                                                                   const T* __restrict__ H) {
   const long long e = (long long)blockIdx.x * CP_THREADS + threadIdx.x;
   if (e >= V * K) return;
   const long long v = e / K;
@@ -311,24 +352,53 @@ __global__ __launch_bounds__(CP_THREADS) void class_weights_kernel(const T* __re
       T s = (T)0;
       for (int b = 0; b < K; ++b) s += (Gc[a * ldg + b] + Gc[b * ldg + a]) * z[b];
       out = s / (T)(n - 1);
+      if (keep != nullptr) out = keep[c] * out;   // shrunk: cov_f holds keep_c times the sample covariance
     }
-  } else {
+  } else if (v < N + C) {
     const long long c = v - N;
-    if (class_start[c + 1] - class_start[c] >= 1) out = g_means[(size_t)c * K + a];
+    if (g_means != nullptr && class_start[c + 1] - class_start[c] >= 1) out = g_means[(size_t)c * K + a];
+  } else {
+    out = H[(size_t)a * K + (v - N - C)];   // shrunk: filter row k = v - N - C carries the column H[:,k]
   }
   w[e] = out;
 }
 
+// ---- shrunk backward: H = sum_c shift_c (G_c + G_c^T) over the classes with a covariance --------------------------------
+
+template <typename T>
+__global__ __launch_bounds__(CP_THREADS) void class_shrink_sum_kernel(const T* __restrict__ G, int ldg,
+                                                                      const long long* __restrict__ class_start,
+                                                                      const T* __restrict__ shift, int C, int K,
+                                                                      T* __restrict__ H) {
+  __shared__ T sSum[CP_THREADS];
+  const int e = blockIdx.x, a = e / K, b = e % K, tid = threadIdx.x;
+  T s = (T)0;
+  for (int c = tid; c < C; c += CP_THREADS) {
+    if (class_start[c + 1] - class_start[c] >= 2) {   // by select: NaN in G and shift of the other classes is never read
+      const T* __restrict__ Gc = G + (size_t)c * ldg * ldg;
+      s += shift[c] * (Gc[a * ldg + b] + Gc[b * ldg + a]);
+    }
+  }
+  sSum[tid] = s;
+  __syncthreads();
+  for (int off = CP_THREADS / 2; off > 0; off >>= 1) {
+    if (tid < off) sSum[tid] += sSum[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) H[e] = sSum[0];
+}
+
 // ---- D: partial[p] = sum over the virtual rows of group p of w (x - mu)^T ------------------------------------------------
 
-template <typename T, bool VEC>
-__global__ __launch_bounds__(CP_THREADS) void class_backward_kernel(const T* __restrict__ points, long long N, int D,
-                                                                    const long long* __restrict__ row_index,
-                                                                    const long long* __restrict__ row_class,
-                                                                    const long long* __restrict__ class_start,
-                                                                    const T* __restrict__ means, const T* __restrict__ w,
-                                                                    int K, long long V, long long rows_per_group,
-                                                                    T* __restrict__ partial) {
+// The body of both kernels D.  SHRUNK is a compile-time switch, not a NULL test on F: the float64 kernel sits at 256
+// registers (two waves per SIMD), and the filter rows must not cost the empirical path a wave.
+template <typename T, bool VEC, bool SHRUNK>
+__device__ __forceinline__ void class_backward_body(const T* __restrict__ points, long long N, int D,
+                                                    const long long* __restrict__ row_index,
+                                                    const long long* __restrict__ row_class,
+                                                    const long long* __restrict__ class_start, const T* __restrict__ means,
+                                                    const T* __restrict__ w, int K, long long V, long long rows_per_group,
+                                                    T* __restrict__ partial, int C, const T* __restrict__ F) {
   using Tr = ProjTraits<T>;
   __shared__ T sXt[CP_CHUNK * CP_PITCH], sWt[CP_CHUNK * CP_PITCH];
   __shared__ const T* sXp[2][CP_CHUNK];
@@ -341,7 +411,8 @@ __global__ __launch_bounds__(CP_THREADS) void class_backward_kernel(const T* __r
   const long long v_hi = v_lo + rows_per_group < V ? v_lo + rows_per_group : V;
   const long long w_end = v_hi * K;
 
-  // the pointers of the rows v0 .. v0+31: a point and its class mean, or (v >= N) the mean of class v - N uncentred
+  // the pointers of the rows v0 .. v0+31: a point and its class mean, or (v >= N) the mean of class v - N uncentred, or
+  // (shrunk, v >= N + C) the filter v - N - C uncentred
   auto fill = [&](int buf, long long v0) {
     if (tid < CP_CHUNK) {
       const long long v = v0 + tid;
@@ -351,8 +422,13 @@ __global__ __launch_bounds__(CP_THREADS) void class_backward_kernel(const T* __r
         if (v < N) {
           xp = points + cp_row(row_index, v) * (size_t)D;
           mp = means + (size_t)row_class[v] * D;
-        } else if (class_start[v - N + 1] - class_start[v - N] >= 1) {   // an empty class's mean is NaN: a row of zeros
-          xp = means + (size_t)(v - N) * D;
+        } else {
+          // one address expression for both kinds of row (filter k = v - N - C: F + k D = (F - C D) + (v - N) D): a branch
+          // of its own for the filters costs the float64 kernel two registers and with them its second wave per SIMD
+          const bool filter = SHRUNK && v >= N + C;
+          const long long c = filter ? 0 : v - N;
+          // an empty class's mean is NaN: a row of zeros
+          if (filter || class_start[c + 1] - class_start[c] >= 1) xp = (filter ? F - (size_t)C * D : means) + (size_t)(v - N) * D;
         }
       }
       sXp[buf][tid] = xp;
@@ -413,6 +489,33 @@ __global__ __launch_bounds__(CP_THREADS) void class_backward_kernel(const T* __r
     }
 }
 
+template <typename T, bool VEC>
+__global__ __launch_bounds__(CP_THREADS) void class_backward_kernel(const T* __restrict__ points, long long N, int D,
+                                                                    const long long* __restrict__ row_index,
+                                                                    const long long* __restrict__ row_class,
+                                                                    const long long* __restrict__ class_start,
+                                                                    const T* __restrict__ means, const T* __restrict__ w,
+                                                                    int K, long long V, long long rows_per_group,
+                                                                    T* __restrict__ partial) {
+  class_backward_body<T, VEC, false>(points, N, D, row_index, row_class, class_start, means, w, K, V, rows_per_group, partial,
+                                     0, nullptr);
+}
+
+// rows N + C .. N + C + K - 1 are the filters F[k,:] uncentred.  Two workgroups per CU asked for: without the bound the
+// float64 instantiation takes 250 + 8 registers, two past the 256 of two waves per SIMD, and runs at half the occupancy.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(CP_THREADS) void class_backward_shrunk_kernel(const T* __restrict__ points, long long N, int D,
+                                                                           const long long* __restrict__ row_index,
+                                                                           const long long* __restrict__ row_class,
+                                                                           const long long* __restrict__ class_start,
+                                                                           const T* __restrict__ means,
+                                                                           const T* __restrict__ w, int K, long long V,
+                                                                           long long rows_per_group, T* __restrict__ partial,
+                                                                           int C, const T* __restrict__ F) {
+  class_backward_body<T, VEC, true>(points, N, D, row_index, row_class, class_start, means, w, K, V, rows_per_group, partial, C,
+                                    F);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 
 struct CpLayout {
@@ -439,6 +542,26 @@ static bool cp_layout(long long N, int C, int D, int K, int dtype, CpLayout* w) 
   return true;
 }
 
+// The shrunk entries: F F^T (K,K) after the Gram partials forward; K more virtual rows and H (K,K) after them backward.
+struct CpShrunkLayout {
+  int split;
+  size_t fft_off, h_off, total;
+};
+
+static bool cp_layout_shrunk(long long N, int C, int D, int K, int dtype, CpShrunkLayout* w) {
+  CpLayout base;
+  if (!cp_layout(N, C, D, K, dtype, &base)) return false;
+  const long long V = N + C + K;
+  if ((V * K + CP_THREADS - 1) / CP_THREADS > (long long)INT_MAX) return false;
+  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
+  w->split = base.split;
+  w->fft_off = (size_t)C * base.split * K * K * esz;
+  w->h_off = (size_t)V * K * esz;
+  const size_t fwd = w->fft_off + (size_t)K * K * esz, bwd = w->h_off + (size_t)K * K * esz;
+  w->total = fwd > bwd ? fwd : bwd;
+  return true;
+}
+
 template <typename T> static bool cp_vec(const void* points, const void* means, const void* F, int D) {
   return (D % ProjTraits<T>::VW) == 0 &&
          ((reinterpret_cast<size_t>(points) | reinterpret_cast<size_t>(means) | reinterpret_cast<size_t>(F)) & 15) == 0;
@@ -447,7 +570,8 @@ template <typename T> static bool cp_vec(const void* points, const void* means, 
 template <typename T>
 static void run_feature_moments(const T* points, long long N, int D, const long long* row_index, const long long* row_class,
                                 const long long* class_start, int C, const T* means, const T* F, int K, double noise,
-                                T* zc, T* means_f, T* cov_f, T* second_f, char* ws, const CpLayout& w, hipStream_t stream) {
+                                T* zc, T* means_f, T* cov_f, T* second_f, char* ws, int split, hipStream_t stream,
+                                const T* keep = nullptr, const T* shift = nullptr, T* fft = nullptr) {
   T* partial = reinterpret_cast<T*>(ws);
   if (N > 0) {
     const unsigned grid = (unsigned)((N + CP_ROWS - 1) / CP_ROWS);
@@ -456,24 +580,39 @@ static void run_feature_moments(const T* points, long long N, int D, const long 
     else
       class_project_kernel<T, false><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, means, F, K, zc);
   }
-  class_gram_kernel<T><<<dim3(C, w.split), CP_THREADS, 0, stream>>>(zc, class_start, K, w.split, partial);
-  class_feature_finish_kernel<T><<<C, CP_THREADS, 0, stream>>>(partial, class_start, means, F, D, K, w.split, (T)noise,
-                                                               means_f, cov_f, second_f);
+  class_gram_kernel<T><<<dim3(C, split), CP_THREADS, 0, stream>>>(zc, class_start, K, split, partial);
+  if (keep != nullptr) {
+    const int waves = K * (K + 1) / 2, per_block = CP_THREADS / 64;
+    filter_gram_kernel<T><<<(waves + per_block - 1) / per_block, CP_THREADS, 0, stream>>>(F, D, K, fft);
+  }
+  class_feature_finish_kernel<T><<<C, CP_THREADS, 0, stream>>>(partial, class_start, means, F, D, K, split, (T)noise,
+                                                               means_f, cov_f, second_f, keep, shift, fft);
 }
 
 template <typename T>
 static void run_feature_backward(const T* points, long long N, int D, const long long* row_index, const long long* row_class,
                                  const long long* class_start, int C, const T* means, const T* zc, const T* G, int ldg,
-                                 const T* g_means, int K, int n_groups, T* partial_out, char* ws, hipStream_t stream) {
+                                 const T* g_means, int K, int n_groups, T* partial_out, char* ws, hipStream_t stream,
+                                 const T* keep = nullptr, const T* shift = nullptr, const T* F = nullptr, T* H = nullptr) {
   T* wbuf = reinterpret_cast<T*>(ws);
-  const long long V = N + (g_means != nullptr ? C : 0);
+  // shrunk: the class rows are always there (zeros without g_means), so that the filter rows start at N + C
+  const long long V = keep != nullptr ? N + C + K : N + (g_means != nullptr ? C : 0);
+  if (keep != nullptr) class_shrink_sum_kernel<T><<<K * K, CP_THREADS, 0, stream>>>(G, ldg, class_start, shift, C, K, H);
   if (V > 0)
     class_weights_kernel<T><<<(unsigned)((V * K + CP_THREADS - 1) / CP_THREADS), CP_THREADS, 0, stream>>>(
-        zc, N, row_class, class_start, G, ldg, g_means, V, K, wbuf);
+        zc, N, row_class, class_start, G, ldg, g_means, V, K, wbuf, C, keep, H);
   long long per = (V + n_groups - 1) / n_groups;
   per = (per + CP_CHUNK - 1) / CP_CHUNK * CP_CHUNK;
   const dim3 grid((D + CP_STRIPE - 1) / CP_STRIPE, n_groups);
-  if (cp_vec<T>(points, means, nullptr, D))
+  const bool vec = cp_vec<T>(points, means, F, D);
+  if (keep != nullptr) {
+    if (vec)
+      class_backward_shrunk_kernel<T, true><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, class_start,
+                                                                             means, wbuf, K, V, per, partial_out, C, F);
+    else
+      class_backward_shrunk_kernel<T, false><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, class_start,
+                                                                              means, wbuf, K, V, per, partial_out, C, F);
+  } else if (vec)
     class_backward_kernel<T, true><<<grid, CP_THREADS, 0, stream>>>(points, N, D, row_index, row_class, class_start, means,
                                                                     wbuf, K, V, per, partial_out);
   else
@@ -508,12 +647,12 @@ extern "C" int sqfa_class_feature_moments(const void* points, long long N, int D
     run_feature_moments(static_cast<const float*>(points), N, D, row_index, row_class, class_start, C,
                         static_cast<const float*>(means), static_cast<const float*>(F), K, noise, static_cast<float*>(zc_out),
                         static_cast<float*>(means_f_out), static_cast<float*>(cov_f_out), static_cast<float*>(second_f_out),
-                        ws, w, stream);
+                        ws, w.split, stream);
   else
     run_feature_moments(static_cast<const double*>(points), N, D, row_index, row_class, class_start, C,
                         static_cast<const double*>(means), static_cast<const double*>(F), K, noise,
                         static_cast<double*>(zc_out), static_cast<double*>(means_f_out), static_cast<double*>(cov_f_out),
-                        static_cast<double*>(second_f_out), ws, w, stream);
+                        static_cast<double*>(second_f_out), ws, w.split, stream);
   return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }
 
@@ -541,5 +680,92 @@ extern "C" int sqfa_class_feature_moments_backward(const void* points, long long
     run_feature_backward(static_cast<const double*>(points), N, D, row_index, row_class, class_start, C,
                          static_cast<const double*>(means), static_cast<const double*>(zc), static_cast<const double*>(G),
                          ldg, static_cast<const double*>(g_means), K, n_groups, static_cast<double*>(partial_out), ws, stream);
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+// ---- the shrunk entries: cov_c -> keep_c cov_c + shift_c I in D-space (OAS; keep, shift from sqfa_class_shrinkage) ---------
+
+extern "C" size_t sqfa_class_feature_moments_shrunk_workspace_bytes(long long N, int C, int D, int K, int dtype) {
+  sqfa::CpShrunkLayout w;
+  if (!sqfa::cp_layout_shrunk(N, C, D, K, dtype, &w)) return 0;
+  return w.total < 16 ? 16 : w.total;
+}
+
+namespace sqfa {
+
+template <typename T>
+static void shrunk_forward(const void* points, long long N, int D, const long long* row_index, const long long* row_class,
+                           const long long* class_start, int C, const void* means, const void* F, int K, double noise,
+                           const void* keep, const void* shift, void* zc, void* means_f, void* cov_f, void* second_f,
+                           char* ws, const CpShrunkLayout& w, hipStream_t stream) {
+  run_feature_moments(static_cast<const T*>(points), N, D, row_index, row_class, class_start, C, static_cast<const T*>(means),
+                      static_cast<const T*>(F), K, noise, static_cast<T*>(zc), static_cast<T*>(means_f),
+                      static_cast<T*>(cov_f), static_cast<T*>(second_f), ws, w.split, stream, static_cast<const T*>(keep),
+                      static_cast<const T*>(shift), reinterpret_cast<T*>(ws + w.fft_off));
+}
+
+template <typename T>
+static void shrunk_backward(const void* points, long long N, int D, const long long* row_index, const long long* row_class,
+                            const long long* class_start, int C, const void* means, const void* F, const void* zc,
+                            const void* G, int ldg, const void* g_means, const void* keep, const void* shift, int K,
+                            int n_groups, void* partial_out, char* ws, const CpShrunkLayout& w, hipStream_t stream) {
+  run_feature_backward(static_cast<const T*>(points), N, D, row_index, row_class, class_start, C,
+                       static_cast<const T*>(means), static_cast<const T*>(zc), static_cast<const T*>(G), ldg,
+                       static_cast<const T*>(g_means), K, n_groups, static_cast<T*>(partial_out), ws, stream,
+                       static_cast<const T*>(keep), static_cast<const T*>(shift), static_cast<const T*>(F),
+                       reinterpret_cast<T*>(ws + w.h_off));
+}
+
+}  // namespace sqfa
+
+extern "C" int sqfa_class_feature_moments_shrunk(const void* points, long long N, int D, const long long* row_index,
+                                                 const long long* row_class, const long long* class_start, int C,
+                                                 const void* means, const void* F, int K, int dtype, double noise,
+                                                 const void* keep, const void* shift, void* zc_out, void* means_f_out,
+                                                 void* cov_f_out, void* second_f_out, void* workspace,
+                                                 size_t workspace_bytes, void* stream_) {
+  using namespace sqfa;
+  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc_out == nullptr)) ||
+      class_start == nullptr || means == nullptr || F == nullptr || keep == nullptr || shift == nullptr ||
+      means_f_out == nullptr || cov_f_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CpShrunkLayout w;
+  if (!cp_layout_shrunk(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  if (dtype == SQFA_F32)
+    shrunk_forward<float>(points, N, D, row_index, row_class, class_start, C, means, F, K, noise, keep, shift, zc_out,
+                          means_f_out, cov_f_out, second_f_out, ws, w, stream);
+  else
+    shrunk_forward<double>(points, N, D, row_index, row_class, class_start, C, means, F, K, noise, keep, shift, zc_out,
+                           means_f_out, cov_f_out, second_f_out, ws, w, stream);
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+extern "C" int sqfa_class_feature_moments_shrunk_backward(const void* points, long long N, int D, const long long* row_index,
+                                                          const long long* row_class, const long long* class_start, int C,
+                                                          const void* means, const void* F, const void* zc, const void* G,
+                                                          int ldg, const void* g_means, const void* keep, const void* shift,
+                                                          int K, int dtype, int n_groups, void* partial_out, void* workspace,
+                                                          size_t workspace_bytes, void* stream_) {
+  using namespace sqfa;
+  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc == nullptr)) ||
+      class_start == nullptr || means == nullptr || F == nullptr || G == nullptr || keep == nullptr || shift == nullptr ||
+      ldg < K || n_groups < 1 || n_groups > 65535 || partial_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CpShrunkLayout w;
+  if (!cp_layout_shrunk(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  if (dtype == SQFA_F32)
+    shrunk_backward<float>(points, N, D, row_index, row_class, class_start, C, means, F, zc, G, ldg, g_means, keep, shift, K,
+                           n_groups, partial_out, ws, w, stream);
+  else
+    shrunk_backward<double>(points, N, D, row_index, row_class, class_start, C, means, F, zc, G, ldg, g_means, keep, shift, K,
+                            n_groups, partial_out, ws, w, stream);
   return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }

@@ -371,7 +371,8 @@ class SecondMomentsSQFA(nn.Module):
         loss becomes -sum_{i>j} W_ij D_ij / sum_{i>j} W_ij (the diagonal is ignored; every stage of a pairwise fit uses the
         same weights).  ``statistics`` (with ``X, y``): "dense" (default) builds the (C,D,D) class statistics once;
         "points" keeps the labelled points (statistics.ClassPoints, also accepted as ``data_statistics``) and every closure
-        computes the class moments of the projected points: nothing of size (C,D,D) is formed (empirical estimator only).
+        computes the class moments of the projected points: nothing of size (C,D,D) is formed (empirical estimator only;
+        for OAS shrinkage without (C,D,D) statistics pass ``data_statistics=ClassPoints(X, y, estimator="oas")``).
         Extra keyword arguments go to torch.optim.LBFGS."""
         if data_statistics is None:
             if X is None or y is None:

@@ -5,7 +5,8 @@ float32 / float64 points on the GPU go through the native segmented SYRK (sqfa_c
 copy of the points, exactly symmetric outputs); CPU tensors and other dtypes keep the batched torch expression.
 ClassStatisticsAccumulator builds the same statistics from batches and merges partial results.
 ClassPoints keeps the labelled points themselves as the statistics of a fit: every closure computes the class moments of
-the projected points (sqfa_class_feature_moments) and nothing of size (C,D,D) is ever formed.
+the projected points (sqfa_class_feature_moments) and nothing of size (C,D,D) is ever formed; with estimator="oas" the
+covariances are shrunk as class_statistics shrinks them, from coefficients measured once (sqfa_class_shrinkage).
 """
 import torch
 
@@ -217,9 +218,19 @@ class ClassPoints:
     is the only host read (none when ``n_classes`` is given).  An empty class has NaN means and feature moments, a class
     of one point a NaN covariance, as ``class_statistics`` gives them.  float32 / float64 points on the GPU go through the
     native kernels (sqfa_class_means, sqfa_class_feature_moments); CPU tensors, other dtypes, more than 64 filters and
-    NATIVE_CLASS_POINTS = False evaluate the same formulas as a torch expression."""
+    NATIVE_CLASS_POINTS = False evaluate the same formulas as a torch expression.
 
-    def __init__(self, points, labels, n_classes=None):
+    ``estimator="oas"`` shrinks every class covariance as ``class_statistics(estimator="oas")`` does, still without forming
+    it:  OAS(S_c) = keep_c S_c + shift_c I  with keep_c = 1 - rho_c and shift_c = rho_c tr S_c / D, so that
+    F OAS(S_c) F^T = keep_c cov(F x | c) + shift_c F F^T.  The coefficients are measured once, here: ``shrink_keep`` and
+    ``shrink_shift`` (C, the points' dtype) and ``shrinkage`` (rho, float64), NaN for a class below two points; all three
+    are None for "empirical".  Natively that is one pass over the points (sqfa_class_shrinkage: the SYRK of the dense OAS
+    statistics without its stores, the same bits of keep and shift); the fallback takes one class at a time and the Gram
+    of the centred rows on their smaller side."""
+
+    def __init__(self, points, labels, n_classes=None, estimator="empirical"):
+        if estimator not in ("empirical", "oas"):
+            raise ValueError("estimator must be 'empirical' or 'oas'")
         if not torch.is_tensor(points) or points.dim() != 2 or not points.is_floating_point():
             raise TypeError("points must be a floating-point tensor of shape (n_points, n_dim)")
         labels = torch.as_tensor(labels).to(points.device).long()   # float labels too, as class_statistics
@@ -247,6 +258,34 @@ class ClassPoints:
             sums = torch.zeros(C, self.n_dim, dtype=torch.float64, device=points.device)
             sums.index_add_(0, labels, self.points.double())
             self.means = (sums / self.counts.double()[:, None]).to(points.dtype)   # 0/0 = NaN for an empty class
+        self.estimator = estimator
+        self.shrink_keep = self.shrink_shift = self.shrinkage = None
+        if estimator == "oas":
+            if NATIVE_CLASS_POINTS and _native_applies(self.points):
+                from . import _native
+                self.shrink_keep, self.shrink_shift, self.shrinkage = _native.class_shrinkage(
+                    self.points, self.order, self.class_start, self.means, C)
+            else:
+                self.shrink_keep, self.shrink_shift, self.shrinkage = self._torch_shrinkage()
+
+    def _torch_shrinkage(self):
+        """(keep, shift, rho) of the OAS shrinkage, one class at a time: S in the dtype through the Gram of the centred rows
+        on their smaller side (||Z^T Z||_F = ||Z Z^T||_F and the traces agree), tr S and sum S o S in double, rho as
+        oas_covariance.  Nothing of size (C,D,D); (D,D) only for a class of more than D points."""
+        C, d = self.n_classes, self.n_dim
+        rho = torch.full((C,), float("nan"), dtype=torch.float64, device=self.points.device)
+        tr = torch.full_like(rho, float("nan"))
+        sizes, starts = self.counts.tolist(), self.class_start.tolist()
+        for c, n in enumerate(sizes):
+            if n < 2:
+                continue
+            Z = self.points[self.order[starts[c]:starts[c] + n]] - self.means[c]
+            S = ((Z @ Z.T) if n <= d else (Z.T @ Z)) / (n - 1)
+            t = torch.diagonal(S).double().sum()
+            t2 = (S.double() ** 2).sum()
+            r = ((1 - 2 / d) * t2 + t * t) / ((n + 1 - 2 / d) * (t2 - t * t / d))   # 0/0 = NaN stays NaN under the clamp
+            rho[c], tr[c] = torch.clamp(r, max=1.0), t
+        return (1 - rho).to(self.points.dtype), (rho * tr / d).to(self.points.dtype), rho
 
     @property
     def dtype(self):
@@ -289,7 +328,15 @@ class ClassPoints:
         # NaN where class_statistics has it (no covariance below two points, no mean of no point), placed by `where` so that
         # the gradient of the other classes stays finite
         denom = (self.counts - 1).clamp(min=1).to(dtype)
-        cov = torch.where((self.counts >= 2)[:, None, None], gram / denom[:, None, None], nan)
+        full = (self.counts >= 2)[:, None, None]
+        cov = gram / denom[:, None, None]
+        if self.shrink_keep is not None:   # keep_c cov(F x | c) + shift_c F F^T; the NaN coefficients of the classes
+            # below two points are replaced before the product, so that no gradient passes through them
+            zero = torch.zeros((), dtype=dtype, device=z.device)
+            keep = torch.where(full, self.shrink_keep.to(dtype)[:, None, None], zero)
+            shift = torch.where(full, self.shrink_shift.to(dtype)[:, None, None], zero)
+            cov = keep * cov + shift * (F @ F.T)
+        cov = torch.where(full, cov, nan)
         if noise:
             cov = cov + noise * torch.eye(K, dtype=dtype, device=z.device)
         present = (self.counts > 0)[:, None]
@@ -299,8 +346,11 @@ class ClassPoints:
             stats["second_moments"] = cov + m[:, :, None] * m[:, None, :]
         return stats
 
-    def class_statistics(self, estimator="empirical"):
-        """The dense {'means', 'covariances', 'second_moments'} of the same points (for comparison: (C,D,D) tensors)."""
+    def class_statistics(self, estimator=None):
+        """The dense {'means', 'covariances', 'second_moments'} of the same points (for comparison: (C,D,D) tensors);
+        `estimator` defaults to this object's own."""
+        if estimator is None:
+            estimator = self.estimator
         stats = class_statistics(self.points, self.labels, estimator=estimator)
         missing = self.n_classes - stats["means"].shape[0]   # classes beyond the largest label: empty
         if missing > 0:

@@ -418,6 +418,39 @@ int sqfa_log_euclidean_pairwise_loss_weighted(const void *S, int n, int m, int d
                                               void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Fused closure loss of the Jeffreys divergence (the symmetric Kullback-Leibler divergence) between the n class Gaussians
+ * N(mu_c, Sigma_c): with P_c = Sigma_c^-1 and delta = mu_i - mu_j,
+ *     J_ij = KL(i||j) + KL(j||i) = -1/2 <P_i - P_j, Sigma_i - Sigma_j> + 1/2 delta^T (P_i + P_j) delta
+ *     sqrt_mode 0   D_ij = J_ij
+ *     sqrt_mode 1   D_ij = sqrt(J_ij + eps)
+ *     loss = sum_{i>j} w_ij D_ij,  w_ij = uniform_weight, or pair_weights[i*n + j]
+ * together with its gradient wrt mu and Sigma.  Stages, all on the caller's stream (jeffreys_kernel.hip): per-class
+ * precisions (Cholesky and triangular inverse, double inside; exactly symmetric); ONE pass over the ordered pairs in the
+ * explicit-difference form above (the textbook form with two traces cancels the digits that matter for close classes), O(m^2)
+ * per pair, every class row with one writer; a per-class finish gcov_i = GSigma_i - P_i sym(GP_i) P_i; a one-workgroup
+ * reduction of the per-class partial losses and counters.  No host read-back, no allocation, no float atomics: results are
+ * bitwise reproducible and the call may be captured in a HIP graph.
+ *   mu (n,m) or NULL (zero means: the divergence of the SPD matrices themselves), cov (n,m,m): row-major, dtype;
+ *   n >= 2, 1 <= m <= 64
+ *   pair_weights (n,n) dtype, symmetric, or NULL (then uniform_weight).  The pass visits the ordered pairs: row i reads w_ij,
+ *   row j reads w_ji, the loss counts j < i with w_ij.  The diagonal is never read into a result.  Every pair is evaluated
+ *   and counted in nonfinite_out whatever its weight; dist_out is unweighted.
+ *   loss_out (1) dtype or NULL; gmu_out (n,m) and gcov_out (n,m,m, exactly symmetric): both or neither (NULL, NULL = forward
+ *   only); with mu == NULL gmu_out must be NULL and gcov_out alone selects the gradient; dist_out (n,n) or NULL: D_ij, both
+ *   triangles, the diagonal 0 or sqrt(eps); nonfinite_out (2) int32 or NULL: {#NaN, #inf} among the pairs i > j (a class that
+ *   is not positive definite yields NaN and is counted, never a fault)
+ *   workspace: sqfa_jeffreys_workspace_bytes(n, m, dtype) bytes (0 = shape or dtype not supported)
+ * Returns SQFA_ERR_BAD_ARGUMENT (null cov, n < 2, m < 1, dtype, sqrt_mode outside {0, 1}, gmu_out / gcov_out as above),
+ * SQFA_ERR_UNSUPPORTED_M (m > 64), SQFA_ERR_WORKSPACE, checked in that order; every argument check runs before the first
+ * HIP call.
+ */
+size_t sqfa_jeffreys_workspace_bytes(int n, int m, int dtype);
+int sqfa_jeffreys_pairwise_loss(const void *mu, const void *cov, int n, int m, int dtype, int sqrt_mode,
+                                double eps, const void *pair_weights, double uniform_weight,
+                                void *loss_out, void *gmu_out, void *gcov_out, void *dist_out, int *nonfinite_out,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the
  * reference (src/sqfa/linalg.py:165-183, 121-141: torch.linalg.eigh + einsum), as used by log_euclidean[_sq]
  * (src/sqfa/distances.py:92-138).  The eigen-decomposition is one-sided Jacobi, run to convergence, on the Cholesky

@@ -574,6 +574,67 @@ class LogEuclideanPairwiseLoss(_SavedGradientLoss):
         return _SavedGradientLoss._saved(ctx, 5, out["loss"], out["nonfinite"], out["gS"])
 
 
+# ------------------------------------------------------------------------------------------
+# Jeffreys divergence (divergences.py): per-class precisions, one O(m^2) pass over the class pairs (jeffreys_kernel.hip)
+
+JEFFREYS_MAX_DIM = 64
+
+
+def hip_jeffreys_pairwise_loss(mu, cov, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_jeffreys_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe
+    inside a graph capture).  cov (n,m,m) SPD, mu (n,m) or None (zero means); `pair_weights`: symmetric (n,n) per-pair
+    weights in place of `weight`.  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested; gmu None
+    without means)."""
+    lib = _lib.load()
+    if not cov.is_cuda:
+        raise RuntimeError("sqfa_amd's fused Jeffreys pair loss runs on the GPU only (no CPU fallback)")
+    if mu is not None and (mu.device != cov.device or mu.dtype != cov.dtype):
+        raise ValueError("means and covariances must share device and dtype")
+    cov = cov.detach().contiguous()
+    mu = mu.detach().contiguous() if mu is not None else None
+    n, m = cov.shape[0], cov.shape[-1]
+    if m > JEFFREYS_MAX_DIM:
+        raise NotImplementedError(f"feature dimension {m} exceeds the native Jeffreys kernels' limit ({JEFFREYS_MAX_DIM})")
+    code = _dtype_code(cov)
+    dev, dt = cov.device, cov.dtype
+    with _on_stream(dev) as stream:
+        ws, nbytes = _workspace(lib.sqfa_jeffreys_workspace_bytes, n, m, code)
+        loss = torch.empty((), dtype=dt, device=dev)
+        nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
+        gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad and mu is not None else None
+        gcov = torch.empty((n, m, m), dtype=dt, device=dev) if want_grad else None
+        dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
+        W = _pair_weight_matrix(pair_weights, n, dt, dev)
+        status = lib.sqfa_jeffreys_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(bool(sqrt_mode)), float(eps), _ptr(W),
+                                                 0.0 if W is not None else float(weight), _ptr(loss), _ptr(gmu), _ptr(gcov),
+                                                 _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes, stream)
+    _lib.check(status, "sqfa_jeffreys_pairwise_loss")
+    return {"loss": loss, "gmu": gmu, "gcov": gcov, "dist": dist, "nonfinite": nonfinite}
+
+
+class JeffreysPairwiseLoss(_SavedGradientLoss):
+    """Fused closure loss of jeffreys / jeffreys_spd (sqrt_mode False) and their _root forms (True): weight * sum over the
+    unordered class pairs, with its gradient wrt means (C,K) (None for the means-free operators) and covariances (C,K,K),
+    from ONE pass over the pairs (sqfa_jeffreys_pairwise_loss) -- in place of inv -> the (C,C,K,K) difference tensors ->
+    tril gather -> mean and their autograd backward.  Returns (loss, flags {#NaN, #inf})."""
+
+    @staticmethod
+    def forward(ctx, means, covariances, sqrt_mode, eps, weight, pair_weights=None):
+        out = hip_jeffreys_pairwise_loss(means, covariances, sqrt_mode, eps, weight, pair_weights=pair_weights)
+        ctx.has_means = means is not None
+        if means is None:
+            ctx.save_for_backward(out["gcov"])
+        else:
+            ctx.save_for_backward(out["gmu"], out["gcov"])
+        ctx.mark_non_differentiable(out["nonfinite"])
+        return out["loss"], out["nonfinite"]
+
+    @staticmethod
+    def backward(ctx, gloss, _gflag):
+        grads = tuple(g * gloss for g in ctx.saved_tensors)
+        return ((None,) if not ctx.has_means else ()) + grads + (None,) * 4
+
+
 def spd_function(M, kind):
     """(..., m, m) -> (..., m, m) on the native kernels (the caller has checked spd_function_supported)."""
     lead = M.shape[:-2]

@@ -874,6 +874,9 @@ static int fail(int code, const char* what, hipError_t e) {
   return code;
 }
 
+// for the entry points of other translation units (jeffreys_kernel.hip): the text sqfa_hip_last_error() returns
+void set_last_error(const char* text) { snprintf(g_last_error, sizeof(g_last_error), "%s", text); }
+
 static int clamp_policy(int v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); }
 static bool known_dtype(int dtype) { return dtype == SQFA_F32 || dtype == SQFA_F64; }
 

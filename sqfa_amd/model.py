@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 from torch.nn.utils.parametrize import register_parametrization, remove_parametrizations
 
-from . import _native, distances
+from . import _native, distances, divergences
 from ._memo import TensorMemo
 from ._optim import fitting_loop
 from .constraints import FixedFilters, Identity, Orthogonal, Sphere, orthogonal
@@ -227,6 +227,7 @@ class SecondMomentsSQFA(nn.Module):
         sharded = self.pair_shard is not None or self.class_shard is not None
         spec = distances.fused_spec(fn)
         cspec = distances.class_fused_spec(fn) if spec is None else None
+        jspec = divergences.fused_spec(fn) if spec is None and cspec is None else None
         plan = inputs = None
         if spec is not None and spec[0] == self._fused_kind and spec[3] != "gauss":
             # affine-invariant / Bures-Wasserstein pair kernels: any device (through _pair_backend), any sharding
@@ -267,6 +268,28 @@ class SecondMomentsSQFA(nn.Module):
                     and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
                 return None
             plan = ClosurePlan("log_euclidean", None, cspec[1], None, None, (0, 1), None, None)
+        elif jspec is not None and jspec[0] == self._fused_kind:
+            # jeffreys[_root] (SQFA, a dict) / jeffreys_spd[_root] (SecondMomentsSQFA, a tensor): single process,
+            # <= JEFFREYS_MAX_DIM filters, float32/64 GPU statistics
+            if sharded or nm.shape[0] > _native.JEFFREYS_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
+                return None
+            if isinstance(prepared, ClassPoints):
+                if not (prepared.points.is_cuda and prepared.n_classes >= 2
+                        and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
+                    return None
+            elif prepared is not None and jspec[0] == "gaussian":
+                if not isinstance(prepared, dict):
+                    return None
+                mu, cov = prepared["means"], prepared["covariances"]
+                cov_dtype = torch.promote_types(cov.dtype, nm.dtype)   # of F cov F^T + noise_mat
+                if not (cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[0] >= 2 and cov_dtype in _NATIVE_DTYPES
+                        and mu.dtype == cov_dtype and mu.device == cov.device):
+                    return None
+            elif prepared is not None and not (
+                    torch.is_tensor(prepared) and prepared.dim() == 3 and prepared.is_cuda and prepared.shape[0] >= 2
+                    and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
+                return None
+            plan = ClosurePlan("jeffreys", None, jspec[1], None, None, (0, 1), None, None)
         if plan is None or prepared is None:
             return plan
         return plan._replace(weight=self._pair_weight(self._n_classes_total(prepared)), inputs=inputs,
@@ -303,6 +326,16 @@ class SecondMomentsSQFA(nn.Module):
         """parametrization -> projection (native where it applies) -> noise -> _native.LogEuclideanPairwiseLoss."""
         return _native.LogEuclideanPairwiseLoss.apply(self._feature_scatters(prepared, True), plan.sqrt_mode,
                                                       distances.EPSILON, plan.weight, plan.pair_weights)
+
+    def _evaluate_jeffreys(self, plan, prepared):
+        """parametrization -> projection (native where it applies) -> noise -> _native.JeffreysPairwiseLoss: with the
+        feature means and covariances (SQFA), or the feature scatters and zero means (SecondMomentsSQFA)."""
+        if self._fused_kind == "gaussian":
+            stats = self._feature_statistics(prepared, True)
+            mu, cov = stats["means"], stats["covariances"]
+        else:
+            mu, cov = None, self._feature_scatters(prepared, True)
+        return _native.JeffreysPairwiseLoss.apply(mu, cov, plan.sqrt_mode, distances.EPSILON, plan.weight, plan.pair_weights)
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once

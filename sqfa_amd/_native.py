@@ -6,6 +6,7 @@ the hot path happens inside libsqfa_hip.so.  The single call site of the library
 functions call through); it refuses CPU tensors and there is no other implementation in
 this package.
 """
+import collections
 import ctypes
 import math
 
@@ -251,15 +252,18 @@ class _SavedGradientLoss(torch.autograd.Function):
 
     @staticmethod
     def _saved(ctx, n_inputs, loss, nonfinite, *grads):
-        ctx.save_for_backward(*grads)
+        """`grads`: one per leading input, None for an absent one (the means of a means-free loss)."""
+        ctx.save_for_backward(*(g for g in grads if g is not None))
+        ctx.present = tuple(g is not None for g in grads)
         ctx.n_inputs = n_inputs
         ctx.mark_non_differentiable(nonfinite)
         return loss, nonfinite
 
     @staticmethod
     def backward(ctx, gloss, _gflag):
-        grads = ctx.saved_tensors
-        return tuple(g * gloss for g in grads) + (None,) * (ctx.n_inputs - len(grads))
+        saved = iter(ctx.saved_tensors)
+        grads = tuple(next(saved) * gloss if present else None for present in ctx.present)
+        return grads + (None,) * (ctx.n_inputs - len(grads))
 
 
 class PairwiseLoss(_SavedGradientLoss):
@@ -427,66 +431,116 @@ def _pair_weight_matrix(pair_weights, n, dtype, device):
     return W
 
 
-def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
-    """sqfa_gauss_pairwise_loss[_weighted] on the current stream (no host read-back, workspace from the torch allocator:
-    safe inside a graph capture).  `pair_weights`: symmetric (n,n) per-pair weights in place of `weight` (never padded: the
-    identity padding below changes K, not the classes).  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not
-    requested)."""
+# ------------------------------------------------------------------------------------------
+# fused class-pair losses: per-class pre-stages, ONE pass over the ordered class pairs, a one-workgroup reduction
+
+SPD_FUNCTION_MAX_DIM = 64   # the per-class SPD functions (log_euclidean's pre-stage; see spd_function_supported)
+JEFFREYS_MAX_DIM = 64
+
+# One row per family.  entry: the C entry that takes pair weights (NULL: uniform); name: what _lib.check reports; query: the
+# workspace query; limit: the largest matrix size; means: whether the entry takes means and returns their gradient; what,
+# size_error: the wording of the family's error messages.
+PairFamily = collections.namedtuple("PairFamily", "entry name query limit means what size_error")
+PAIR_FAMILIES = {
+    "gauss": PairFamily("sqfa_gauss_pairwise_loss_weighted", "sqfa_gauss_pairwise_loss", "sqfa_gauss_pairwise_workspace_bytes",
+                        GAUSS_MAX_DIM, True, "Gaussian",
+                        "feature dimension {m} exceeds the native Gaussian pair kernels' limit ({limit})"),
+    "log_euclidean": PairFamily("sqfa_log_euclidean_pairwise_loss_weighted", "sqfa_log_euclidean_pairwise_loss",
+                                "sqfa_log_euclidean_workspace_bytes", SPD_FUNCTION_MAX_DIM, False, "log-Euclidean",
+                                "matrix size {m} exceeds the native per-class SPD functions' limit ({limit})"),
+    "jeffreys": PairFamily("sqfa_jeffreys_pairwise_loss", "sqfa_jeffreys_pairwise_loss", "sqfa_jeffreys_workspace_bytes",
+                           JEFFREYS_MAX_DIM, True, "Jeffreys",
+                           "feature dimension {m} exceeds the native Jeffreys kernels' limit ({limit})"),
+}
+
+
+def _class_pair_call(family, mu, cov, mode, eps, weight, want_grad, want_dist, pair_weights):
+    """One fused class-pair loss on the current stream (no host read-back, workspace from the torch allocator: safe inside
+    a graph capture): cov (n,m,m) SPD, mu (n,m) or None, `mode` the family's kind code / sqrt_mode, `pair_weights` symmetric
+    (n,n) per-pair weights in place of `weight`.  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested;
+    gmu None without means)."""
+    fam = PAIR_FAMILIES[family]
     lib = _lib.load()
     if not cov.is_cuda:
-        raise RuntimeError("sqfa_amd's fused Gaussian pair loss runs on the GPU only (no CPU fallback)")
-    if mu.device != cov.device or mu.dtype != cov.dtype:
+        raise RuntimeError(f"sqfa_amd's fused {fam.what} pair loss runs on the GPU only (no CPU fallback)")
+    if mu is not None and (mu.device != cov.device or mu.dtype != cov.dtype):
         raise ValueError("means and covariances must share device and dtype")
-    mu, cov = mu.detach().contiguous(), cov.detach().contiguous()
+    cov = cov.detach().contiguous()
+    mu = mu.detach().contiguous() if mu is not None else None
     n, m = cov.shape[0], cov.shape[-1]
-    if m > GAUSS_MAX_DIM:
-        raise NotImplementedError(f"feature dimension {m} exceeds the native Gaussian pair kernels' limit ({GAUSS_MAX_DIM})")
-    m_true, m = m, _gauss_padded_size(m, n * n)
-    if m != m_true:
-        mu, cov = _pad_gauss(mu, cov, m)
+    if m > fam.limit:
+        raise NotImplementedError(fam.size_error.format(m=m, limit=fam.limit))
     code = _dtype_code(cov)
     dev, dt = cov.device, cov.dtype
     with _on_stream(dev) as stream:
-        ws, nbytes = _workspace(lib.sqfa_gauss_pairwise_workspace_bytes, n, m, code)
+        ws, nbytes = _workspace(getattr(lib, fam.query), n, m, code)
         loss = torch.empty((), dtype=dt, device=dev)
         nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
-        gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad else None
+        gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad and mu is not None else None
         gcov = torch.empty((n, m, m), dtype=dt, device=dev) if want_grad else None
         dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        if pair_weights is None:
-            status = lib.sqfa_gauss_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), float(weight),
-                                                  _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist), _ptr(nonfinite),
-                                                  _ptr(ws), nbytes, stream)
-        else:
-            W = _pair_weight_matrix(pair_weights, n, dt, dev)
-            status = lib.sqfa_gauss_pairwise_loss_weighted(_ptr(mu), _ptr(cov), n, m, code, int(kind), float(eps), _ptr(W),
-                                                           0.0, _ptr(loss), _ptr(gmu), _ptr(gcov), _ptr(dist),
-                                                           _ptr(nonfinite), _ptr(ws), nbytes, stream)
-    _lib.check(status, "sqfa_gauss_pairwise_loss")
-    if m != m_true and want_grad:
-        gmu, gcov = gmu[:, :m_true].contiguous(), gcov[:, :m_true, :m_true].contiguous()
+        W = _pair_weight_matrix(pair_weights, n, dt, dev)
+        means_in, means_out = ((_ptr(mu),), (_ptr(gmu),)) if fam.means else ((), ())
+        status = getattr(lib, fam.entry)(*means_in, _ptr(cov), n, m, code, int(mode), float(eps), _ptr(W),
+                                         0.0 if W is not None else float(weight), _ptr(loss), *means_out, _ptr(gcov),
+                                         _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes, stream)
+    _lib.check(status, fam.name)
     return {"loss": loss, "gmu": gmu, "gcov": gcov, "dist": dist, "nonfinite": nonfinite}
 
 
-class GaussPairwiseLoss(_SavedGradientLoss):
-    """Fused closure loss of the Gaussian pair distances (kind: _lib.SQFA_GAUSS_*): weight * sum over the unordered
-    class pairs of bhattacharyya / hellinger / mahalanobis[_sq], with its gradient wrt means (C,K) and covariances
-    (C,K,K), from ONE pass over the pairs (sqfa_gauss_pairwise_loss) -- in place of GaussPairTerms forward + the
-    element-wise chain + its backward + GaussPairTerms backward.  Returns (loss, flags {#NaN, #inf})."""
+def class_pair_loss(family, mu, cov, mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """_class_pair_call, with the Gaussian family's identity padding around it (`pair_weights` are never padded: the
+    padding changes K, not the classes)."""
+    m = cov.shape[-1]
+    M = _gauss_padded_size(m, cov.shape[0] * cov.shape[0]) if family == "gauss" else m
+    if M != m:
+        mu, cov = _pad_gauss(mu.detach(), cov.detach(), M)
+    out = _class_pair_call(family, mu, cov, mode, eps, weight, want_grad, want_dist, pair_weights)
+    if M != m and want_grad:
+        out["gmu"], out["gcov"] = out["gmu"][:, :m].contiguous(), out["gcov"][:, :m, :m].contiguous()
+    return out
+
+
+def hip_gauss_pairwise_loss(mu, cov, kind, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_gauss_pairwise_loss_weighted on the current stream (class_pair_loss, family "gauss"; kind: _lib.SQFA_GAUSS_*).
+    Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested)."""
+    return class_pair_loss("gauss", mu, cov, kind, eps, weight, want_grad, want_dist, pair_weights)
+
+
+def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_log_euclidean_pairwise_loss_weighted on the current stream (class_pair_loss, family "log_euclidean"): S (n,m,m)
+    SPD.  Returns dict(loss, gS, dist, nonfinite) (None where not requested)."""
+    out = class_pair_loss("log_euclidean", None, S, bool(sqrt_mode), eps, weight, want_grad, want_dist, pair_weights)
+    return {"loss": out["loss"], "gS": out["gcov"], "dist": out["dist"], "nonfinite": out["nonfinite"]}
+
+
+def hip_jeffreys_pairwise_loss(mu, cov, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_jeffreys_pairwise_loss on the current stream (class_pair_loss, family "jeffreys"): cov (n,m,m) SPD, mu (n,m) or
+    None (zero means).  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested; gmu None without means)."""
+    return class_pair_loss("jeffreys", mu, cov, bool(sqrt_mode), eps, weight, want_grad, want_dist, pair_weights)
+
+
+class ClassPairLoss(_SavedGradientLoss):
+    """Fused closure loss of a class-pair family (PAIR_FAMILIES): weight * sum over the unordered class pairs of the
+    distance, with its gradient wrt means (C,K) (None for a means-free loss: log_euclidean, jeffreys_spd) and covariances
+    (C,K,K), from ONE native call -- in place of the operator's torch / per-pair-term expression, the tril gather, the mean
+    and their autograd backward.  family "gauss": bhattacharyya / hellinger / mahalanobis[_sq] (mode: _lib.SQFA_GAUSS_*);
+    "log_euclidean": log_euclidean (mode True) / log_euclidean_sq (False), the pass over the pairs between the per-class
+    logarithm and its Daleckii-Krein backward; "jeffreys": jeffreys[_spd] (mode False) / their _root forms (True).
+    Returns (loss, flags {#NaN, #inf})."""
 
     @staticmethod
-    def forward(ctx, means, covariances, kind, eps, weight, pair_weights=None):
-        out = hip_gauss_pairwise_loss(means, covariances, kind, eps, weight, pair_weights=pair_weights)
-        return _SavedGradientLoss._saved(ctx, 6, out["loss"], out["nonfinite"], out["gmu"], out["gcov"])
+    def forward(ctx, means, covariances, family, mode, eps, weight, pair_weights=None):
+        out = class_pair_loss(family, means, covariances, mode, eps, weight, pair_weights=pair_weights)
+        return _SavedGradientLoss._saved(ctx, 7, out["loss"], out["nonfinite"], out["gmu"], out["gcov"])
 
 
 # ------------------------------------------------------------------------------------------
 # per-class matrix functions (spd_log / spd_sqrt: log_euclidean's building block)
 
 SPD_LOG, SPD_SQRT, SPD_INV_SQRT = 0, 1, 2
-# the per-class SPD functions have their own size limit (the pair kernels go to sqfa_hip_max_dim() = 128); larger
-# matrices keep the eigh path of linalg.py
-SPD_FUNCTION_MAX_DIM = 64
+# the per-class SPD functions have their own size limit, SPD_FUNCTION_MAX_DIM (the pair kernels go to sqfa_hip_max_dim() =
+# 128); larger matrices keep the eigh path of linalg.py
 
 
 def spd_function_supported(M):
@@ -528,111 +582,6 @@ class SpdFunction(torch.autograd.Function):
             _lib.check(lib.sqfa_spd_function_backward(_ptr(U), _ptr(lam), _ptr(G), n, m, _dtype_code(G), ctx.kind, _ptr(gS), stream),
                        "sqfa_spd_function_backward")
         return gS, None
-
-
-def hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
-    """sqfa_log_euclidean_pairwise_loss[_weighted] on the current stream (no host read-back, workspace from the torch
-    allocator: safe inside a graph capture).  S (n,m,m) SPD; `pair_weights`: symmetric (n,n) per-pair weights in place of
-    `weight`.  Returns dict(loss, gS, dist, nonfinite) (None where not requested)."""
-    lib = _lib.load()
-    if not S.is_cuda:
-        raise RuntimeError("sqfa_amd's fused log-Euclidean pair loss runs on the GPU only (no CPU fallback)")
-    S = S.detach().contiguous()
-    n, m = S.shape[0], S.shape[-1]
-    if m > SPD_FUNCTION_MAX_DIM:
-        raise NotImplementedError(f"matrix size {m} exceeds the native per-class SPD functions' limit ({SPD_FUNCTION_MAX_DIM})")
-    code = _dtype_code(S)
-    dev, dt = S.device, S.dtype
-    with _on_stream(dev) as stream:
-        ws, nbytes = _workspace(lib.sqfa_log_euclidean_workspace_bytes, n, m, code)
-        loss = torch.empty((), dtype=dt, device=dev)
-        nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
-        gS = torch.empty_like(S) if want_grad else None
-        dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        if pair_weights is None:
-            status = lib.sqfa_log_euclidean_pairwise_loss(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps), float(weight),
-                                                          _ptr(loss), _ptr(gS), _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes,
-                                                          stream)
-        else:
-            W = _pair_weight_matrix(pair_weights, n, dt, dev)
-            status = lib.sqfa_log_euclidean_pairwise_loss_weighted(_ptr(S), n, m, code, int(bool(sqrt_mode)), float(eps),
-                                                                   _ptr(W), 0.0, _ptr(loss), _ptr(gS), _ptr(dist),
-                                                                   _ptr(nonfinite), _ptr(ws), nbytes, stream)
-    _lib.check(status, "sqfa_log_euclidean_pairwise_loss")
-    return {"loss": loss, "gS": gS, "dist": dist, "nonfinite": nonfinite}
-
-
-class LogEuclideanPairwiseLoss(_SavedGradientLoss):
-    """Fused closure loss of log_euclidean (sqrt_mode True) / log_euclidean_sq (False): weight * sum over the unordered
-    class pairs, with its gradient wrt the (C,K,K) SPD matrices, from ONE pass over the pairs between the per-class
-    logarithm and its Daleckii-Krein backward (sqfa_log_euclidean_pairwise_loss) -- in place of SpdFunction forward ->
-    cdist -> square / sqrt -> tril gather -> mean and their autograd backward.  Returns (loss, flags {#NaN, #inf})."""
-
-    @staticmethod
-    def forward(ctx, S, sqrt_mode, eps, weight, pair_weights=None):
-        out = hip_log_euclidean_pairwise_loss(S, sqrt_mode, eps, weight, pair_weights=pair_weights)
-        return _SavedGradientLoss._saved(ctx, 5, out["loss"], out["nonfinite"], out["gS"])
-
-
-# ------------------------------------------------------------------------------------------
-# Jeffreys divergence (divergences.py): per-class precisions, one O(m^2) pass over the class pairs (jeffreys_kernel.hip)
-
-JEFFREYS_MAX_DIM = 64
-
-
-def hip_jeffreys_pairwise_loss(mu, cov, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
-    """sqfa_jeffreys_pairwise_loss on the current stream (no host read-back, workspace from the torch allocator: safe
-    inside a graph capture).  cov (n,m,m) SPD, mu (n,m) or None (zero means); `pair_weights`: symmetric (n,n) per-pair
-    weights in place of `weight`.  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested; gmu None
-    without means)."""
-    lib = _lib.load()
-    if not cov.is_cuda:
-        raise RuntimeError("sqfa_amd's fused Jeffreys pair loss runs on the GPU only (no CPU fallback)")
-    if mu is not None and (mu.device != cov.device or mu.dtype != cov.dtype):
-        raise ValueError("means and covariances must share device and dtype")
-    cov = cov.detach().contiguous()
-    mu = mu.detach().contiguous() if mu is not None else None
-    n, m = cov.shape[0], cov.shape[-1]
-    if m > JEFFREYS_MAX_DIM:
-        raise NotImplementedError(f"feature dimension {m} exceeds the native Jeffreys kernels' limit ({JEFFREYS_MAX_DIM})")
-    code = _dtype_code(cov)
-    dev, dt = cov.device, cov.dtype
-    with _on_stream(dev) as stream:
-        ws, nbytes = _workspace(lib.sqfa_jeffreys_workspace_bytes, n, m, code)
-        loss = torch.empty((), dtype=dt, device=dev)
-        nonfinite = torch.empty(2, dtype=torch.int32, device=dev)
-        gmu = torch.empty((n, m), dtype=dt, device=dev) if want_grad and mu is not None else None
-        gcov = torch.empty((n, m, m), dtype=dt, device=dev) if want_grad else None
-        dist = torch.empty((n, n), dtype=dt, device=dev) if want_dist else None
-        W = _pair_weight_matrix(pair_weights, n, dt, dev)
-        status = lib.sqfa_jeffreys_pairwise_loss(_ptr(mu), _ptr(cov), n, m, code, int(bool(sqrt_mode)), float(eps), _ptr(W),
-                                                 0.0 if W is not None else float(weight), _ptr(loss), _ptr(gmu), _ptr(gcov),
-                                                 _ptr(dist), _ptr(nonfinite), _ptr(ws), nbytes, stream)
-    _lib.check(status, "sqfa_jeffreys_pairwise_loss")
-    return {"loss": loss, "gmu": gmu, "gcov": gcov, "dist": dist, "nonfinite": nonfinite}
-
-
-class JeffreysPairwiseLoss(_SavedGradientLoss):
-    """Fused closure loss of jeffreys / jeffreys_spd (sqrt_mode False) and their _root forms (True): weight * sum over the
-    unordered class pairs, with its gradient wrt means (C,K) (None for the means-free operators) and covariances (C,K,K),
-    from ONE pass over the pairs (sqfa_jeffreys_pairwise_loss) -- in place of inv -> the (C,C,K,K) difference tensors ->
-    tril gather -> mean and their autograd backward.  Returns (loss, flags {#NaN, #inf})."""
-
-    @staticmethod
-    def forward(ctx, means, covariances, sqrt_mode, eps, weight, pair_weights=None):
-        out = hip_jeffreys_pairwise_loss(means, covariances, sqrt_mode, eps, weight, pair_weights=pair_weights)
-        ctx.has_means = means is not None
-        if means is None:
-            ctx.save_for_backward(out["gcov"])
-        else:
-            ctx.save_for_backward(out["gmu"], out["gcov"])
-        ctx.mark_non_differentiable(out["nonfinite"])
-        return out["loss"], out["nonfinite"]
-
-    @staticmethod
-    def backward(ctx, gloss, _gflag):
-        grads = tuple(g * gloss for g in ctx.saved_tensors)
-        return ((None,) if not ctx.has_means else ()) + grads + (None,) * 4
 
 
 def spd_function(M, kind):
@@ -769,35 +718,35 @@ def point_backward_groups(N, D):
     return max(1, min(64, -(-1024 // stripes), -(-max(N, 1) // 32)))
 
 
+def _feature_moments_entry(cp, suffix=""):
+    """(shrinkage coefficients or (), entry name, workspace query) for a ClassPoints: one with shrinkage coefficients
+    (estimator="oas") goes through the _shrunk entries, which take `keep` and `shift` (and the filters, backward) as well."""
+    keep, shift = getattr(cp, "shrink_keep", None), getattr(cp, "shrink_shift", None)
+    shrink = () if keep is None else (keep, shift)
+    name = "sqfa_class_feature_moments" + ("_shrunk" if shrink else "")
+    return shrink, name + suffix, getattr(_lib.load(), name + "_workspace_bytes")
+
+
 def class_feature_moments(cp, F, second_moments, noise):
     """sqfa_class_feature_moments on the current stream for a statistics.ClassPoints `cp` and contiguous filters F (K,D):
     (zc (N,K) in grouped order, means_f (C,K), cov_f (C,K,K), second_f (C,K,K) or None).  A `cp` with shrinkage
     coefficients (estimator="oas") goes through sqfa_class_feature_moments_shrunk."""
-    lib = _lib.load()
     X = cp.points
     N, D = X.shape
     K, C = F.shape[0], cp.n_classes
     code = _dtype_code(X)
     dev, dt = X.device, X.dtype
-    keep, shift = getattr(cp, "shrink_keep", None), getattr(cp, "shrink_shift", None)
-    query = lib.sqfa_class_feature_moments_workspace_bytes if keep is None else lib.sqfa_class_feature_moments_shrunk_workspace_bytes
+    shrink, name, query = _feature_moments_entry(cp)
     with _on_stream(dev) as stream:
         ws, nbytes = _workspace(query, N, C, D, K, code)
         zc = torch.empty((N, K), dtype=dt, device=dev)
         means_f = torch.empty((C, K), dtype=dt, device=dev)
         cov_f = torch.empty((C, K, K), dtype=dt, device=dev)
         second_f = torch.empty((C, K, K), dtype=dt, device=dev) if second_moments else None
-        if keep is None:
-            _lib.check(lib.sqfa_class_feature_moments(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class), _ptr(cp.class_start), C,
-                                                      _ptr(cp.means), _ptr(F), K, code, float(noise), _ptr(zc), _ptr(means_f),
-                                                      _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream),
-                       "sqfa_class_feature_moments")
-        else:
-            _lib.check(lib.sqfa_class_feature_moments_shrunk(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
-                                                             _ptr(cp.class_start), C, _ptr(cp.means), _ptr(F), K, code,
-                                                             float(noise), _ptr(keep), _ptr(shift), _ptr(zc), _ptr(means_f),
-                                                             _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream),
-                       "sqfa_class_feature_moments_shrunk")
+        status = getattr(_lib.load(), name)(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class), _ptr(cp.class_start), C,
+                                            _ptr(cp.means), _ptr(F), K, code, float(noise), *map(_ptr, shrink), _ptr(zc),
+                                            _ptr(means_f), _ptr(cov_f), _ptr(second_f), _ptr(ws), nbytes, stream)
+    _lib.check(status, name)
     return zc, means_f, cov_f, second_f
 
 
@@ -805,7 +754,6 @@ def class_feature_moments_backward(cp, zc, G, g_means, F=None):
     """sqfa_class_feature_moments_backward on the current stream: the (n_groups, K, D) partial sums of dL/dF for
     G = dL/dcov_f (C,K,K) and g_means = dL/dmeans_f (C,K) or None.  A `cp` with shrinkage coefficients needs the contiguous
     filters F (K,D) of the forward call as well (sqfa_class_feature_moments_shrunk_backward)."""
-    lib = _lib.load()
     X = cp.points
     N, D = X.shape
     K, C = zc.shape[1], cp.n_classes
@@ -813,25 +761,17 @@ def class_feature_moments_backward(cp, zc, G, g_means, F=None):
     G = G.detach().contiguous()
     g_means = g_means.detach().contiguous() if g_means is not None else None
     groups = point_backward_groups(N, D)
-    keep, shift = getattr(cp, "shrink_keep", None), getattr(cp, "shrink_shift", None)
-    if keep is not None and F is None:
+    shrink, name, query = _feature_moments_entry(cp, "_backward")
+    if shrink and F is None:
         raise ValueError("the backward of shrunk feature moments needs the filters")
-    query = lib.sqfa_class_feature_moments_workspace_bytes if keep is None else lib.sqfa_class_feature_moments_shrunk_workspace_bytes
     with _on_stream(X.device) as stream:
         ws, nbytes = _workspace(query, N, C, D, K, code)
         partial = torch.empty((groups, K, D), dtype=X.dtype, device=X.device)
-        if keep is None:
-            _lib.check(lib.sqfa_class_feature_moments_backward(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
-                                                               _ptr(cp.class_start), C, _ptr(cp.means), _ptr(zc), _ptr(G), K,
-                                                               _ptr(g_means), K, code, groups, _ptr(partial), _ptr(ws), nbytes,
-                                                               stream), "sqfa_class_feature_moments_backward")
-        else:
-            _lib.check(lib.sqfa_class_feature_moments_shrunk_backward(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class),
-                                                                      _ptr(cp.class_start), C, _ptr(cp.means), _ptr(F),
-                                                                      _ptr(zc), _ptr(G), K, _ptr(g_means), _ptr(keep),
-                                                                      _ptr(shift), K, code, groups, _ptr(partial), _ptr(ws),
-                                                                      nbytes, stream),
-                       "sqfa_class_feature_moments_shrunk_backward")
+        status = getattr(_lib.load(), name)(_ptr(X), N, D, _ptr(cp.order), _ptr(cp.row_class), _ptr(cp.class_start), C,
+                                            _ptr(cp.means), *((_ptr(F),) if shrink else ()), _ptr(zc), _ptr(G), K,
+                                            _ptr(g_means), *map(_ptr, shrink), K, code, groups, _ptr(partial), _ptr(ws),
+                                            nbytes, stream)
+    _lib.check(status, name)
     return partial
 
 

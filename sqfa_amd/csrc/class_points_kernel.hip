@@ -39,6 +39,7 @@
 
 #include <climits>
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/sqfa_hip.h"
 #include "proj_traits.hpp"
@@ -620,6 +621,69 @@ static void run_feature_backward(const T* points, long long N, int D, const long
                                                                      wbuf, K, V, per, partial_out);
 }
 
+// The plain and the shrunk entries over one implementation: `shrunk` selects the layout (cp_layout_shrunk) and asks for
+// keep / shift (and F, backward); the plain entries pass nullptr for them.
+static int feature_moments_impl(bool shrunk, const void* points, long long N, int D, const long long* row_index,
+                                const long long* row_class, const long long* class_start, int C, const void* means,
+                                const void* F, int K, int dtype, double noise, const void* keep, const void* shift,
+                                void* zc_out, void* means_f_out, void* cov_f_out, void* second_f_out, void* workspace,
+                                size_t workspace_bytes, void* stream_) {
+  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc_out == nullptr)) ||
+      class_start == nullptr || means == nullptr || F == nullptr || (shrunk && (keep == nullptr || shift == nullptr)) ||
+      means_f_out == nullptr || cov_f_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CpShrunkLayout w{};
+  CpLayout plain;
+  if (!(shrunk ? cp_layout_shrunk(N, C, D, K, dtype, &w) : cp_layout(N, C, D, K, dtype, &plain))) return SQFA_ERR_UNSUPPORTED_M;
+  if (!shrunk) w.split = plain.split, w.total = plain.total;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  auto run = [&](auto* element) {   // the dtype fork: called with a null float* / double*
+    using T = std::remove_pointer_t<decltype(element)>;
+    run_feature_moments(static_cast<const T*>(points), N, D, row_index, row_class, class_start, C, static_cast<const T*>(means),
+                        static_cast<const T*>(F), K, noise, static_cast<T*>(zc_out), static_cast<T*>(means_f_out),
+                        static_cast<T*>(cov_f_out), static_cast<T*>(second_f_out), ws, w.split, stream,
+                        static_cast<const T*>(keep), static_cast<const T*>(shift),
+                        shrunk ? reinterpret_cast<T*>(ws + w.fft_off) : nullptr);
+  };
+  if (dtype == SQFA_F32) run(static_cast<float*>(nullptr));
+  else run(static_cast<double*>(nullptr));
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+static int feature_backward_impl(bool shrunk, const void* points, long long N, int D, const long long* row_index,
+                                 const long long* row_class, const long long* class_start, int C, const void* means,
+                                 const void* F, const void* zc, const void* G, int ldg, const void* g_means, const void* keep,
+                                 const void* shift, int K, int dtype, int n_groups, void* partial_out, void* workspace,
+                                 size_t workspace_bytes, void* stream_) {
+  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc == nullptr)) ||
+      class_start == nullptr || means == nullptr || G == nullptr ||
+      (shrunk && (F == nullptr || keep == nullptr || shift == nullptr)) || ldg < K || n_groups < 1 || n_groups > 65535 ||
+      partial_out == nullptr)
+    return SQFA_ERR_BAD_ARGUMENT;
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
+  CpShrunkLayout w{};
+  CpLayout plain;
+  if (!(shrunk ? cp_layout_shrunk(N, C, D, K, dtype, &w) : cp_layout(N, C, D, K, dtype, &plain))) return SQFA_ERR_UNSUPPORTED_M;
+  if (!shrunk) w.total = plain.total;
+  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  auto run = [&](auto* element) {   // the dtype fork: called with a null float* / double*
+    using T = std::remove_pointer_t<decltype(element)>;
+    run_feature_backward(static_cast<const T*>(points), N, D, row_index, row_class, class_start, C,
+                         static_cast<const T*>(means), static_cast<const T*>(zc), static_cast<const T*>(G), ldg,
+                         static_cast<const T*>(g_means), K, n_groups, static_cast<T*>(partial_out), ws, stream,
+                         static_cast<const T*>(keep), static_cast<const T*>(shift), static_cast<const T*>(F),
+                         shrunk ? reinterpret_cast<T*>(ws + w.h_off) : nullptr);
+  };
+  if (dtype == SQFA_F32) run(static_cast<float*>(nullptr));
+  else run(static_cast<double*>(nullptr));
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
 }  // namespace sqfa
 
 extern "C" size_t sqfa_class_feature_moments_workspace_bytes(long long N, int C, int D, int K, int dtype) {
@@ -633,27 +697,9 @@ extern "C" int sqfa_class_feature_moments(const void* points, long long N, int D
                                           const void* means, const void* F, int K, int dtype, double noise, void* zc_out,
                                           void* means_f_out, void* cov_f_out, void* second_f_out, void* workspace,
                                           size_t workspace_bytes, void* stream_) {
-  using namespace sqfa;
-  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc_out == nullptr)) ||
-      class_start == nullptr || means == nullptr || F == nullptr || means_f_out == nullptr || cov_f_out == nullptr)
-    return SQFA_ERR_BAD_ARGUMENT;
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
-  CpLayout w;
-  if (!cp_layout(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  if (dtype == SQFA_F32)
-    run_feature_moments(static_cast<const float*>(points), N, D, row_index, row_class, class_start, C,
-                        static_cast<const float*>(means), static_cast<const float*>(F), K, noise, static_cast<float*>(zc_out),
-                        static_cast<float*>(means_f_out), static_cast<float*>(cov_f_out), static_cast<float*>(second_f_out),
-                        ws, w.split, stream);
-  else
-    run_feature_moments(static_cast<const double*>(points), N, D, row_index, row_class, class_start, C,
-                        static_cast<const double*>(means), static_cast<const double*>(F), K, noise,
-                        static_cast<double*>(zc_out), static_cast<double*>(means_f_out), static_cast<double*>(cov_f_out),
-                        static_cast<double*>(second_f_out), ws, w.split, stream);
-  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+  return sqfa::feature_moments_impl(false, points, N, D, row_index, row_class, class_start, C, means, F, K, dtype, noise,
+                                    nullptr, nullptr, zc_out, means_f_out, cov_f_out, second_f_out, workspace,
+                                    workspace_bytes, stream_);
 }
 
 extern "C" int sqfa_class_feature_moments_backward(const void* points, long long N, int D, const long long* row_index,
@@ -661,26 +707,9 @@ extern "C" int sqfa_class_feature_moments_backward(const void* points, long long
                                                    const void* means, const void* zc, const void* G, int ldg,
                                                    const void* g_means, int K, int dtype, int n_groups, void* partial_out,
                                                    void* workspace, size_t workspace_bytes, void* stream_) {
-  using namespace sqfa;
-  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc == nullptr)) ||
-      class_start == nullptr || means == nullptr || G == nullptr || ldg < K || n_groups < 1 || n_groups > 65535 ||
-      partial_out == nullptr)
-    return SQFA_ERR_BAD_ARGUMENT;
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
-  CpLayout w;
-  if (!cp_layout(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  if (dtype == SQFA_F32)
-    run_feature_backward(static_cast<const float*>(points), N, D, row_index, row_class, class_start, C,
-                         static_cast<const float*>(means), static_cast<const float*>(zc), static_cast<const float*>(G), ldg,
-                         static_cast<const float*>(g_means), K, n_groups, static_cast<float*>(partial_out), ws, stream);
-  else
-    run_feature_backward(static_cast<const double*>(points), N, D, row_index, row_class, class_start, C,
-                         static_cast<const double*>(means), static_cast<const double*>(zc), static_cast<const double*>(G),
-                         ldg, static_cast<const double*>(g_means), K, n_groups, static_cast<double*>(partial_out), ws, stream);
-  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+  return sqfa::feature_backward_impl(false, points, N, D, row_index, row_class, class_start, C, means, nullptr, zc, G, ldg,
+                                     g_means, nullptr, nullptr, K, dtype, n_groups, partial_out, workspace, workspace_bytes,
+                                     stream_);
 }
 
 // ---- the shrunk entries: cov_c -> keep_c cov_c + shift_c I in D-space (OAS; keep, shift from sqfa_class_shrinkage) ---------
@@ -691,57 +720,14 @@ extern "C" size_t sqfa_class_feature_moments_shrunk_workspace_bytes(long long N,
   return w.total < 16 ? 16 : w.total;
 }
 
-namespace sqfa {
-
-template <typename T>
-static void shrunk_forward(const void* points, long long N, int D, const long long* row_index, const long long* row_class,
-                           const long long* class_start, int C, const void* means, const void* F, int K, double noise,
-                           const void* keep, const void* shift, void* zc, void* means_f, void* cov_f, void* second_f,
-                           char* ws, const CpShrunkLayout& w, hipStream_t stream) {
-  run_feature_moments(static_cast<const T*>(points), N, D, row_index, row_class, class_start, C, static_cast<const T*>(means),
-                      static_cast<const T*>(F), K, noise, static_cast<T*>(zc), static_cast<T*>(means_f),
-                      static_cast<T*>(cov_f), static_cast<T*>(second_f), ws, w.split, stream, static_cast<const T*>(keep),
-                      static_cast<const T*>(shift), reinterpret_cast<T*>(ws + w.fft_off));
-}
-
-template <typename T>
-static void shrunk_backward(const void* points, long long N, int D, const long long* row_index, const long long* row_class,
-                            const long long* class_start, int C, const void* means, const void* F, const void* zc,
-                            const void* G, int ldg, const void* g_means, const void* keep, const void* shift, int K,
-                            int n_groups, void* partial_out, char* ws, const CpShrunkLayout& w, hipStream_t stream) {
-  run_feature_backward(static_cast<const T*>(points), N, D, row_index, row_class, class_start, C,
-                       static_cast<const T*>(means), static_cast<const T*>(zc), static_cast<const T*>(G), ldg,
-                       static_cast<const T*>(g_means), K, n_groups, static_cast<T*>(partial_out), ws, stream,
-                       static_cast<const T*>(keep), static_cast<const T*>(shift), static_cast<const T*>(F),
-                       reinterpret_cast<T*>(ws + w.h_off));
-}
-
-}  // namespace sqfa
-
 extern "C" int sqfa_class_feature_moments_shrunk(const void* points, long long N, int D, const long long* row_index,
                                                  const long long* row_class, const long long* class_start, int C,
                                                  const void* means, const void* F, int K, int dtype, double noise,
                                                  const void* keep, const void* shift, void* zc_out, void* means_f_out,
                                                  void* cov_f_out, void* second_f_out, void* workspace,
                                                  size_t workspace_bytes, void* stream_) {
-  using namespace sqfa;
-  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc_out == nullptr)) ||
-      class_start == nullptr || means == nullptr || F == nullptr || keep == nullptr || shift == nullptr ||
-      means_f_out == nullptr || cov_f_out == nullptr)
-    return SQFA_ERR_BAD_ARGUMENT;
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
-  CpShrunkLayout w;
-  if (!cp_layout_shrunk(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  if (dtype == SQFA_F32)
-    shrunk_forward<float>(points, N, D, row_index, row_class, class_start, C, means, F, K, noise, keep, shift, zc_out,
-                          means_f_out, cov_f_out, second_f_out, ws, w, stream);
-  else
-    shrunk_forward<double>(points, N, D, row_index, row_class, class_start, C, means, F, K, noise, keep, shift, zc_out,
-                           means_f_out, cov_f_out, second_f_out, ws, w, stream);
-  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+  return sqfa::feature_moments_impl(true, points, N, D, row_index, row_class, class_start, C, means, F, K, dtype, noise, keep,
+                                    shift, zc_out, means_f_out, cov_f_out, second_f_out, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int sqfa_class_feature_moments_shrunk_backward(const void* points, long long N, int D, const long long* row_index,
@@ -750,22 +736,6 @@ extern "C" int sqfa_class_feature_moments_shrunk_backward(const void* points, lo
                                                           int ldg, const void* g_means, const void* keep, const void* shift,
                                                           int K, int dtype, int n_groups, void* partial_out, void* workspace,
                                                           size_t workspace_bytes, void* stream_) {
-  using namespace sqfa;
-  if (N < 0 || C < 1 || D < 1 || K < 1 || (N > 0 && (points == nullptr || row_class == nullptr || zc == nullptr)) ||
-      class_start == nullptr || means == nullptr || F == nullptr || G == nullptr || keep == nullptr || shift == nullptr ||
-      ldg < K || n_groups < 1 || n_groups > 65535 || partial_out == nullptr)
-    return SQFA_ERR_BAD_ARGUMENT;
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
-  CpShrunkLayout w;
-  if (!cp_layout_shrunk(N, C, D, K, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  if (dtype == SQFA_F32)
-    shrunk_backward<float>(points, N, D, row_index, row_class, class_start, C, means, F, zc, G, ldg, g_means, keep, shift, K,
-                           n_groups, partial_out, ws, w, stream);
-  else
-    shrunk_backward<double>(points, N, D, row_index, row_class, class_start, C, means, F, zc, G, ldg, g_means, keep, shift, K,
-                            n_groups, partial_out, ws, w, stream);
-  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+  return sqfa::feature_backward_impl(true, points, N, D, row_index, row_class, class_start, C, means, F, zc, G, ldg, g_means,
+                                     keep, shift, K, dtype, n_groups, partial_out, workspace, workspace_bytes, stream_);
 }

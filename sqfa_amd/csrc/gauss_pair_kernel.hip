@@ -33,6 +33,7 @@
 #include <stdio.h>
 
 #include "../../include/sqfa_hip.h"
+#include "class_pair_loss.hpp"
 #include "pair_kernel.hpp"   // transposing tree reductions (tree_reduce_blocks), wave_sum
 
 namespace sqfa {
@@ -56,6 +57,10 @@ template <int G, typename T> __device__ __forceinline__ T group_total(T v) {
   return v;
 }
 
+// The fused mode's fields are those of PairLossParams (class_pair_loss.hpp), declared here in the order the kernels below
+// were tuned with: the order of the kernel arguments decides the scalar loads, and through the scalar spills of the register
+// kernels their vector registers and occupancy (the common struct as a base costs gauss_pair_kernel<float, 64, GAUSS_FUSED>
+// 24 VGPRs and a wave per SIMD).
 struct GaussParams {
   const void *muA, *covA, *muB, *covB;
   const void *gQ, *gLD;      // (nA,nB) or nullptr
@@ -63,7 +68,7 @@ struct GaussParams {
   void *gmuA, *gcovA;        // (nA,m), (nA,m,m) or nullptr
   int nA, nB, m, ng;         // ng: lane groups per workgroup
   // fused mode only (B is A)
-  int kind;                  // SQFA_GAUSS_*
+  int kind, n;               // SQFA_GAUSS_*; n: nA = nB again (it sits in the padding behind `kind`)
   double eps, weight;
   float epsf, weightf;       // the same two, rounded once on the host (scalar kernel arguments, no conversion per wave)
   void *ldc;                 // (n) logdet Sigma_c: written by the pre-pass, read by the fused pass
@@ -77,13 +82,6 @@ struct GaussParams {
 // GAUSS_FUSED_W: the fused mode with w_ij = W[i n + j] in place of the scalar weight -- an instantiation of its own, so
 // that the uniform fused kernels stay the code they were
 enum { GAUSS_PLAIN = 0, GAUSS_FUSED = 1, GAUSS_PRE = 2, GAUSS_FUSED_W = 3 };
-
-template <typename T> __device__ __forceinline__ T fused_weight(const GaussParams& p);
-template <> __device__ __forceinline__ float fused_weight<float>(const GaussParams& p) { return p.weightf; }
-template <> __device__ __forceinline__ double fused_weight<double>(const GaussParams& p) { return p.weight; }
-template <typename T> __device__ __forceinline__ T fused_eps(const GaussParams& p);
-template <> __device__ __forceinline__ float fused_eps<float>(const GaussParams& p) { return p.epsf; }
-template <> __device__ __forceinline__ double fused_eps<double>(const GaussParams& p) { return p.eps; }
 
 __device__ __forceinline__ float g_exp(float x) { return expf(x); }
 __device__ __forceinline__ double g_exp(double x) { return exp(x); }
@@ -141,7 +139,7 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
   // Sbar^-1 is needed where logdet Sbar has a gradient
   const bool with_inv = FUSED ? p.kind <= SQFA_GAUSS_HELLINGER : gLD != nullptr;
   const T* ldc = static_cast<const T*>(p.ldc);
-  const T fw0 = fused_weight<T>(p), feps = fused_eps<T>(p);
+  const T fw0 = pair_weight<T>(p), feps = pair_eps<T>(p);
   T loss_acc = T(0), csum = T(0);   // fused: lane 0 of the group keeps the group's partial sums
   int n_nan = 0, n_inf = 0;
 
@@ -403,7 +401,7 @@ void gauss_pair_reg_kernel(const GaussParams p) {
   // Sbar^-1 is needed where logdet Sbar has a gradient
   const bool with_inv = FUSED ? p.kind <= SQFA_GAUSS_HELLINGER : gLD != nullptr;
   const T* ldc = static_cast<const T*>(p.ldc);
-  const T fw0 = fused_weight<T>(p), feps = fused_eps<T>(p);
+  const T fw0 = pair_weight<T>(p), feps = pair_eps<T>(p);
   T loss_acc = T(0), csum = T(0);   // fused: per-wave partial sums and counts (wave-uniform: scalar registers)
   int n_nan = 0, n_inf = 0;
 
@@ -645,55 +643,6 @@ static hipError_t dispatch_gauss(const GaussParams& p, int dtype, hipStream_t st
   if (m <= 32) return launch_gauss<double, 32, MODE>(p, stream);
   return launch_gauss<double, 64, MODE>(p, stream);
 }
-
-// loss = sum of the per-class partial losses, {#NaN, #inf} = sums of the per-class counts: one workgroup, fixed order
-template <typename T>
-__global__ __launch_bounds__(256) void gauss_finalize_kernel(const double* loss_part, const int* cnt_part, int n,
-                                                              T* loss_out, int* nonfinite_out) {
-  __shared__ double s_loss[256];
-  __shared__ int s_cnt[256][2];
-  const int tid = threadIdx.x;
-  double l = 0.0;
-  int nn = 0, ni = 0;
-  for (int c = tid; c < n; c += 256) {
-    l += loss_part[c];
-    nn += cnt_part[2 * c];
-    ni += cnt_part[2 * c + 1];
-  }
-  s_loss[tid] = l;
-  s_cnt[tid][0] = nn;
-  s_cnt[tid][1] = ni;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (tid < d) {
-      s_loss[tid] += s_loss[tid + d];
-      s_cnt[tid][0] += s_cnt[tid + d][0];
-      s_cnt[tid][1] += s_cnt[tid + d][1];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    if (loss_out != nullptr) *loss_out = T(s_loss[0]);
-    if (nonfinite_out != nullptr) {
-      nonfinite_out[0] = s_cnt[0][0];
-      nonfinite_out[1] = s_cnt[0][1];
-    }
-  }
-}
-
-// (also the last stage of sqfa_log_euclidean_pairwise_loss, log_euclidean_kernel.hip)
-hipError_t launch_pair_loss_finalize(const double* loss_part, const int* cnt_part, int n, int dtype, void* loss_out,
-                                     int* nonfinite_out, hipStream_t stream) {
-  if (dtype == SQFA_F32)
-    hipLaunchKernelGGL((gauss_finalize_kernel<float>), dim3(1), dim3(256), 0, stream, loss_part, cnt_part, n,
-                       static_cast<float*>(loss_out), nonfinite_out);
-  else
-    hipLaunchKernelGGL((gauss_finalize_kernel<double>), dim3(1), dim3(256), 0, stream, loss_part, cnt_part, n,
-                       static_cast<double*>(loss_out), nonfinite_out);
-  return hipGetLastError();
-}
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 }  // namespace sqfa
 
 using namespace sqfa;
@@ -769,22 +718,16 @@ extern "C" int sqfa_gauss_pairwise_loss_weighted(const void* mu, const void* cov
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const size_t block = align256((size_t)n * 8);
   GaussParams p{mu, cov, mu, cov, nullptr, nullptr, nullptr, nullptr, gmu_out, gcov_out, n, n, m, 1};
+  fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + block),
+                        reinterpret_cast<int*>(ws + 2 * block));
   p.kind = kind;
-  p.eps = eps;
-  p.weight = uniform_weight;
-  p.epsf = (float)eps;
-  p.weightf = (float)uniform_weight;
   p.ldc = ws;
-  p.loss_part = reinterpret_cast<double*>(ws + block);
-  p.cnt_part = reinterpret_cast<int*>(ws + 2 * block);
   p.sinv = ws + 3 * block;
-  p.dist = dist_out;
   if (kind <= SQFA_GAUSS_HELLINGER) {   // per-class log-determinants first: every pair needs both of its classes'
     GaussParams pre = p;
     pre.gmuA = pre.gcovA = nullptr;
     if (dispatch_gauss<GAUSS_PRE>(pre, dtype, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   }
-  p.W = pair_weights;
   const hipError_t e = pair_weights != nullptr ? dispatch_gauss<GAUSS_FUSED_W>(p, dtype, stream)
                                                : dispatch_gauss<GAUSS_FUSED>(p, dtype, stream);
   if (e != hipSuccess) return SQFA_ERR_LAUNCH;

@@ -27,42 +27,28 @@
 //      float64 with m > 32 (BIG): one record is 48-64 KiB, so nothing is staged -- the lanes read Sigma_j, P_j and their own
 //      class's rows from global memory (coalesced, L2 resident) and only the accumulators live in registers.
 //   3. jeffreys_finish_kernel: gcov_i = GSigma_i - P_i sym(GP_i) P_i per class (the chain rule through the inverse), lower
-//      triangle computed in double and mirrored; then launch_pair_loss_finalize (gauss_pair_kernel.hip) for the loss and counters.
+//      triangle computed in double and mirrored; then launch_pair_loss_finalize (class_pair_loss.hip) for the loss and counters.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sqfa_hip.h"
+#include "class_pair_loss.hpp"
 #include "pair_kernel.hpp"   // group_sum
 
 namespace sqfa {
 
-// gauss_pair_kernel.hip: loss = sum of the per-class partial losses, {#NaN, #inf} = sums of the per-class counts
-hipError_t launch_pair_loss_finalize(const double* loss_part, const int* cnt_part, int n, int dtype, void* loss_out,
-                                     int* nonfinite_out, hipStream_t stream);
 // sqfa_api.hip: the text sqfa_hip_last_error() returns
 void set_last_error(const char* text);
 
-struct JeffParams {
+struct JeffParams : PairLossParams {
   const void* mu;     // (n,m) or nullptr
   const void* cov;    // (n,m,m)
   const void* P;      // (n,m,m) precisions (stage 1)
   void* GS;           // (n,m,m) d loss / d Sigma at fixed P, or nullptr (forward only)
   void* GP;           // (n,m,m) d loss / d P
   void* gmu;          // (n,m) or nullptr
-  void* dist;         // (n,n) or nullptr
-  double* loss_part;  // (n) per-class partial losses sum_{j<i} w_ij D_ij
-  int* cnt_part;      // (n,2) per-class {#NaN, #inf} among j < i
-  int n, m, sqrt_mode;
-  double eps, weight;
-  float epsf, weightf;  // the same two, rounded once on the host
-  const void* W;        // (n,n) symmetric per-pair weights (WEIGHTED kernels only; `weight` is then unused)
+  int sqrt_mode;
 };
 
-template <typename T> __device__ __forceinline__ T jf_weight(const JeffParams& p);
-template <> __device__ __forceinline__ float jf_weight<float>(const JeffParams& p) { return p.weightf; }
-template <> __device__ __forceinline__ double jf_weight<double>(const JeffParams& p) { return p.weight; }
-template <typename T> __device__ __forceinline__ T jf_eps(const JeffParams& p);
-template <> __device__ __forceinline__ float jf_eps<float>(const JeffParams& p) { return p.epsf; }
-template <> __device__ __forceinline__ double jf_eps<double>(const JeffParams& p) { return p.eps; }
 __device__ __forceinline__ float jf_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double jf_sqrt(double x) { return sqrt(x); }
 template <typename T> __device__ __forceinline__ T jf_nan();
@@ -214,7 +200,7 @@ __global__ __launch_bounds__(256) void jeffreys_pair_kernel(const JeffParams p) 
   for (int c = 0; c < MMAX; ++c) accS[c] = accP[c] = T(0);
   T gmu_acc = T(0);
 
-  const T w = jf_weight<T>(p), eps = jf_eps<T>(p);
+  const T w = pair_weight<T>(p), eps = pair_eps<T>(p);
   const bool sqrt_mode = p.sqrt_mode != 0, want_grad = p.GS != nullptr;
   T* dist = static_cast<T*>(p.dist);
   double loss_acc = 0.0;
@@ -477,8 +463,6 @@ static hipError_t dispatch_jeffreys(const JeffParams& p, hipStream_t stream) {
   return launch_jeffreys<T, 64, 64, F64>(p, stream);
 }
 
-static size_t jf_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // workspace: [P (n,m,m) dtype] [GSigma (n,m,m) dtype] [GP (n,m,m) dtype] [Y (n,m,m) double] [partial losses (n) double]
 //            [counts (n,2) int]
 struct JeffLayout {
@@ -489,12 +473,12 @@ static bool jeffreys_layout(int n, int m, int dtype, JeffLayout* out) {
   const size_t esz = dtype == SQFA_F32 ? 4 : 8, mat = (size_t)n * m * m;
   JeffLayout w;
   size_t o = 0;
-  w.off_p = o;    o = jf_align(o + mat * esz);
-  w.off_gs = o;   o = jf_align(o + mat * esz);
-  w.off_gp = o;   o = jf_align(o + mat * esz);
-  w.off_y = o;    o = jf_align(o + mat * sizeof(double));
-  w.off_loss = o; o = jf_align(o + (size_t)n * sizeof(double));
-  w.off_cnt = o;  o = jf_align(o + (size_t)n * 2 * sizeof(int));
+  w.off_p = o;    o = align256(o + mat * esz);
+  w.off_gs = o;   o = align256(o + mat * esz);
+  w.off_gp = o;   o = align256(o + mat * esz);
+  w.off_y = o;    o = align256(o + mat * sizeof(double));
+  w.off_loss = o; o = align256(o + (size_t)n * sizeof(double));
+  w.off_cnt = o;  o = align256(o + (size_t)n * 2 * sizeof(int));
   w.total = o;
   *out = w;
   return true;
@@ -559,17 +543,9 @@ extern "C" int sqfa_jeffreys_pairwise_loss(const void* mu, const void* cov, int 
   p.GS = want_grad ? ws + w.off_gs : nullptr;
   p.GP = want_grad ? ws + w.off_gp : nullptr;
   p.gmu = gmu_out;
-  p.dist = dist_out;
-  p.loss_part = reinterpret_cast<double*>(ws + w.off_loss);
-  p.cnt_part = reinterpret_cast<int*>(ws + w.off_cnt);
-  p.n = n;
-  p.m = m;
   p.sqrt_mode = sqrt_mode;
-  p.eps = eps;
-  p.weight = uniform_weight;
-  p.epsf = (float)eps;
-  p.weightf = (float)uniform_weight;
-  p.W = pair_weights;
+  fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + w.off_loss),
+                        reinterpret_cast<int*>(ws + w.off_cnt));
   const hipError_t e = dtype == SQFA_F32 ? dispatch_jeffreys<float>(p, stream) : dispatch_jeffreys<double>(p, stream);
   if (e != hipSuccess) return SQFA_ERR_LAUNCH;
   // 3. the chain rule through the inverse

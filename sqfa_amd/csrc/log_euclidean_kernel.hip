@@ -24,32 +24,17 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sqfa_hip.h"
+#include "class_pair_loss.hpp"
 #include "pair_kernel.hpp"   // group_sum
 
 namespace sqfa {
 
-// gauss_pair_kernel.hip: loss = sum of the per-class partial losses, {#NaN, #inf} = sums of the per-class counts
-hipError_t launch_pair_loss_finalize(const double* loss_part, const int* cnt_part, int n, int dtype, void* loss_out,
-                                     int* nonfinite_out, hipStream_t stream);
-
-struct LogEucParams {
+struct LogEucParams : PairLossParams {
   const void* L;      // (n,m,m) class logarithms
   void* G;            // (n,m,m) d loss / d L, full symmetric matrices, or nullptr (forward only)
-  void* dist;         // (n,n) or nullptr
-  double* loss_part;  // (n) per-class partial losses w sum_{j<i} D_ij
-  int* cnt_part;      // (n,2) per-class {#NaN, #inf} among j < i
-  int n, m, sqrt_mode;
-  double eps, weight;
-  float epsf, weightf;  // the same two, rounded once on the host
-  const void* W;        // (n,n) symmetric per-pair weights (WEIGHTED kernels only; `weight` is then unused)
+  int sqrt_mode;
 };
 
-template <typename T> __device__ __forceinline__ T le_weight(const LogEucParams& p);
-template <> __device__ __forceinline__ float le_weight<float>(const LogEucParams& p) { return p.weightf; }
-template <> __device__ __forceinline__ double le_weight<double>(const LogEucParams& p) { return p.weight; }
-template <typename T> __device__ __forceinline__ T le_eps(const LogEucParams& p);
-template <> __device__ __forceinline__ float le_eps<float>(const LogEucParams& p) { return p.epsf; }
-template <> __device__ __forceinline__ double le_eps<double>(const LogEucParams& p) { return p.eps; }
 __device__ __forceinline__ float le_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double le_sqrt(double x) { return sqrt(x); }
 
@@ -123,7 +108,7 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
     li[e] = (ivalid && off >= 0) ? L[(size_t)i * mm + off] : T(0);
     acc[e] = T(0);
   }
-  const T w = le_weight<T>(p), eps = le_eps<T>(p);
+  const T w = pair_weight<T>(p), eps = pair_eps<T>(p);
   const bool sqrt_mode = p.sqrt_mode != 0;
   T* dist = static_cast<T*>(p.dist);
   double loss_acc = 0.0;
@@ -274,8 +259,6 @@ static hipError_t dispatch_log_euclidean(const LogEucParams& p, hipStream_t stre
   return launch_log_euclidean<T, 64, 64>(p, stream);
 }
 
-static size_t le_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // workspace: [sqfa_spd_function's] [L (n,m,m) dtype] [U (n,m,m) double] [lambda (n,m) double] [G (n,m,m) dtype]
 //            [partial losses (n) double] [counts (n,2) int]
 struct LogEucLayout {
@@ -287,13 +270,13 @@ static bool log_euclidean_layout(int n, int m, int dtype, LogEucLayout* out) {
   w.spd_bytes = sqfa_spd_function_workspace_bytes(n, m, dtype);
   if (w.spd_bytes == 0) return false;
   const size_t esz = dtype == SQFA_F32 ? 4 : 8, mat = (size_t)n * m * m;
-  size_t o = le_align(w.spd_bytes);
-  w.off_l = o;    o = le_align(o + mat * esz);
-  w.off_u = o;    o = le_align(o + mat * sizeof(double));
-  w.off_lam = o;  o = le_align(o + (size_t)n * m * sizeof(double));
-  w.off_g = o;    o = le_align(o + mat * esz);
-  w.off_loss = o; o = le_align(o + (size_t)n * sizeof(double));
-  w.off_cnt = o;  o = le_align(o + (size_t)n * 2 * sizeof(int));
+  size_t o = align256(w.spd_bytes);
+  w.off_l = o;    o = align256(o + mat * esz);
+  w.off_u = o;    o = align256(o + mat * sizeof(double));
+  w.off_lam = o;  o = align256(o + (size_t)n * m * sizeof(double));
+  w.off_g = o;    o = align256(o + mat * esz);
+  w.off_loss = o; o = align256(o + (size_t)n * sizeof(double));
+  w.off_cnt = o;  o = align256(o + (size_t)n * 2 * sizeof(int));
   w.total = o;
   *out = w;
   return true;
@@ -329,17 +312,9 @@ extern "C" int sqfa_log_euclidean_pairwise_loss_weighted(const void* S, int n, i
   LogEucParams p{};
   p.L = ws + w.off_l;
   p.G = gradS_out != nullptr ? ws + w.off_g : nullptr;
-  p.dist = dist_out;
-  p.loss_part = reinterpret_cast<double*>(ws + w.off_loss);
-  p.cnt_part = reinterpret_cast<int*>(ws + w.off_cnt);
-  p.n = n;
-  p.m = m;
   p.sqrt_mode = sqrt_mode;
-  p.eps = eps;
-  p.weight = uniform_weight;
-  p.epsf = (float)eps;
-  p.weightf = (float)uniform_weight;
-  p.W = pair_weights;
+  fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + w.off_loss),
+                        reinterpret_cast<int*>(ws + w.off_cnt));
   const hipError_t e = dtype == SQFA_F32 ? dispatch_log_euclidean<float>(p, stream) : dispatch_log_euclidean<double>(p, stream);
   if (e != hipSuccess) return SQFA_ERR_LAUNCH;
   // 3. d loss / d S = Daleckii-Krein backward of the logarithm on G

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sqfa_hip.h"
+#include "class_pair_loss.hpp"   // align256
 
 namespace sqfa {
 
@@ -285,8 +286,6 @@ __global__ __launch_bounds__(256) void orth_gv_kernel(const T* __restrict__ X, c
   }
 }
 
-static size_t orth_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // workspace: [G partials (nblk,K,K)] [gW partials (nblk,K,K)] [W] [Z] [S] (K,K) double; [P | gP (D,K) dtype]
 struct OrthLayout {
   int nblk;
@@ -298,12 +297,12 @@ static bool orth_layout(int K, int D, int dtype, OrthLayout* out) {
   w.nblk = (D + ORTH_ROWS - 1) / ORTH_ROWS;
   const size_t kk = (size_t)K * K * sizeof(double), esz = dtype == SQFA_F32 ? 4 : 8;
   size_t o = 0;
-  w.off_g = o;  o = orth_align(o + (size_t)w.nblk * kk);
-  w.off_gw = o; o = orth_align(o + (size_t)w.nblk * kk);
-  w.off_w = o;  o = orth_align(o + kk);
-  w.off_z = o;  o = orth_align(o + kk);
-  w.off_s = o;  o = orth_align(o + kk);
-  w.off_p = o;  o = orth_align(o + (size_t)D * K * esz);
+  w.off_g = o;  o = align256(o + (size_t)w.nblk * kk);
+  w.off_gw = o; o = align256(o + (size_t)w.nblk * kk);
+  w.off_w = o;  o = align256(o + kk);
+  w.off_z = o;  o = align256(o + kk);
+  w.off_s = o;  o = align256(o + kk);
+  w.off_p = o;  o = align256(o + (size_t)D * K * esz);
   w.total = o;
   *out = w;
   return true;

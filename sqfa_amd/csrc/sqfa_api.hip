@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/sqfa_hip.h"
+#include "class_pair_loss.hpp"   // align256
 #include "configs.hpp"
 #include "pair_kernel.hpp"
 #include "pair_kernel_2d.hpp"
@@ -148,8 +149,6 @@ std::mutex& sqfa_project_events_mutex() {
 }
 namespace sqfa {
 
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct WorkspaceLayout {
   size_t off_lt, off_linv, off_slab, off_loss, off_flag, off_rows, off_mean, total;
 };
@@ -241,14 +240,14 @@ static WorkspaceLayout layout(const PairPlan& pl, bool any_width) {
     if (tj % 2) break;
   }
   size_t o = 0;
-  w.off_lt = o;   o = align_up(o + (size_t)pl.nA * mat);
-  w.off_linv = o; o = align_up(o + (size_t)pl.nBeff * mat);  // (packed for MR >= 32: uses about half)
-  w.off_slab = o; o = align_up(o + slab);
-  w.off_loss = o; o = align_up(o + tiles * pl.esz);
-  w.off_flag = o; o = align_up(o + tiles * 2 * sizeof(int));
-  w.off_rows = o; o = align_up(o + ((size_t)pl.nbi + 1) * sizeof(int));
+  w.off_lt = o;   o = align256(o + (size_t)pl.nA * mat);
+  w.off_linv = o; o = align256(o + (size_t)pl.nBeff * mat);  // (packed for MR >= 32: uses about half)
+  w.off_slab = o; o = align256(o + slab);
+  w.off_loss = o; o = align256(o + tiles * pl.esz);
+  w.off_flag = o; o = align256(o + tiles * 2 * sizeof(int));
+  w.off_rows = o; o = align256(o + ((size_t)pl.nbi + 1) * sizeof(int));
   // mean-metric factor pass: kMeanParts partial sums of the A classes (MR x MR doubles each), then Lbar^-1 (MR x MR doubles)
-  w.off_mean = o; o = align_up(o + (size_t)(kMeanParts + 1) * g.MR * g.MR * sizeof(double));
+  w.off_mean = o; o = align256(o + (size_t)(kMeanParts + 1) * g.MR * g.MR * sizeof(double));
   w.total = o;
   return w;
 }
@@ -260,12 +259,12 @@ static WorkspaceLayout layout_lds(const PairPlan& pl) {
     owned = std::max(owned, (size_t)shard_tiles(pl.nA, pl.nBeff, pl.TI, pl.tj, pl.self_mode, r, pl.shard_count));
   const size_t tri = (size_t)pl.MR * (pl.MR + 1) / 2;
   size_t o = 0;
-  w.off_lt = o;   o = align_up(o + (size_t)pl.nA * pl.MR * pl.MR * pl.esz);
-  w.off_linv = o; o = align_up(o + (size_t)pl.nBeff * tri * pl.esz);  // packed lower triangles
-  w.off_slab = o; o = align_up(o + owned * (size_t)(pl.TI + pl.tj) * tri * pl.esz);
-  w.off_loss = o; o = align_up(o + owned * pl.esz);
-  w.off_flag = o; o = align_up(o + owned * 2 * sizeof(int));
-  w.off_rows = o; o = align_up(o + ((size_t)pl.nbi + 1) * sizeof(int));
+  w.off_lt = o;   o = align256(o + (size_t)pl.nA * pl.MR * pl.MR * pl.esz);
+  w.off_linv = o; o = align256(o + (size_t)pl.nBeff * tri * pl.esz);  // packed lower triangles
+  w.off_slab = o; o = align256(o + owned * (size_t)(pl.TI + pl.tj) * tri * pl.esz);
+  w.off_loss = o; o = align256(o + owned * pl.esz);
+  w.off_flag = o; o = align256(o + owned * 2 * sizeof(int));
+  w.off_rows = o; o = align256(o + ((size_t)pl.nbi + 1) * sizeof(int));
   w.off_mean = o;  // no class factor pass above 64
   w.total = o;
   return w;
@@ -1171,12 +1170,12 @@ static BwExtra bw_extra(size_t base, int nA, int nB, int m, int dtype) {
   bw_tiles(nA, nB, m, dtype, &nbi, &TJ);
   BwExtra x;
   size_t o = base;
-  x.off_tr = o;   o = align_up(o + (size_t)(nA + nBeff) * sizeof(double));
-  x.off_h = o;    o = align_up(o + (size_t)nbi * (nBeff + TJ) * sizeof(double));
-  x.off_hsum = o; o = align_up(o + (size_t)nBeff * sizeof(double));
-  x.off_sinv = o; o = align_up(o + (size_t)nBeff * m * m * sizeof(double));
-  x.off_g = o;    o = align_up(o + (size_t)nBeff * m * m * sizeof(double));
-  x.off_w = o;    o = align_up(o + (size_t)nBeff * m * m * sizeof(double));
+  x.off_tr = o;   o = align256(o + (size_t)(nA + nBeff) * sizeof(double));
+  x.off_h = o;    o = align256(o + (size_t)nbi * (nBeff + TJ) * sizeof(double));
+  x.off_hsum = o; o = align256(o + (size_t)nBeff * sizeof(double));
+  x.off_sinv = o; o = align256(o + (size_t)nBeff * m * m * sizeof(double));
+  x.off_g = o;    o = align256(o + (size_t)nBeff * m * m * sizeof(double));
+  x.off_w = o;    o = align256(o + (size_t)nBeff * m * m * sizeof(double));
   x.total = o;
   return x;
 }
@@ -1300,12 +1299,12 @@ int sqfa_airm_eigenvalues_backward(const void* A, int nA, const void* B, int nB,
 
 size_t sqfa_bw_workspace_bytes(int nA, int nB, int m, int dtype) {
   const size_t base = sqfa_airm_workspace_bytes(nA, nB, m, dtype);
-  return base == 0 ? 0 : bw_extra(align_up(base), nA, nB, m, dtype).total;
+  return base == 0 ? 0 : bw_extra(align256(base), nA, nB, m, dtype).total;
 }
 
 size_t sqfa_bw_workspace_bytes_sharded(int nA, int nB, int m, int dtype, int shard_count, int geometry_policy) {
   const size_t base = sqfa_airm_workspace_bytes_sharded(nA, nB, m, dtype, shard_count, geometry_policy);
-  return base == 0 ? 0 : bw_extra(align_up(base), nA, nB, m, dtype).total;
+  return base == 0 ? 0 : bw_extra(align256(base), nA, nB, m, dtype).total;
 }
 
 int sqfa_bw_pairwise(const void* A, int nA, const void* B, int nB, int m, int dtype, double eps, int sqrt_mode,
@@ -1319,7 +1318,7 @@ int sqfa_bw_pairwise(const void* A, int nA, const void* B, int nB, int m, int dt
 size_t sqfa_spd_function_workspace_bytes(int n, int m, int dtype) {
   Geometry g;
   if (n < 1 || m < 1 || !known_dtype(dtype) || !find_geometry(m, dtype, -1, &g, -1)) return 0;
-  return align_up((size_t)n * g.MR * g.MR * (dtype == SQFA_F32 ? 4 : 8));
+  return align256((size_t)n * g.MR * g.MR * (dtype == SQFA_F32 ? 4 : 8));
 }
 
 int sqfa_spd_function(const void* S, int n, int m, int dtype, int kind, void* F_out, double* U_out, double* lam_out,

@@ -10,7 +10,8 @@ the reference's (nA,nB,m,m) tensor (``log_euclidean[_sq]``: per-class logarithms
 tensors keep the reference's torch expression.  As ``SQFA``'s ``distance_fun``, ``bhattacharyya`` / ``hellinger`` /
 ``mahalanobis[_sq]`` train through one fused loss+gradient pass per closure (sqfa_gauss_pairwise_loss, GAUSS_FUSED_CLOSURE);
 as ``SecondMomentsSQFA``'s ``distance_fun``, ``log_euclidean[_sq]`` do the same through sqfa_log_euclidean_pairwise_loss
-(LOG_EUCLIDEAN_FUSED_CLOSURE, ``class_fused_spec``).  Called directly, every operator keeps its own implementation.
+(LOG_EUCLIDEAN_FUSED_CLOSURE).  Both are families of ``class_pair_spec``, the one registry of the class-pair losses
+(``sqfa_amd.divergences`` adds the Jeffreys family).  Called directly, every operator keeps its own implementation.
 """
 import torch
 
@@ -72,9 +73,34 @@ def _pair_matrix(A, B, scale, sqrt_mode):
 _FUSED = {}
 
 # bhattacharyya / hellinger / mahalanobis[_sq] as SQFA's distance_fun: one fused loss+gradient pass over the class pairs
-# (_native.GaussPairwiseLoss), captured in a HIP graph by the fitting loop.  False restores the generic closure
+# (_native.ClassPairLoss, family "gauss"), captured in a HIP graph by the fitting loop.  False restores the generic closure
 # (GaussPairTerms -> element-wise chain -> validity check on the host -> autograd backward, no graph).
 GAUSS_FUSED_CLOSURE = True
+
+# The class-pair losses (_native.PAIR_FAMILIES): operators whose closure runs as per-class stages around ONE pass over the
+# ordered class pairs.  fn -> (family, input kind, mode); a family's switch is read at every lookup.
+_CLASS_PAIR = {}
+_CLASS_PAIR_ENABLED = {}
+
+
+def register_class_pair(family, enabled, operators):
+    """Registers a family of class-pair losses: `operators` {fn: (input kind "gaussian" | "spd", mode)}, `enabled()` the
+    family's switch."""
+    _CLASS_PAIR_ENABLED[family] = enabled
+    _CLASS_PAIR.update({fn: (family,) + tuple(spec) for fn, spec in operators.items()})
+
+
+def class_pair_spec(fn):
+    """(family, input kind, mode) if `fn` is an operator a fused class-pair loss evaluates, else None; None for a family
+    whose switch is off.  family: "gauss" (mode: the SQFA_GAUSS_* kind code), "log_euclidean" or "jeffreys" (mode:
+    sqrt_mode).  THE lookup of model._closure_plan; the per-family lookups below are views of it."""
+    spec = _CLASS_PAIR.get(fn)
+    return spec if spec is not None and _CLASS_PAIR_ENABLED[spec[0]]() else None
+
+
+def _family_spec(fn, family):
+    spec = class_pair_spec(fn)
+    return spec[1:] if spec is not None and spec[0] == family else None
 
 
 def _fusable(kind, scale, sqrt_mode, metric="airm"):
@@ -162,17 +188,18 @@ def log_euclidean(A, B):
 
 
 # log_euclidean / log_euclidean_sq as SecondMomentsSQFA's distance_fun: per-class logarithm -> one pass over the class pairs
-# -> Daleckii-Krein backward in one native call (_native.LogEuclideanPairwiseLoss), captured in a HIP graph by the fitting
-# loop.  False restores the generic closure (SpdFunction -> cdist -> validity check on the host -> autograd, no graph).
-# These two are not pair-kernel operators: they stay out of _FUSED (fused_spec is None for them) and have their own lookup.
+# -> Daleckii-Krein backward in one native call (_native.ClassPairLoss, family "log_euclidean"), captured in a HIP graph by
+# the fitting loop.  False restores the generic closure (SpdFunction -> cdist -> validity check on the host -> autograd, no
+# graph).  These two are not pair-kernel operators: they stay out of _FUSED (fused_spec is None for them).
 LOG_EUCLIDEAN_FUSED_CLOSURE = True
-_CLASS_FUSED = {log_euclidean: ("spd", True), log_euclidean_sq: ("spd", False)}
+register_class_pair("log_euclidean", lambda: LOG_EUCLIDEAN_FUSED_CLOSURE,
+                    {log_euclidean: ("spd", True), log_euclidean_sq: ("spd", False)})
 
 
 def class_fused_spec(fn):
-    """(input kind, sqrt_mode) if `fn` is an operator whose closure runs as per-class stages around one pass over the
-    class pairs (log_euclidean, log_euclidean_sq), else None; None for everything when the switch is off."""
-    return _CLASS_FUSED.get(fn) if LOG_EUCLIDEAN_FUSED_CLOSURE else None
+    """(input kind, sqrt_mode) of the "log_euclidean" family of class_pair_spec (log_euclidean, log_euclidean_sq), else
+    None; None for everything when the switch is off."""
+    return _family_spec(fn, "log_euclidean")
 
 
 def _gaussian_inputs(statistics_A, statistics_B):
@@ -241,3 +268,8 @@ def fisher_rao_same_cov(statistics_A, statistics_B):
     d2 = mahalanobis_sq(statistics_A, statistics_B)
     # like the reference, sqrt(2) is a default-dtype tensor (float32-rounded under the float32 default)
     return torch.sqrt(torch.tensor(2.0)).to(d2.device) * torch.acosh(1 + d2 / 4)
+
+
+# the _FUSED entries with metric "gauss" are the "gauss" family of the class-pair losses (mode: their kind code)
+register_class_pair("gauss", lambda: GAUSS_FUSED_CLOSURE,
+                    {fn: (spec[0], spec[1]) for fn, spec in _FUSED.items() if spec[3] == "gauss"})

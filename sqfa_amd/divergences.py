@@ -18,12 +18,13 @@ cancel the digits that matter when two classes are close (in float32, two classe
 Called directly the operators are plain torch expressions: any device and dtype, differentiable by autograd, results
 (nA, nB) with unit batch dimensions squeezed as the operators of ``sqfa_amd.distances``.  As a model's ``distance_fun`` in
 ``fit()`` the closure runs through one native fused pass, ``sqfa_jeffreys_pairwise_loss`` (jeffreys_kernel.hip, captured in
-a HIP graph by the fitting loop), under ``JEFFREYS_FUSED_CLOSURE``; ``fused_spec`` is the registry ``model._closure_plan``
-asks.  The operators are deliberately not in ``distances._FUSED``: they are no pair-kernel operators.
+a HIP graph by the fitting loop), under ``JEFFREYS_FUSED_CLOSURE``: the "jeffreys" family of ``distances.class_pair_spec``,
+the registry ``model._closure_plan`` asks.  The operators are deliberately not in ``distances._FUSED``: they are no
+pair-kernel operators.
 """
 import torch
 
-from .distances import EPSILON, _batch_of_matrices, _gaussian_inputs, _squeeze_pairs
+from .distances import EPSILON, _batch_of_matrices, _family_spec, _gaussian_inputs, _squeeze_pairs, register_class_pair
 
 __all__ = ["jeffreys", "jeffreys_root", "jeffreys_spd", "jeffreys_spd_root"]
 
@@ -72,13 +73,14 @@ def jeffreys_spd_root(A, B):
 
 
 # As a model's distance_fun: per-class precisions -> one pass over the class pairs -> per-class chain rule through the
-# inverse, one native call (_native.JeffreysPairwiseLoss).  False restores the fitting loop's generic closure.
+# inverse, one native call (_native.ClassPairLoss, family "jeffreys").  False restores the fitting loop's generic closure.
 JEFFREYS_FUSED_CLOSURE = True
-_JEFFREYS_FUSED = {jeffreys: ("gaussian", False), jeffreys_root: ("gaussian", True),
-                   jeffreys_spd: ("spd", False), jeffreys_spd_root: ("spd", True)}
+register_class_pair("jeffreys", lambda: JEFFREYS_FUSED_CLOSURE,
+                    {jeffreys: ("gaussian", False), jeffreys_root: ("gaussian", True),
+                     jeffreys_spd: ("spd", False), jeffreys_spd_root: ("spd", True)})
 
 
 def fused_spec(fn):
-    """(input kind "gaussian" | "spd", sqrt_mode) when `fn` is an operator the native Jeffreys pass evaluates, else None;
-    None for everything when the switch is off."""
-    return _JEFFREYS_FUSED.get(fn) if JEFFREYS_FUSED_CLOSURE else None
+    """(input kind "gaussian" | "spd", sqrt_mode) when `fn` is an operator the native Jeffreys pass evaluates (the "jeffreys"
+    family of distances.class_pair_spec), else None; None for everything when the switch is off."""
+    return _family_spec(fn, "jeffreys")

@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 from torch.nn.utils.parametrize import register_parametrization, remove_parametrizations
 
-from . import _native, distances, divergences
+from . import _native, distances
+from . import divergences  # noqa: F401  (registers its operators with distances.class_pair_spec)
 from ._memo import TensorMemo
 from ._optim import fitting_loop
 from .constraints import FixedFilters, Identity, Orthogonal, Sphere, orthogonal
@@ -226,10 +227,9 @@ class SecondMomentsSQFA(nn.Module):
         fn, nm = self.distance_fun, self.noise_mat   # noise_mat: (K,K), the model's dtype (reading self.filters would run the parametrization)
         sharded = self.pair_shard is not None or self.class_shard is not None
         spec = distances.fused_spec(fn)
-        cspec = distances.class_fused_spec(fn) if spec is None else None
-        jspec = divergences.fused_spec(fn) if spec is None and cspec is None else None
+        pair = distances.class_pair_spec(fn)
         plan = inputs = None
-        if spec is not None and spec[0] == self._fused_kind and spec[3] != "gauss":
+        if pair is None and spec is not None and spec[0] == self._fused_kind:
             # affine-invariant / Bures-Wasserstein pair kernels: any device (through _pair_backend), any sharding
             shard, reducer = (self.pair_shard.shard, self.pair_shard.reduce) if self.pair_shard is not None else ((0, 1), None)
             plan = ClosurePlan("chain", spec[1], spec[2], spec[3], None, shard, reducer, None)
@@ -238,62 +238,39 @@ class SecondMomentsSQFA(nn.Module):
                 noise = self._noise_scalar() if single is not None else None   # a non-scalar noise_mat keeps the chain
                 if noise is not None:
                     plan, inputs = plan._replace(evaluator="single_node"), single + (noise,)
-        elif spec is not None and spec[0] == self._fused_kind:
-            # bhattacharyya / hellinger / mahalanobis[_sq]: single process, <= GAUSS_MAX_DIM filters, a dict of float32/64 GPU statistics
-            if sharded or nm.shape[0] > _native.GAUSS_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
+        elif pair is not None and pair[1] == self._fused_kind:
+            # the class-pair losses (bhattacharyya / hellinger / mahalanobis[_sq], log_euclidean[_sq], jeffreys[_spd][_root]):
+            # single process, filters within the family's limit, float32/64 GPU statistics of the model's input kind
+            family, kind, mode = pair
+            if sharded or nm.shape[0] > _native.PAIR_FAMILIES[family].limit or nm.dtype not in _NATIVE_DTYPES:
                 return None
-            if isinstance(prepared, ClassPoints):   # feature means and covariances of the points' dtype, on their device
-                if not (prepared.points.is_cuda and prepared.n_classes >= 2
-                        and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
-                    return None
-            elif prepared is not None:
-                if not isinstance(prepared, dict):
-                    return None
-                mu, cov = prepared["means"], prepared["covariances"]
-                cov_dtype = torch.promote_types(cov.dtype, nm.dtype)   # of F cov F^T + noise_mat
-                if not (cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[0] >= 2 and cov_dtype in _NATIVE_DTYPES
-                        and mu.dtype == cov_dtype and mu.device == cov.device):
-                    return None
-            plan = ClosurePlan("gauss", spec[1], spec[2], "gauss", None, (0, 1), None, None)
-        elif cspec is not None and cspec[0] == self._fused_kind:
-            # log_euclidean[_sq]: single process, within the per-class SPD functions' limit, a (C,D,D) float32/64 GPU tensor
-            if sharded or nm.shape[0] > _native.SPD_FUNCTION_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
+            if prepared is not None and not self._class_pair_statistics(prepared, kind, nm.dtype):
                 return None
-            if isinstance(prepared, ClassPoints):
-                if not (prepared.points.is_cuda and prepared.n_classes >= 2
-                        and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
-                    return None
-            elif prepared is not None and not (
-                    torch.is_tensor(prepared) and prepared.dim() == 3 and prepared.is_cuda and prepared.shape[0] >= 2
-                    and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
-                return None
-            plan = ClosurePlan("log_euclidean", None, cspec[1], None, None, (0, 1), None, None)
-        elif jspec is not None and jspec[0] == self._fused_kind:
-            # jeffreys[_root] (SQFA, a dict) / jeffreys_spd[_root] (SecondMomentsSQFA, a tensor): single process,
-            # <= JEFFREYS_MAX_DIM filters, float32/64 GPU statistics
-            if sharded or nm.shape[0] > _native.JEFFREYS_MAX_DIM or nm.dtype not in _NATIVE_DTYPES:
-                return None
-            if isinstance(prepared, ClassPoints):
-                if not (prepared.points.is_cuda and prepared.n_classes >= 2
-                        and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
-                    return None
-            elif prepared is not None and jspec[0] == "gaussian":
-                if not isinstance(prepared, dict):
-                    return None
-                mu, cov = prepared["means"], prepared["covariances"]
-                cov_dtype = torch.promote_types(cov.dtype, nm.dtype)   # of F cov F^T + noise_mat
-                if not (cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[0] >= 2 and cov_dtype in _NATIVE_DTYPES
-                        and mu.dtype == cov_dtype and mu.device == cov.device):
-                    return None
-            elif prepared is not None and not (
-                    torch.is_tensor(prepared) and prepared.dim() == 3 and prepared.is_cuda and prepared.shape[0] >= 2
-                    and torch.promote_types(prepared.dtype, nm.dtype) in _NATIVE_DTYPES):
-                return None
-            plan = ClosurePlan("jeffreys", None, jspec[1], None, None, (0, 1), None, None)
+            if family == "gauss":
+                plan = ClosurePlan("gauss", mode, spec[2], "gauss", None, (0, 1), None, None)
+            else:
+                plan = ClosurePlan(family, None, mode, None, None, (0, 1), None, None)
         if plan is None or prepared is None:
             return plan
         return plan._replace(weight=self._pair_weight(self._n_classes_total(prepared)), inputs=inputs,
                              pair_weights=self._pair_weights)
+
+    @staticmethod
+    def _class_pair_statistics(prepared, kind, noise_dtype):
+        """True when `prepared` is what a class-pair loss of input kind `kind` takes: a ClassPoints, a dict of means and
+        covariances ("gaussian") or a (C,D,D) tensor ("spd"), at least two classes, on the GPU, the features float32/64."""
+        if isinstance(prepared, ClassPoints):   # feature moments of the points' dtype, on their device
+            return bool(prepared.points.is_cuda and prepared.n_classes >= 2
+                        and torch.promote_types(prepared.dtype, noise_dtype) in _NATIVE_DTYPES)
+        if kind == "gaussian":
+            if not isinstance(prepared, dict):
+                return False
+            mu, cov = prepared["means"], prepared["covariances"]
+            cov_dtype = torch.promote_types(cov.dtype, noise_dtype)   # of F cov F^T + noise_mat
+            return bool(cov.is_cuda and cov.dim() == 3 and mu.dim() == 2 and cov.shape[0] >= 2 and cov_dtype in _NATIVE_DTYPES
+                        and mu.dtype == cov_dtype and mu.device == cov.device)
+        return bool(torch.is_tensor(prepared) and prepared.dim() == 3 and prepared.is_cuda and prepared.shape[0] >= 2
+                    and torch.promote_types(prepared.dtype, noise_dtype) in _NATIVE_DTYPES)
 
     def _fused_closure_loss(self, prepared):
         """(loss, flags) through the fused loss+gradient evaluator of _closure_plan, or None when there is none (the
@@ -316,26 +293,19 @@ class SecondMomentsSQFA(nn.Module):
         return _native.PairwiseLoss.apply(S, plan.scale, distances.EPSILON, plan.sqrt_mode, plan.weight, plan.shard,
                                           plan.reducer, plan.metric, plan.pair_weights)
 
-    def _evaluate_gauss(self, plan, prepared):
-        """parametrization -> projection -> noise -> _native.GaussPairwiseLoss (one fused pass over the class pairs)."""
-        stats = self._feature_statistics(prepared, True)
-        return _native.GaussPairwiseLoss.apply(stats["means"], stats["covariances"], int(plan.scale), distances.EPSILON,
-                                               plan.weight, plan.pair_weights)
-
-    def _evaluate_log_euclidean(self, plan, prepared):
-        """parametrization -> projection (native where it applies) -> noise -> _native.LogEuclideanPairwiseLoss."""
-        return _native.LogEuclideanPairwiseLoss.apply(self._feature_scatters(prepared, True), plan.sqrt_mode,
-                                                      distances.EPSILON, plan.weight, plan.pair_weights)
-
-    def _evaluate_jeffreys(self, plan, prepared):
-        """parametrization -> projection (native where it applies) -> noise -> _native.JeffreysPairwiseLoss: with the
-        feature means and covariances (SQFA), or the feature scatters and zero means (SecondMomentsSQFA)."""
+    def _evaluate_class_pairs(self, plan, prepared):
+        """parametrization -> projection (native where it applies) -> noise -> _native.ClassPairLoss (one fused pass over
+        the class pairs): with the feature means and covariances (SQFA), or the feature scatters and no means
+        (SecondMomentsSQFA)."""
         if self._fused_kind == "gaussian":
             stats = self._feature_statistics(prepared, True)
             mu, cov = stats["means"], stats["covariances"]
         else:
             mu, cov = None, self._feature_scatters(prepared, True)
-        return _native.JeffreysPairwiseLoss.apply(mu, cov, plan.sqrt_mode, distances.EPSILON, plan.weight, plan.pair_weights)
+        mode = int(plan.scale) if plan.evaluator == "gauss" else plan.sqrt_mode
+        return _native.ClassPairLoss.apply(mu, cov, plan.evaluator, mode, distances.EPSILON, plan.weight, plan.pair_weights)
+
+    _evaluate_gauss = _evaluate_log_euclidean = _evaluate_jeffreys = _evaluate_class_pairs
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once

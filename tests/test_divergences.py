@@ -167,7 +167,7 @@ def test_native_call_refuses_cpu_tensors():
     with pytest.raises(RuntimeError, match="GPU only"):
         _native.hip_jeffreys_pairwise_loss(mu, cov, False, 1e-6, -0.1)
     with pytest.raises(RuntimeError, match="GPU only"):
-        _native.JeffreysPairwiseLoss.apply(None, cov, True, 1e-6, -0.1)
+        _native.ClassPairLoss.apply(None, cov, "jeffreys", True, 1e-6, -0.1)
 
 
 @pytest.mark.parametrize("fn_name", NAMES)

@@ -1,4 +1,4 @@
-"""CPU tests of the fused Gaussian pair closure (sqfa_gauss_pairwise_loss, _native.GaussPairwiseLoss): exported symbols and
+"""CPU tests of the fused Gaussian pair closure (sqfa_gauss_pairwise_loss, _native.ClassPairLoss): exported symbols and
 bindings, host-side argument validation (every code is returned before any launch, so no GPU is needed), workspace
 query, the fused specs of the four operators and the models' _has_fused_closure()."""
 import ctypes
@@ -120,4 +120,4 @@ def test_cpu_statistics_keep_the_generic_closure():
     loss, _ = model.fit(data_statistics=stats, max_epochs=3, show_progress=False, return_loss=True)
     assert torch.isfinite(loss).all() and loss[-1] < loss[0]
     with pytest.raises(RuntimeError, match="GPU only"):
-        _native.GaussPairwiseLoss.apply(stats["means"][:, :2], stats["covariances"][:, :2, :2], 0, 1e-6, -0.1)
+        _native.ClassPairLoss.apply(stats["means"][:, :2], stats["covariances"][:, :2, :2], "gauss", 0, 1e-6, -0.1)

@@ -1,5 +1,5 @@
 """GPU tests of the fused Gaussian pair closure: sqfa_gauss_pairwise_loss (fused mode of the Gaussian pair kernels),
-_native.GaussPairwiseLoss and SQFA's closure with bhattacharyya / hellinger / mahalanobis_sq / mahalanobis as
+_native.ClassPairLoss (family "gauss") and SQFA's closure with bhattacharyya / hellinger / mahalanobis_sq / mahalanobis as
 distance_fun, against the reference's values (golden G8, tests/golden/make_golden_gauss_closure.py) and a float64 torch
 expression of the definitions (tests/gauss_oracle.py).
 

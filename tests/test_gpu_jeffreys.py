@@ -1,5 +1,5 @@
 """GPU tests of the fused Jeffreys closure: sqfa_jeffreys_pairwise_loss (per-class precisions -> one O(m^2) pass over the
-ordered class pairs -> per-class chain rule through the inverse), _native.JeffreysPairwiseLoss and the closures of SQFA
+ordered class pairs -> per-class chain rule through the inverse), _native.ClassPairLoss (family "jeffreys") and the closures of SQFA
 (jeffreys, jeffreys_root) and SecondMomentsSQFA (jeffreys_spd, jeffreys_spd_root), against the float64 textbook form of
 tests/jeffreys_oracle.py and its autograd gradients.
 

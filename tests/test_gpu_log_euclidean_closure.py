@@ -1,5 +1,5 @@
 """GPU tests of the fused log-Euclidean closure: sqfa_log_euclidean_pairwise_loss (per-class logarithm -> one pass over the
-ordered class pairs -> Daleckii-Krein backward), _native.LogEuclideanPairwiseLoss and SecondMomentsSQFA's closure with
+ordered class pairs -> Daleckii-Krein backward), _native.ClassPairLoss (family "log_euclidean") and SecondMomentsSQFA's closure with
 log_euclidean / log_euclidean_sq as distance_fun, against the reference's values (golden G9,
 tests/golden/make_golden_log_euclidean_closure.py) and a float64 CPU expression of the definition (eigh -> log -> explicit
 differences, `_expression` below).

@@ -1,4 +1,4 @@
-"""CPU tests of the fused log-Euclidean closure (sqfa_log_euclidean_pairwise_loss, _native.LogEuclideanPairwiseLoss): exported
+"""CPU tests of the fused log-Euclidean closure (sqfa_log_euclidean_pairwise_loss, _native.ClassPairLoss): exported
 symbols and bindings, host-side argument validation (every code is returned before any HIP call, so no GPU is needed), the
 workspace query, distances.class_fused_spec and the models' _has_fused_closure()."""
 import ctypes
@@ -143,6 +143,6 @@ def test_cpu_statistics_keep_the_generic_closure():
         loss, _ = model.fit(data_statistics=scatters, max_epochs=3, show_progress=False, return_loss=True)
         assert torch.isfinite(loss).all() and loss[-1] < loss[0]
     with pytest.raises(RuntimeError, match="GPU only"):
-        _native.LogEuclideanPairwiseLoss.apply(scatters[:, :2, :2], True, 1e-6, -0.1)
+        _native.ClassPairLoss.apply(None, scatters[:, :2, :2], "log_euclidean", True, 1e-6, -0.1)
     with pytest.raises(RuntimeError, match="GPU only"):
         _native.hip_log_euclidean_pairwise_loss(scatters[:, :2, :2], False, 1e-6, -0.1)

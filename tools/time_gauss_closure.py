@@ -2,7 +2,7 @@
 
   (a) generic   the fitting loop's generic closure: get_class_distances (GaussPairTerms + element-wise chain), validity
                 check on the host, tril gather + mean, autograd backward
-  (b) fused     _fused_closure_loss (projection -> noise -> GaussPairwiseLoss) + backward, eager
+  (b) fused     _fused_closure_loss (projection -> noise -> ClassPairLoss) + backward, eager
   (c) graph     the same, captured once in a HIP graph and replayed
   pairs         the pair stage alone on the (C,K) / (C,K,K) feature statistics: sqfa_gauss_pair_terms forward + backward
                 (Q and LD with unit upstream gradients: the two launches the fused call replaces, without the element-wise

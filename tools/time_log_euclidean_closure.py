@@ -2,7 +2,7 @@
 
   generic   distances.LOG_EUCLIDEAN_FUSED_CLOSURE = False: the fitting loop's generic closure (projection -> SpdFunction ->
             cdist -> validity check on the host -> tril gather + mean -> autograd backward), never captured
-  fused     the switch on: projection -> _native.LogEuclideanPairwiseLoss, captured in a HIP graph after the warm-up closures
+  fused     the switch on: projection -> _native.ClassPairLoss, captured in a HIP graph after the warm-up closures
 
     python tools/time_log_euclidean_closure.py [--out profiles/log_euclidean_closure_time.txt] [--label NAME] [--quick]
 

@@ -451,6 +451,36 @@ int sqfa_jeffreys_pairwise_loss(const void *mu, const void *cov, int n, int m, i
                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Fused closure loss of the Stein divergence (Jensen-Bregman log-det divergence, S-divergence) between the n SPD matrices
+ * S_c:
+ *     S_ij = logdet((S_i + S_j)/2) - 1/2 logdet S_i - 1/2 logdet S_j
+ *     sqrt_mode 0   D_ij = S_ij
+ *     sqrt_mode 1   D_ij = sqrt(|S_ij| + eps)
+ *     loss = sum_{i>j} w_ij D_ij,  w_ij = uniform_weight, or pair_weights[i*n + j]
+ * together with its gradient  gradS_i = sum_{j != i} c_ij 1/2 (Sbar_ij^-1 - S_i^-1),  Sbar_ij = (S_i + S_j)/2,  c_ij = w_ij
+ * (sqrt_mode 0) or w_ij sign(S_ij) / (2 sqrt(|S_ij| + eps)) (sqrt_mode 1).  Stages, all on the caller's stream
+ * (stein_kernel.hip): per-class Cholesky (double inside) for logdet S_c and S_c^-1; ONE pass over the ordered pairs that
+ * factors Sbar_ij in registers, one lane group per pair, every class row with one writer; a per-class finish; a
+ * one-workgroup reduction of the per-class partial losses and counters.  No host read-back, no allocation, no float
+ * atomics: results are bitwise reproducible and the call may be captured in a HIP graph.
+ *   S (n,m,m): row-major, dtype, symmetric; n >= 2, 1 <= m <= 64
+ *   pair_weights (n,n) dtype, symmetric, or NULL (then uniform_weight).  The pass visits the ordered pairs: row i reads w_ij,
+ *   row j reads w_ji, the loss counts j < i with w_ij.  The diagonal is never read into a result.  Every pair is evaluated
+ *   and counted in nonfinite_out whatever its weight; dist_out is unweighted.
+ *   loss_out (1) dtype or NULL; gradS_out (n,m,m, exactly symmetric) or NULL (forward only); dist_out (n,n) or NULL: D_ij,
+ *   both triangles, the diagonal 0 or sqrt(eps); nonfinite_out (2) int32 or NULL: {#NaN, #inf} among the pairs i > j (a
+ *   class with a pivot that is not positive yields NaN for its pairs and is counted, never a fault)
+ *   workspace: sqfa_stein_workspace_bytes(n, m, dtype) bytes (0 = shape or dtype not supported)
+ * Returns SQFA_ERR_BAD_ARGUMENT (null S, n < 2, m < 1, dtype, sqrt_mode outside {0, 1}), SQFA_ERR_UNSUPPORTED_M (m > 64),
+ * SQFA_ERR_WORKSPACE, checked in that order; every argument check runs before the first HIP call.
+ */
+size_t sqfa_stein_workspace_bytes(int n, int m, int dtype);
+int sqfa_stein_pairwise_loss(const void *S, int n, int m, int dtype, int sqrt_mode,
+                             double eps, const void *pair_weights, double uniform_weight,
+                             void *loss_out, void *gradS_out, void *dist_out, int *nonfinite_out,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the
  * reference (src/sqfa/linalg.py:165-183, 121-141: torch.linalg.eigh + einsum), as used by log_euclidean[_sq]
  * (src/sqfa/distances.py:92-138).  The eigen-decomposition is one-sided Jacobi, run to convergence, on the Cholesky

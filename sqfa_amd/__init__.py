@@ -4,9 +4,10 @@ Same sub-modules and public names as the reference package ``sqfa`` (model, dist
 linalg, statistics, constraints, _optim); the pairwise affine-invariant distance path is
 implemented by hand-written HIP kernels behind the C ABI in include/sqfa_hip.h.  ``transport`` adds the
 Bures-Wasserstein / Wasserstein distances of the reference's tutorial on the same kernels; ``divergences`` adds the
-Jeffreys (symmetric Kullback-Leibler) divergence with its own native fused closure.
+Jeffreys (symmetric Kullback-Leibler) divergence with its own native fused closure; ``logdet`` the Stein (Jensen-Bregman
+log-det) divergence with its own.
 """
-from . import _optim, constraints, distances, divergences, linalg, model, parallel, statistics, transport  # noqa: F401
+from . import _optim, constraints, distances, divergences, linalg, logdet, model, parallel, statistics, transport  # noqa: F401
 
-__all__ = ["model", "distances", "linalg", "statistics", "constraints", "parallel", "transport", "divergences"]
+__all__ = ["model", "distances", "linalg", "statistics", "constraints", "parallel", "transport", "divergences", "logdet"]
 __version__ = "0.1.0"

@@ -454,12 +454,27 @@ PAIR_FAMILIES = {
 }
 
 
+# The Stein family (sqfa_amd.logdet) has its own table: the keys of PAIR_FAMILIES are the three families the registry was
+# unified over, and tests pin them.  pair_family() is the lookup over both.
+STEIN_MAX_DIM = 64
+LOGDET_PAIR_FAMILIES = {
+    "stein": PairFamily("sqfa_stein_pairwise_loss", "sqfa_stein_pairwise_loss", "sqfa_stein_workspace_bytes", STEIN_MAX_DIM,
+                        False, "Stein", "matrix size {m} exceeds the native Stein kernels' limit ({limit})"),
+}
+
+
+def pair_family(family):
+    """The PairFamily row of a class-pair family, whichever table holds it."""
+    row = PAIR_FAMILIES.get(family)
+    return row if row is not None else LOGDET_PAIR_FAMILIES[family]
+
+
 def _class_pair_call(family, mu, cov, mode, eps, weight, want_grad, want_dist, pair_weights):
     """One fused class-pair loss on the current stream (no host read-back, workspace from the torch allocator: safe inside
     a graph capture): cov (n,m,m) SPD, mu (n,m) or None, `mode` the family's kind code / sqrt_mode, `pair_weights` symmetric
     (n,n) per-pair weights in place of `weight`.  Returns dict(loss, gmu, gcov, dist, nonfinite) (None where not requested;
     gmu None without means)."""
-    fam = PAIR_FAMILIES[family]
+    fam = pair_family(family)
     lib = _lib.load()
     if not cov.is_cuda:
         raise RuntimeError(f"sqfa_amd's fused {fam.what} pair loss runs on the GPU only (no CPU fallback)")
@@ -520,13 +535,21 @@ def hip_jeffreys_pairwise_loss(mu, cov, sqrt_mode, eps, weight, want_grad=True, 
     return class_pair_loss("jeffreys", mu, cov, bool(sqrt_mode), eps, weight, want_grad, want_dist, pair_weights)
 
 
+def hip_stein_pairwise_loss(S, sqrt_mode, eps, weight, want_grad=True, want_dist=False, pair_weights=None):
+    """sqfa_stein_pairwise_loss on the current stream (class_pair_loss, family "stein"): S (n,m,m) SPD.  Returns dict(loss,
+    gS, dist, nonfinite) (None where not requested)."""
+    out = class_pair_loss("stein", None, S, bool(sqrt_mode), eps, weight, want_grad, want_dist, pair_weights)
+    return {"loss": out["loss"], "gS": out["gcov"], "dist": out["dist"], "nonfinite": out["nonfinite"]}
+
+
 class ClassPairLoss(_SavedGradientLoss):
     """Fused closure loss of a class-pair family (PAIR_FAMILIES): weight * sum over the unordered class pairs of the
     distance, with its gradient wrt means (C,K) (None for a means-free loss: log_euclidean, jeffreys_spd) and covariances
     (C,K,K), from ONE native call -- in place of the operator's torch / per-pair-term expression, the tril gather, the mean
     and their autograd backward.  family "gauss": bhattacharyya / hellinger / mahalanobis[_sq] (mode: _lib.SQFA_GAUSS_*);
     "log_euclidean": log_euclidean (mode True) / log_euclidean_sq (False), the pass over the pairs between the per-class
-    logarithm and its Daleckii-Krein backward; "jeffreys": jeffreys[_spd] (mode False) / their _root forms (True).
+    logarithm and its Daleckii-Krein backward; "jeffreys": jeffreys[_spd] (mode False) / their _root forms (True); "stein":
+    logdet.stein (False) / stein_root (True).
     Returns (loss, flags {#NaN, #inf})."""
 
     @staticmethod

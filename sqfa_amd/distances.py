@@ -11,7 +11,7 @@ tensors keep the reference's torch expression.  As ``SQFA``'s ``distance_fun``, 
 ``mahalanobis[_sq]`` train through one fused loss+gradient pass per closure (sqfa_gauss_pairwise_loss, GAUSS_FUSED_CLOSURE);
 as ``SecondMomentsSQFA``'s ``distance_fun``, ``log_euclidean[_sq]`` do the same through sqfa_log_euclidean_pairwise_loss
 (LOG_EUCLIDEAN_FUSED_CLOSURE).  Both are families of ``class_pair_spec``, the one registry of the class-pair losses
-(``sqfa_amd.divergences`` adds the Jeffreys family).  Called directly, every operator keeps its own implementation.
+(``sqfa_amd.divergences`` adds the Jeffreys family, ``sqfa_amd.logdet`` the Stein family).  Called directly, every operator keeps its own implementation.
 """
 import torch
 
@@ -92,7 +92,7 @@ def register_class_pair(family, enabled, operators):
 
 def class_pair_spec(fn):
     """(family, input kind, mode) if `fn` is an operator a fused class-pair loss evaluates, else None; None for a family
-    whose switch is off.  family: "gauss" (mode: the SQFA_GAUSS_* kind code), "log_euclidean" or "jeffreys" (mode:
+    whose switch is off.  family: "gauss" (mode: the SQFA_GAUSS_* kind code), "log_euclidean", "jeffreys" or "stein" (mode:
     sqrt_mode).  THE lookup of model._closure_plan; the per-family lookups below are views of it."""
     spec = _CLASS_PAIR.get(fn)
     return spec if spec is not None and _CLASS_PAIR_ENABLED[spec[0]]() else None

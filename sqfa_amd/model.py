@@ -12,6 +12,7 @@ from torch.nn.utils.parametrize import register_parametrization, remove_parametr
 
 from . import _native, distances
 from . import divergences  # noqa: F401  (registers its operators with distances.class_pair_spec)
+from . import logdet  # noqa: F401  (likewise)
 from ._memo import TensorMemo
 from ._optim import fitting_loop
 from .constraints import FixedFilters, Identity, Orthogonal, Sphere, orthogonal
@@ -239,10 +240,11 @@ class SecondMomentsSQFA(nn.Module):
                 if noise is not None:
                     plan, inputs = plan._replace(evaluator="single_node"), single + (noise,)
         elif pair is not None and pair[1] == self._fused_kind:
-            # the class-pair losses (bhattacharyya / hellinger / mahalanobis[_sq], log_euclidean[_sq], jeffreys[_spd][_root]):
+            # the class-pair losses (bhattacharyya / hellinger / mahalanobis[_sq], log_euclidean[_sq], jeffreys[_spd][_root],
+            # stein[_root]):
             # single process, filters within the family's limit, float32/64 GPU statistics of the model's input kind
             family, kind, mode = pair
-            if sharded or nm.shape[0] > _native.PAIR_FAMILIES[family].limit or nm.dtype not in _NATIVE_DTYPES:
+            if sharded or nm.shape[0] > _native.pair_family(family).limit or nm.dtype not in _NATIVE_DTYPES:
                 return None
             if prepared is not None and not self._class_pair_statistics(prepared, kind, nm.dtype):
                 return None
@@ -306,6 +308,7 @@ class SecondMomentsSQFA(nn.Module):
         return _native.ClassPairLoss.apply(mu, cov, plan.evaluator, mode, distances.EPSILON, plan.weight, plan.pair_weights)
 
     _evaluate_gauss = _evaluate_log_euclidean = _evaluate_jeffreys = _evaluate_class_pairs
+    _evaluate_stein = _evaluate_class_pairs
 
     def _noise_scalar(self):
         """feature_noise as a host scalar when noise_mat is (still) noise * I, else None; read back once

@@ -21,6 +21,10 @@
  *       autograd backward of all of the above (torch LinalgEighBackward0 x2, BmmBackward)
  *                                  via gradA_out / gradB_out (closed form)
  *
+ *   sqfa_gauss_class_factors, sqfa_gauss_scores   the step the reference's tutorial judges a fit by
+ *       get_qda_accuracy           docs/source/tutorials/digit_processing.md (scikit-learn's
+ *                                  QuadraticDiscriminantAnalysis on the features, on the host)
+ *
  * The reference-side binding a maintainer would add is shown in INTEGRATION.md.
  */
 #ifndef SQFA_HIP_H
@@ -57,7 +61,8 @@ int sqfa_hip_max_dim(void);            /* largest matrix size m of the pair func
  *                 then counts pairs, not wave rounds); geometry_policy, class_factor_policy and mean_metric_policy are
  *                 ignored (no small-launch rows, no class factor pass).  Workspace: the factors (nA m^2 + nB m^2 / 2 values)
  *                 and a slab of P (1/TI + 1/TJ) lower triangles for P pairs: 2.1 GB at C = 1000, m = 128, float32.
- * The per-class SPD functions (sqfa_spd_function*) and the Gaussian pair terms keep m <= 64, the projection K <= 64.
+ * The per-class SPD functions (sqfa_spd_function*) and the Gaussian pair terms keep m <= 64, the projection and the
+ * Gaussian class scores (sqfa_gauss_scores) K <= 64.
  */
 const char *sqfa_hip_last_error(void); /* text of the last HIP error seen by this library (host thread local) */
 
@@ -479,6 +484,46 @@ int sqfa_stein_pairwise_loss(const void *S, int n, int m, int dtype, int sqrt_mo
                              double eps, const void *pair_weights, double uniform_weight,
                              void *loss_out, void *gradS_out, void *dist_out, int *nonfinite_out,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Gaussian class scores: quadratic discriminant analysis in feature space.  For features z_n (K), class means mu_c, class
+ * covariances Sigma_c = L_c L_c^T and priors pi_c
+ *     score[n][c] = -1/2 |L_c^-1 (z_n - mu_c)|^2 - sum_k log (L_c)_kk - K/2 log 2 pi + log pi_c  =  log p(z_n, c),
+ * evaluated in this whitened-difference form (gauss_scores_kernel.hip).  Two entries, both on the caller's stream, nothing
+ * allocated, synchronised or read back, no float atomics (bitwise reproducible), usable inside a HIP graph:
+ *
+ * sqfa_gauss_class_factors -- once per classifier; one workgroup per class, Cholesky in double in LDS.
+ *   means (C,K) dtype or NULL (zero-mean classes); cov (C,K,K) dtype, symmetric (the lower triangle is read);
+ *   log_priors (C) FLOAT64 or NULL (uniform: -log C); -inf is a class that never wins
+ *   W_out (C,K,K) dtype: W_c = L_c^-1, lower triangular, exact zeros above the diagonal
+ *   offset_out (C) FLOAT64: -sum_k log (L_c)_kk - K/2 log 2 pi + log pi_c
+ *   bad_out (1) int32: the number of classes with a pivot that is not positive and finite, a mean that is not finite, or a
+ *   log prior that is NaN or +inf (their W and offset are NaN).  The call sets it: the caller reads it once.
+ *
+ * sqfa_gauss_scores -- once per batch of samples.  A workgroup owns 64 samples and a range of classes; per class
+ *   y = W_c (Z_tile - mu_c) on the exact MFMA (16x16x4), the blocks of W_c above the diagonal skipped, rows of y squared and
+ *   summed, the offset added.  The running (max, index) and (max, sum exp) of every sample are carried in registers across
+ *   the classes and, where the classes are split over workgroups, merged in the order of the splits by a second launch.
+ *   Z (N,K) dtype; means (C,K) or NULL (no subtraction); W, offset as written by sqfa_gauss_class_factors
+ *   Each output may be NULL (not wanted):
+ *   scores_out (N,C) dtype; argmax_out (N) int64 with best_out (N) dtype, the winning score (best_out needs argmax_out);
+ *   logsumexp_out (N) dtype: log p(z_n).  With scores_out == NULL nothing of size (N,C) is written anywhere.
+ *   Ties go to the lowest class index; a class whose score is -inf never wins against a finite one and adds nothing to the
+ *   sum.  A sample whose row holds a NaN gets index -1, NaN in best_out and logsumexp_out, and is counted in
+ *   nonfinite_out (1) int32 (never NULL; the call sets it).  argmax_out / best_out / logsumexp_out are the same bits
+ *   whether or not scores_out is asked for.
+ *   workspace: sqfa_gauss_scores_workspace_bytes(N, C, K, dtype) bytes (0 = shape or dtype not supported): the partial
+ *   reductions of at most 16 class splits, 16 bytes (float32) per sample and split; no N C term.
+ * 1 <= K <= 64, C >= 1, N >= 1.  Return SQFA_ERR_BAD_ARGUMENT (null input, sizes < 1, dtype, best_out without argmax_out),
+ * SQFA_ERR_UNSUPPORTED_M (K > 64, or more than 2^31 - 1 sample tiles), SQFA_ERR_WORKSPACE, checked in that order; every
+ * argument check runs before the first HIP call.
+ */
+size_t sqfa_gauss_scores_workspace_bytes(long long N, int C, int K, int dtype);
+int sqfa_gauss_class_factors(const void *means, const void *cov, const double *log_priors, int C, int K, int dtype,
+                             void *W_out, double *offset_out, int *bad_out, void *stream);
+int sqfa_gauss_scores(const void *Z, long long N, const void *means, const void *W, const double *offset, int C, int K,
+                      int dtype, void *scores_out, long long *argmax_out, void *best_out, void *logsumexp_out,
+                      int *nonfinite_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the

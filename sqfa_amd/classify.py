@@ -1,0 +1,319 @@
+"""Gaussian class scores: quadratic discriminant analysis (QDA) in feature space, the step the reference's tutorial judges
+every fit by (QDA accuracy on held-out samples), without leaving the GPU.
+
+For features z (K), class means mu_c, class covariances Sigma_c = L_c L_c^T and priors pi_c
+
+    score[n, c] = -1/2 |L_c^-1 (z_n - mu_c)|^2 - sum_k log (L_c)_kk - K/2 log 2 pi + log pi_c  =  log p(z_n, c)
+
+evaluated in this whitened-difference form (the expanded quadratic z^T P z - 2 b^T z + const cancels in float32).
+
+    gaussian_class_scores(Z, means, covariances, priors=None)      (N, C) scores
+    GaussianClassifier(means, covariances, priors=None)            scores / predict / log_evidence / predict_log_proba /
+                                                                   predict_proba / accuracy of features Z (N, K)
+    FeatureClassifier.from_model(model, X, y | data_statistics)    the same of raw points X (N, D), through the model's filters
+
+float32 / float64 GPU tensors with K <= 64 run on the native kernels (gauss_scores_kernel.hip): a factor pass once per
+classifier (sqfa_gauss_class_factors) and one pass per batch of samples (sqfa_gauss_scores) that carries the argmax and the
+log-sum-exp of every sample across the classes in registers, so that ``predict``, ``log_evidence`` and ``accuracy`` never
+form anything of size (N, C).  Native results carry no graph.  CPU tensors, other dtypes, K > 64,
+``NATIVE_CLASS_SCORES = False`` and any input that requires grad while grad is enabled evaluate the same formula as a torch
+expression, chunked over the classes so that its (classes, N, K) temporary stays under ``FALLBACK_BYTES``; that expression is
+differentiable.
+"""
+import math
+
+import torch
+
+from . import _lib, _native
+from .statistics import ClassPoints, class_statistics
+
+__all__ = ["gaussian_class_scores", "GaussianClassifier", "FeatureClassifier"]
+
+NATIVE_CLASS_SCORES = True
+NATIVE_MAX_FEATURES = 64
+# the torch expression's (classes, N, K) temporaries (the differences and the solve's result) stay below this many bytes
+FALLBACK_BYTES = 1 << 28
+_NATIVE_DTYPES = (torch.float32, torch.float64)
+
+
+def _log_priors(priors, n_classes, device):
+    """(C,) float64 log priors: None / "uniform" -> -log C; a (C,) tensor-like of non-negative weights with a positive sum,
+    normalised (a zero weight gives -inf: a class that never wins)."""
+    if priors is None or (isinstance(priors, str) and priors == "uniform"):
+        return torch.full((n_classes,), -math.log(n_classes), dtype=torch.float64, device=device)
+    if isinstance(priors, str):
+        raise ValueError(f"priors must be None, 'uniform' or (n_classes,) non-negative weights, got {priors!r}")
+    try:
+        w = torch.as_tensor(priors).detach().to(device=device, dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError) as err:
+        raise ValueError("priors must be None, 'uniform' or (n_classes,) non-negative weights") from err
+    if w.shape != (n_classes,):
+        raise ValueError(f"priors must have shape ({n_classes},), got {tuple(w.shape)}")
+    lo, total = torch.stack((w.min(), w.sum())).tolist()
+    if not (lo >= 0.0 and 0.0 < total < math.inf):   # also refuses NaN
+        raise ValueError("priors must be non-negative and finite with a positive sum")
+    return torch.log(w / total)
+
+
+def _grad_wanted(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _native_applies(*tensors):
+    """float32 / float64 tensors on one GPU, none of which asks for a gradient, with the switch on."""
+    first = tensors[0]
+    return bool(NATIVE_CLASS_SCORES and first.is_cuda and first.dtype in _NATIVE_DTYPES
+                and all(t is None or (t.device == first.device and t.dtype == first.dtype) for t in tensors)
+                and not _grad_wanted(*tensors))
+
+
+class GaussianClassifier:
+    """Quadratic classifier of features from the class Gaussians N(mu_c, Sigma_c) and priors pi_c.
+
+    means (C, K) or None (zero means), covariances (C, K, K), priors None / "uniform" / (C,) non-negative weights
+    (normalised).  Construction factors every class once and raises ValueError, naming the number of bad classes, when a
+    class is not symmetric positive definite or not finite.  Attributes: ``n_classes``, ``n_features``, ``log_priors``
+    ((C,) float64).  Samples with a non-finite score row raise ValueError with their count.
+    """
+
+    def __init__(self, means, covariances, priors=None):
+        cov = torch.as_tensor(covariances)
+        if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2] or not cov.is_floating_point() or 0 in cov.shape:
+            raise ValueError("covariances must be a floating-point tensor of shape (n_classes, n_features, n_features)")
+        C, K = cov.shape[0], cov.shape[-1]
+        mu = None
+        if means is not None:
+            mu = torch.as_tensor(means).to(device=cov.device, dtype=cov.dtype)
+            if mu.shape != (C, K):
+                raise ValueError(f"means must have shape ({C}, {K}), got {tuple(mu.shape)}")
+        self.n_classes, self.n_features = C, K
+        self.means, self.covariances = mu, cov
+        self.log_priors = _log_priors(priors, C, cov.device)
+        self._factors = None   # native: (W (C,K,K), offset (C,) float64)
+        self._torch = None     # the torch expression's (W = L^-1 (C,K,K), offset (C,) in the dtype)
+        if K <= NATIVE_MAX_FEATURES and _native_applies(cov, mu):
+            bad = self._native_factors()
+        else:
+            bad = self._torch_factors()
+        if bad:
+            raise ValueError(f"{bad} of {C} classes are not symmetric positive definite or not finite")
+
+    @property
+    def dtype(self):
+        return self.covariances.dtype
+
+    @property
+    def device(self):
+        return self.covariances.device
+
+    # ------------------------------------------------------------------ factors
+    def _native_factors(self):
+        lib = _lib.load()
+        cov = self.covariances.detach().contiguous()
+        mu = self.means.detach().contiguous() if self.means is not None else None
+        C, K = self.n_classes, self.n_features
+        with _native._on_stream(cov.device) as stream:
+            W = torch.empty_like(cov)
+            offset = torch.empty(C, dtype=torch.float64, device=cov.device)
+            bad = torch.empty(1, dtype=torch.int32, device=cov.device)
+            lp = self.log_priors.contiguous()
+            _lib.check(lib.sqfa_gauss_class_factors(_native._ptr(mu), _native._ptr(cov), _native._ptr(lp), C, K,
+                                                    _native._dtype_code(cov), _native._ptr(W), _native._ptr(offset),
+                                                    _native._ptr(bad), stream), "sqfa_gauss_class_factors")
+        self._means_native = mu
+        self._factors = (W, offset)
+        return int(bad.item())
+
+    def _torch_factors(self):
+        """Inverse Cholesky factors and offsets as torch tensors (differentiable); the number of bad classes."""
+        cov, mu = self.covariances, self.means
+        L, info = torch.linalg.cholesky_ex(cov)
+        finite = torch.isfinite(cov).flatten(1).all(1)
+        if mu is not None:
+            finite = finite & torch.isfinite(mu).all(1)
+        bad = int(((info != 0) | ~finite).sum().item())
+        logdiag = torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
+        offset = -logdiag - 0.5 * self.n_features * math.log(2.0 * math.pi) + self.log_priors.to(cov.dtype)
+        # W_c = L_c^-1 once, as the native factor pass: the triangular solve then has K right-hand sides per class, not N
+        # (hipBLAS's batched trsm cannot allocate its workspace for tens of thousands of them)
+        eye = torch.eye(self.n_features, dtype=cov.dtype, device=cov.device).expand_as(L)
+        self._torch = (torch.linalg.solve_triangular(L, eye, upper=False), offset)
+        return bad
+
+    # ------------------------------------------------------------------ evaluation
+    def _samples(self, Z):
+        Z = torch.as_tensor(Z)
+        if Z.dim() != 2 or Z.shape[1] != self.n_features or Z.shape[0] < 1:
+            raise ValueError(f"samples must have shape (n_samples >= 1, {self.n_features}), got {tuple(Z.shape)}")
+        return Z.to(device=self.device, dtype=self.dtype)
+
+    def _use_native(self, Z):
+        return self._factors is not None and _native_applies(Z)
+
+    def _native_call(self, Z, scores=False, argmax=False, logsumexp=False):
+        """One sqfa_gauss_scores call: (scores (N,C) | None, argmax (N,) int64 | None, logsumexp (N,) | None, the count of
+        samples with a NaN in their row as a (1,) int32 device tensor)."""
+        lib = _lib.load()
+        Z = Z.detach().contiguous()
+        W, offset = self._factors
+        N, K, C = Z.shape[0], self.n_features, self.n_classes
+        code = _native._dtype_code(Z)
+        with _native._on_stream(Z.device) as stream:
+            ws, nbytes = _native._workspace(lib.sqfa_gauss_scores_workspace_bytes, N, C, K, code)
+            out_s = torch.empty((N, C), dtype=Z.dtype, device=Z.device) if scores else None
+            out_a = torch.empty(N, dtype=torch.int64, device=Z.device) if argmax else None
+            out_l = torch.empty(N, dtype=Z.dtype, device=Z.device) if logsumexp else None
+            bad = torch.empty(1, dtype=torch.int32, device=Z.device)
+            _lib.check(lib.sqfa_gauss_scores(_native._ptr(Z), N, _native._ptr(self._means_native), _native._ptr(W),
+                                             _native._ptr(offset), C, K, code, _native._ptr(out_s), _native._ptr(out_a),
+                                             None, _native._ptr(out_l), _native._ptr(bad), _native._ptr(ws), nbytes, stream),
+                       "sqfa_gauss_scores")
+        return out_s, out_a, out_l, bad
+
+    def _torch_scores(self, Z):
+        """The definition as a torch expression, a chunk of classes at a time."""
+        if self._torch is None:
+            self._torch_factors()
+        W, offset = self._torch
+        N, K, C = Z.shape[0], self.n_features, self.n_classes
+        per_class = 3 * N * K * Z.element_size()
+        step = max(1, min(C, FALLBACK_BYTES // max(1, per_class)))
+        out = []
+        for c0 in range(0, C, step):
+            Wc = W[c0:c0 + step]
+            if self.means is None:
+                y = Wc @ Z.T                                                             # (c, K, N)
+            else:
+                y = Wc @ (Z[None] - self.means[c0:c0 + step, None]).transpose(-1, -2)    # the whitened differences
+            out.append(-0.5 * (y * y).sum(1) + offset[c0:c0 + step, None])
+        return (out[0] if len(out) == 1 else torch.cat(out)).T
+
+    @staticmethod
+    def _refuse(count):
+        if count:
+            raise ValueError(f"{count} samples have non-finite scores (NaN features, or features at infinity)")
+
+    def _evaluate(self, Z, scores=False, argmax=False, logsumexp=False):
+        """(scores, argmax, logsumexp, count of NaN rows as a device tensor) on whichever path applies."""
+        Z = self._samples(Z)
+        if self._use_native(Z):
+            return self._native_call(Z, scores, argmax, logsumexp)
+        S = self._torch_scores(Z)
+        nan = torch.isnan(S).any(1)
+        return (S if scores else None, torch.where(nan, -1, S.argmax(1)) if argmax else None,
+                torch.logsumexp(S, 1) if logsumexp else None, nan.sum().reshape(1))
+
+    def scores(self, Z):
+        """(N, C) joint log densities log p(z_n, c)."""
+        S, _, _, bad = self._evaluate(Z, scores=True)
+        self._refuse(int(bad.item()))
+        return S
+
+    def predict(self, Z):
+        """(N,) int64: the class of the largest score, ties to the lowest index."""
+        _, A, _, bad = self._evaluate(Z, argmax=True)
+        self._refuse(int(bad.item()))
+        return A
+
+    def log_evidence(self, Z):
+        """(N,) log p(z_n) = logsumexp_c score[n, c]."""
+        _, _, E, bad = self._evaluate(Z, logsumexp=True)
+        self._refuse(int(bad.item()))
+        return E
+
+    def predict_log_proba(self, Z):
+        """(N, C) log posteriors: scores - log evidence."""
+        S, _, E, bad = self._evaluate(Z, scores=True, logsumexp=True)
+        self._refuse(int(bad.item()))
+        return S - E[:, None]
+
+    def predict_proba(self, Z):
+        return torch.exp(self.predict_log_proba(Z))
+
+    def accuracy(self, Z, y):
+        """The share of samples whose predicted class is y, a Python float (one read from the device)."""
+        _, A, _, bad = self._evaluate(Z, argmax=True)
+        y = torch.as_tensor(y).to(A.device).long()
+        if y.shape != A.shape:
+            raise ValueError(f"labels must have shape ({A.shape[0]},), got {tuple(y.shape)}")
+        correct, n_bad = torch.stack(((A == y).sum(), bad.reshape(()).to(torch.int64))).tolist()
+        self._refuse(n_bad)
+        return correct / A.shape[0]
+
+
+def gaussian_class_scores(Z, means, covariances, priors=None):
+    """(N, C) scores log p(z_n, c) of the samples Z (N, K) under the class Gaussians: means (C, K) or None (zero means),
+    covariances (C, K, K), priors None / "uniform" / (C,) non-negative weights.  Differentiable where an input asks for it
+    (the torch expression)."""
+    return GaussianClassifier(means, covariances, priors).scores(Z)
+
+
+class FeatureClassifier:
+    """A GaussianClassifier behind a snapshot of a model's filters: its methods take raw points X (N, D).  Built by
+    ``FeatureClassifier.from_model``; ``classifier`` is the GaussianClassifier in feature space, ``filters`` (K, D)."""
+
+    def __init__(self, filters, classifier):
+        self.filters = filters
+        self.classifier = classifier
+
+    @classmethod
+    def from_model(cls, model, X=None, y=None, data_statistics=None, priors="uniform", regularized=True,
+                   estimator="empirical"):
+        """The class Gaussians in the feature space of ``model`` (SQFA: means and covariances; SecondMomentsSQFA: zero
+        means and second moments), from ``X, y`` (class_statistics with ``estimator``) or ``data_statistics`` (what the
+        model's fit takes: a dict, a ClassPoints, or for SecondMomentsSQFA a (C,D,D) tensor).  ``regularized`` adds the
+        model's noise_mat, as the closures do.  priors: "uniform" (None), "empirical" (the class counts of ``y`` or of the
+        ClassPoints) or (C,) weights."""
+        counts = None
+        if data_statistics is None:
+            if X is None or y is None:
+                raise ValueError("Either data_statistics or X and y must be provided.")
+            data_statistics = class_statistics(X, y, estimator=estimator)
+        if y is not None:
+            counts = torch.bincount(torch.as_tensor(y).long().flatten())
+        elif isinstance(data_statistics, ClassPoints):
+            counts = data_statistics.counts
+        if isinstance(priors, str) and priors == "empirical":
+            if counts is None:
+                raise ValueError("priors='empirical' needs the labels y or a ClassPoints (its class counts)")
+            priors = counts
+        with torch.no_grad():
+            filters = model.filters.detach().clone()
+            if hasattr(model, "_feature_statistics"):   # SQFA: the class Gaussians themselves
+                stats = model._feature_statistics(data_statistics, regularized)
+                means, cov = stats["means"], stats["covariances"]
+            else:                                        # SecondMomentsSQFA: zero-mean Gaussians of the second moments
+                means, cov = None, model._feature_scatters(data_statistics, regularized)
+            if cov.dim() == 2:
+                cov = cov[None]
+            if torch.is_tensor(priors) and priors.shape[0] < cov.shape[0]:   # labels that stop short of the last class
+                priors = torch.nn.functional.pad(priors, (0, cov.shape[0] - priors.shape[0]))
+            classifier = GaussianClassifier(means.detach() if means is not None else None, cov.detach(), priors)
+        return cls(filters, classifier)
+
+    n_classes = property(lambda self: self.classifier.n_classes)
+    n_features = property(lambda self: self.classifier.n_features)
+    log_priors = property(lambda self: self.classifier.log_priors)
+
+    def transform(self, X):
+        """(N, D) points -> (N, K) features through the snapshot of the filters."""
+        X = torch.as_tensor(X).to(device=self.filters.device, dtype=self.filters.dtype)
+        return X @ self.filters.T
+
+    def scores(self, X):
+        return self.classifier.scores(self.transform(X))
+
+    def predict(self, X):
+        return self.classifier.predict(self.transform(X))
+
+    def log_evidence(self, X):
+        return self.classifier.log_evidence(self.transform(X))
+
+    def predict_log_proba(self, X):
+        return self.classifier.predict_log_proba(self.transform(X))
+
+    def predict_proba(self, X):
+        return self.classifier.predict_proba(self.transform(X))
+
+    def accuracy(self, X, y):
+        return self.classifier.accuracy(self.transform(X), y)

@@ -1,0 +1,523 @@
+// gauss_scores_kernel.hip -- Gaussian class scores (quadratic discriminant analysis in feature space):
+//     score[n][c] = -1/2 |L_c^-1 (z_n - mu_c)|^2 - sum_k log (L_c)_kk - K/2 log 2 pi + log pi_c  =  log p(z_n, c)
+// for features z_n (K), class means mu_c, class covariances Sigma_c = L_c L_c^T and priors pi_c, with the argmax over the
+// classes and the log evidence logsumexp_c score[n][c].  The whitened-difference form: the expanded quadratic
+// z^T P z - 2 b^T z + const cancels in float32.
+//
+// Launches (caller's stream; nothing allocated, synchronised or read back; no float atomics, every sum in a fixed order:
+// bitwise reproducible; every grid a function of (N, C, K) alone):
+//   gauss_factor_kernel   once per classifier, one 64-thread workgroup per class (the pattern of stein_class_kernel):
+//                         Cholesky in double in LDS, W_c = L_c^-1 in place, written lower triangular with exact zeros above
+//                         the diagonal; offset_c = -sum log diag L_c - K/2 log 2 pi + log pi_c in double; a class with a
+//                         pivot that is not positive and finite, a mean that is not finite or a log prior that is NaN or
+//                         +inf gets NaN and is counted (integer atomic).
+//   gauss_scores_kernel   workgroup (64 samples, split s of the classes), 4 waves of 16 samples.  A lane (j = l & 15,
+//                         q = l >> 4) keeps z[j][4 s + q] of its sample in registers for the whole kernel.  Classes come in
+//                         groups of 4.  W_c is staged through LDS as [row][k], pitch 16 KB + 2 (rows on the lanes: banks
+//                         all distinct, see class_points_kernel.hip), the next stage's global loads in flight during the
+//                         MFMAs: 4 classes per stage up to K = 32, one class per stage above (34 KB of LDS at most).  Per
+//                         class y = W_c (z - mu_c) on the exact MFMA: A[i][k] = W_c[i][k], B[k][j] = (z_j - mu_c)[k], the
+//                         16 x 16 blocks of W_c above the diagonal skipped; a lane squares and sums its 4 rows of every row
+//                         block.  The 4 classes' partial sums are then reduced ACROSS the 4 lane quarters and transposed in
+//                         3 cross-lane moves, so that lane (j, q) holds the full sum of class 4 g + q: one score, one
+//                         compare and one exp per lane and group.  Every lane carries (max, index) and (max, sum exp) of
+//                         its classes; the quarters are merged by a butterfly at the end (both partners compute the same
+//                         bits: max and a + b commute).
+//   gauss_merge_kernel    only where the classes are split (few sample tiles): merges the splits' partial (max, index),
+//                         (max, sum exp) in the order s = 0, 1, ...
+// Sample tails, class tails and K not a multiple of 4 or 16 are exact zeros in registers / LDS (a padded class scores
+// -inf by select); no address past a tensor's end is formed.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <type_traits>
+
+#include "../../include/sqfa_hip.h"
+#include "proj_traits.hpp"
+
+namespace sqfa {
+
+// sqfa_api.hip: the text sqfa_hip_last_error() returns
+void set_last_error(const char* text);
+
+constexpr int GS_THREADS = 256;
+constexpr int GS_ROWS = 64;         // samples per workgroup
+constexpr int GS_KMAX = 64;
+constexpr int GS_MAX_SPLIT = 16;    // class splits at most
+constexpr int GS_TARGET_WG = 1024;  // workgroups asked for (four per CU) before the classes stop being split
+
+__device__ __forceinline__ float gs_exp(float x) { return expf(x); }
+__device__ __forceinline__ double gs_exp(double x) { return exp(x); }
+__device__ __forceinline__ float gs_log(float x) { return logf(x); }
+__device__ __forceinline__ double gs_log(double x) { return log(x); }
+template <typename T> __device__ __forceinline__ T gs_nan();
+template <> __device__ __forceinline__ float gs_nan<float>() { return __builtin_nanf(""); }
+template <> __device__ __forceinline__ double gs_nan<double>() { return __builtin_nan(""); }
+template <typename T> __device__ __forceinline__ T gs_ninf() { return -(T)INFINITY; }
+
+// ---- the factor pass --------------------------------------------------------------------------------------------------------
+
+template <typename T>
+__global__ __launch_bounds__(64) void gauss_factor_kernel(const T* __restrict__ mu, const T* __restrict__ cov,
+                                                          const double* __restrict__ log_prior, int C, int K,
+                                                          T* __restrict__ W, double* __restrict__ offset,
+                                                          int* __restrict__ bad_out) {
+  constexpr int LD = 65;
+  __shared__ double a[64 * LD];
+  __shared__ int s_bad;
+  const int r = threadIdx.x, kk = K * K, c = blockIdx.x;
+  const T* S = cov + (size_t)c * kk;
+  T* out = W + (size_t)c * kk;
+  if (r == 0) s_bad = 0;
+  for (int idx = r; idx < kk; idx += 64) {
+    const int rr = idx / K, cc = idx % K;
+    if (cc <= rr) a[rr * LD + cc] = (double)S[idx];
+  }
+  __syncthreads();
+  if (mu != nullptr && r < K) {
+    const double v = (double)mu[(size_t)c * K + r];
+    if (!(fabs(v) < (double)INFINITY)) s_bad = 1;   // every writer writes 1
+  }
+  __syncthreads();
+  const double lp = log_prior != nullptr ? log_prior[c] : -log((double)C);
+  bool bad = s_bad != 0 || !(lp < (double)INFINITY);   // NaN or +inf; -inf is a class that never wins
+  // Cholesky, right-looking: after step k column k holds L[:, k]
+  double logdiag = 0.0;
+  for (int k = 0; k < K && !bad; ++k) {
+    const double d = a[k * LD + k];   // the same value in every thread: the exit is uniform
+    if (!(d > 0.0 && d < (double)INFINITY)) {
+      bad = true;
+      break;
+    }
+    logdiag += 0.5 * log(d);
+    const double root = sqrt(d), inv = 1.0 / root;
+    __syncthreads();
+    if (r == k) a[k * LD + k] = root;
+    if (r > k && r < K) a[r * LD + k] *= inv;
+    __syncthreads();
+    if (r > k && r < K) {
+      const double lrk = a[r * LD + k];
+      for (int cc = k + 1; cc <= r; ++cc) a[r * LD + cc] -= lrk * a[cc * LD + k];
+    }
+    __syncthreads();
+  }
+  if (bad) {
+    for (int idx = r; idx < kk; idx += 64) out[idx] = gs_nan<T>();
+    if (r == 0) {
+      offset[c] = gs_nan<double>();
+      atomicAdd(bad_out, 1);
+    }
+    return;
+  }
+  if (r == 0) offset[c] = -logdiag - 0.5 * K * 1.8378770664093454835606594728112 + lp;   // log 2 pi
+  // X = L^-1 in place, last column first: X[r][j] L[j][j] = -sum_{k=j+1..r} X[r][k] L[k][j]
+  for (int j = K - 1; j >= 0; --j) {
+    const double xjj = 1.0 / a[j * LD + j];
+    double sum = 0.0;
+    if (r > j && r < K)
+      for (int k = j + 1; k <= r; ++k) sum += a[r * LD + k] * a[k * LD + j];
+    __syncthreads();
+    if (r == j) a[j * LD + j] = xjj;
+    if (r > j && r < K) a[r * LD + j] = -sum * xjj;
+    __syncthreads();
+  }
+  for (int idx = r; idx < kk; idx += 64) {
+    const int rr = idx / K, cc = idx % K;
+    out[idx] = cc <= rr ? (T)a[rr * LD + cc] : (T)0;
+  }
+}
+
+// ---- the scores ---------------------------------------------------------------------------------------------------------------
+
+template <typename T> struct GsParams {
+  const T* Z;
+  long long N;
+  const T* mu;
+  const T* W;
+  const double* offset;
+  int C, K;
+  T* scores;
+  long long* argmax;
+  T* best;
+  T* lse;
+  int* nonfinite;
+  int groups_per_split, splits;   // groups of 4 classes
+  // (splits, N) each, splits > 1 only; p_idx -1: the sample's row holds a NaN
+  T* p_best;
+  int* p_idx;
+  T* p_m;
+  T* p_sum;
+};
+
+// the running reductions of one sample over a set of classes
+template <typename T> struct GsRun {
+  T best;    // max score, -inf before the first
+  int idx;   // its class, INT_MAX before the first
+  T m, sum;  // logsumexp = m + log(sum); (-inf, 0) before the first finite score
+  bool nan;
+};
+
+template <typename T> __device__ __forceinline__ void gs_take(GsRun<T>& a, T s, int c) {
+  if (s != s) a.nan = true;
+  if (s > a.best || (s == a.best && c < a.idx)) {
+    a.best = s;
+    a.idx = c;
+  }
+  const T d = s - a.m;
+  const T e = gs_exp(d > T(0) ? -d : d);   // exp(-|d|); d is NaN only for -inf - -inf, which neither branch below takes
+  if (s > a.m) {
+    a.sum = a.sum * e + T(1);
+    a.m = s;
+  } else if (s > gs_ninf<T>()) {
+    a.sum += e;
+  }
+}
+
+// symmetric in its arguments bit for bit: both partners of a butterfly step compute the same values
+template <typename T> __device__ __forceinline__ void gs_merge(GsRun<T>& a, T best, int idx, T m, T sum, bool nan) {
+  if (best > a.best || (best == a.best && idx < a.idx)) {
+    a.best = best;
+    a.idx = idx;
+  }
+  const T mx = m > a.m ? m : a.m;
+  if (mx > gs_ninf<T>()) {
+    const T lo = (m > a.m ? a.sum : sum) * gs_exp((m > a.m ? a.m : m) - mx);   // the side with the smaller max, scaled
+    const T hi = m > a.m ? sum : a.sum;
+    a.sum = m == a.m ? a.sum + sum : hi + lo;
+  }
+  a.m = mx;
+  a.nan = a.nan || nan;
+}
+
+template <typename T> __device__ __forceinline__ T gs_shfl_xor(T v, int mask) { return __shfl_xor(v, mask, 64); }
+
+template <typename T, int KB, bool MEANS>
+__global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams<T> p) {
+  using Tr = ProjTraits<T>;
+  constexpr int CS = KB <= 2 ? 4 : 1;       // classes per stage
+  constexpr int KP = KB * 16;               // padded K
+  constexpr int PITCH = KP + 2;
+  constexpr int PER = CS * KB * KB;         // W values per thread and stage: CS K K <= CS KP KP = 256 PER
+  __shared__ T sW[CS * KP * PITCH];
+  __shared__ T sMu[CS * KP];
+  const int tid = threadIdx.x, l = tid & 63, wave = tid >> 6, q = l >> 4, j = l & 15;
+  const int K = p.K, C = p.C, K4 = (K + 3) / 4, kk = K * K;
+  const long long N = p.N;
+  const long long n = (long long)blockIdx.x * GS_ROWS + wave * 16 + j;
+  const int n_groups = (C + 3) / 4;
+  const int g_lo = blockIdx.y * p.groups_per_split;
+  const int g_hi = g_lo + p.groups_per_split < n_groups ? g_lo + p.groups_per_split : n_groups;
+  const int c_end = 4 * g_hi < C ? 4 * g_hi : C;   // the classes of this split: 4 g_lo .. c_end - 1
+  const size_t w_end = (size_t)c_end * kk;
+
+  // this lane's sample: z[s] = Z[n][4 s + q], zeros past K and past N
+  T z[4 * KB];
+#pragma unroll
+  for (int s = 0; s < 4 * KB; ++s) {
+    const int k = 4 * s + q;
+    const bool ok = n < N && k < K;
+    const T v = p.Z[ok ? (size_t)n * K + k : 0];
+    z[s] = ok ? v : T(0);
+  }
+
+  // a stage: the CS classes from cb on.  W through registers into LDS as [class][row][k]; rows and columns K.. stay zero
+  T wv[PER], mv = T(0);
+  auto load = [&](int cb) {
+    const size_t base = (size_t)cb * kk;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      const int idx = tid + e * GS_THREADS;
+      const bool ok = idx < CS * kk && base + idx < w_end;
+      const T v = p.W[ok ? base + idx : 0];
+      wv[e] = ok ? v : T(0);
+    }
+    if constexpr (MEANS) {
+      const int cls = tid / KP, k = tid % KP;
+      const bool ok = tid < CS * KP && cb + cls < c_end && k < K;
+      const T v = p.mu[ok ? (size_t)(cb + cls) * K + k : 0];
+      mv = ok ? v : T(0);
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      const int idx = tid + e * GS_THREADS;
+      if (idx < CS * kk) {
+        const int cls = idx / kk, rem = idx % kk;
+        sW[cls * KP * PITCH + (rem / K) * PITCH + rem % K] = wv[e];
+      }
+    }
+    if constexpr (MEANS) {
+      if (tid < CS * KP) sMu[tid] = mv;
+    }
+  };
+
+  for (int i = tid; i < CS * KP * PITCH; i += GS_THREADS) sW[i] = T(0);
+  if (g_lo < g_hi) load(4 * g_lo);
+
+  GsRun<T> run;
+  run.best = gs_ninf<T>();
+  run.idx = INT_MAX;
+  run.m = gs_ninf<T>();
+  run.sum = T(0);
+  run.nan = false;
+
+#pragma unroll 1
+  for (int g = g_lo; g < g_hi; ++g) {
+    const int c_mine = 4 * g + q;   // the class whose score this lane ends up with
+    const T off = c_mine < C ? (T)p.offset[c_mine] : gs_ninf<T>();
+    if constexpr (CS == 4) {
+      __syncthreads();   // the previous stage has been consumed (first pass: the zero fill is done)
+      store();
+      __syncthreads();
+      if (g + 1 < g_hi) load(4 * (g + 1));
+    }
+    T part[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      part[t] = T(0);
+      if constexpr (CS == 1) {
+        if (4 * g + t >= c_end) continue;   // uniform over the workgroup: a class past the end has no stage
+        __syncthreads();
+        store();
+        __syncthreads();
+        if (4 * g + t + 1 < c_end) load(4 * g + t + 1);
+      }
+      const T* w = sW + (CS == 4 ? t : 0) * KP * PITCH;
+      const T* m = sMu + (CS == 4 ? t : 0) * KP;
+      T b[4 * KB];
+#pragma unroll
+      for (int s = 0; s < 4 * KB; ++s) {
+        if constexpr (MEANS) b[s] = s < K4 ? z[s] - m[4 * s + q] : T(0);
+        else b[s] = z[s];
+      }
+      T sq = T(0);
+#pragma unroll
+      for (int rb = 0; rb < KB; ++rb) {
+        if (rb * 16 < K) {
+          typename Tr::Acc acc = {};
+#pragma unroll
+          for (int s = 0; s < 4 * (rb + 1); ++s)   // the blocks above the diagonal of W are zero: skipped
+            if (s < K4) acc = Tr::mfma(w[(rb * 16 + j) * PITCH + 4 * s + q], b[s], acc);
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) sq += acc[reg] * acc[reg];
+        }
+      }
+      part[t] = sq;
+    }
+    // reduce over the 4 lane quarters and transpose: lane (j, q) ends with the sum of class 4 g + q
+    const bool hi = (q & 2) != 0, odd = (q & 1) != 0;
+    const T r0 = gs_shfl_xor(hi ? part[0] : part[2], 32), r1 = gs_shfl_xor(hi ? part[1] : part[3], 32);
+    const T a0 = (hi ? part[2] : part[0]) + r0, a1 = (hi ? part[3] : part[1]) + r1;
+    const T tot = (odd ? a1 : a0) + gs_shfl_xor(odd ? a0 : a1, 16);
+    const T sc = c_mine < C ? T(-0.5) * tot + off : gs_ninf<T>();
+    if (c_mine < C) {
+      if (p.scores != nullptr && n < N) p.scores[(size_t)n * C + c_mine] = sc;
+      gs_take(run, sc, c_mine);
+    }
+  }
+
+  // merge the quarters: a butterfly, the same bits in both partners
+#pragma unroll
+  for (int mask = 16; mask <= 32; mask *= 2) {
+    const T ob = gs_shfl_xor(run.best, mask), om = gs_shfl_xor(run.m, mask), os = gs_shfl_xor(run.sum, mask);
+    const int oi = __shfl_xor(run.idx, mask, 64), on = __shfl_xor(run.nan ? 1 : 0, mask, 64);
+    gs_merge(run, ob, oi, om, os, on != 0);
+  }
+  const bool writer = q == 0 && n < N;
+  if (p.splits > 1) {
+    if (writer) {
+      const size_t at = (size_t)blockIdx.y * N + n;
+      p.p_best[at] = run.best;
+      p.p_idx[at] = run.nan ? -1 : run.idx;
+      p.p_m[at] = run.m;
+      p.p_sum[at] = run.sum;
+    }
+    return;
+  }
+  if (writer) {
+    if (p.argmax != nullptr) p.argmax[n] = run.nan ? -1 : run.idx;
+    if (p.best != nullptr) p.best[n] = run.nan ? gs_nan<T>() : run.best;
+    if (p.lse != nullptr) p.lse[n] = run.nan ? gs_nan<T>() : run.m + gs_log(run.sum);
+  }
+  const unsigned long long bal = __ballot(writer && run.nan);
+  if (l == 0 && bal != 0) atomicAdd(p.nonfinite, __popcll(bal));
+}
+
+// one thread per sample: the splits' partial reductions in the order s = 0, 1, ...
+template <typename T>
+__global__ __launch_bounds__(GS_THREADS) void gauss_merge_kernel(const GsParams<T> p) {
+  const long long n = (long long)blockIdx.x * GS_THREADS + threadIdx.x;
+  bool nan = false;
+  if (n < p.N) {
+    GsRun<T> run;
+    run.best = p.p_best[n];
+    run.idx = p.p_idx[n];
+    run.m = p.p_m[n];
+    run.sum = p.p_sum[n];
+    run.nan = run.idx < 0;
+    for (int s = 1; s < p.splits; ++s) {
+      const size_t at = (size_t)s * p.N + n;
+      const int idx = p.p_idx[at];
+      gs_merge(run, p.p_best[at], idx < 0 ? INT_MAX : idx, p.p_m[at], p.p_sum[at], idx < 0);
+    }
+    nan = run.nan;
+    if (p.argmax != nullptr) p.argmax[n] = nan ? -1 : run.idx;
+    if (p.best != nullptr) p.best[n] = nan ? gs_nan<T>() : run.best;
+    if (p.lse != nullptr) p.lse[n] = nan ? gs_nan<T>() : run.m + gs_log(run.sum);
+  }
+  const unsigned long long bal = __ballot(nan);
+  if ((threadIdx.x & 63) == 0 && bal != 0) atomicAdd(p.nonfinite, __popcll(bal));
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+
+struct GsLayout {
+  int groups_per_split, splits;
+  size_t total;   // splits > 1: four (splits, N) arrays [best T][m T][sum T][idx int]
+};
+
+static bool gs_layout(long long N, int C, int K, int dtype, GsLayout* w) {
+  if (N < 1 || C < 1 || K < 1 || K > GS_KMAX || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
+  const long long tiles = (N + GS_ROWS - 1) / GS_ROWS;
+  if (tiles > (long long)INT_MAX) return false;
+  if (C > INT_MAX - 3) return false;
+  const int groups = (C + 3) / 4;
+  long long splits = (GS_TARGET_WG + tiles - 1) / tiles;
+  if (splits > GS_MAX_SPLIT) splits = GS_MAX_SPLIT;
+  if (splits > groups) splits = groups;
+  if (splits < 1) splits = 1;
+  const int per = (int)((groups + splits - 1) / splits);
+  w->groups_per_split = per;
+  w->splits = (groups + per - 1) / per;   // no empty split
+  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
+  w->total = w->splits > 1 ? (size_t)w->splits * (size_t)N * (3 * esz + sizeof(int)) : 0;
+  return true;
+}
+
+template <typename T, int KB>
+static void launch_scores(const GsParams<T>& p, dim3 grid, hipStream_t stream) {
+  if (p.mu != nullptr) hipLaunchKernelGGL((gauss_scores_kernel<T, KB, true>), grid, dim3(GS_THREADS), 0, stream, p);
+  else hipLaunchKernelGGL((gauss_scores_kernel<T, KB, false>), grid, dim3(GS_THREADS), 0, stream, p);
+}
+
+template <typename T>
+static hipError_t run_scores(const void* Z, long long N, const void* mu, const void* W, const double* offset, int C, int K,
+                             void* scores, long long* argmax, void* best, void* lse, int* nonfinite, char* ws,
+                             const GsLayout& lay, hipStream_t stream) {
+  GsParams<T> p{};
+  p.Z = static_cast<const T*>(Z);
+  p.N = N;
+  p.mu = static_cast<const T*>(mu);
+  p.W = static_cast<const T*>(W);
+  p.offset = offset;
+  p.C = C;
+  p.K = K;
+  p.scores = static_cast<T*>(scores);
+  p.argmax = argmax;
+  p.best = static_cast<T*>(best);
+  p.lse = static_cast<T*>(lse);
+  p.nonfinite = nonfinite;
+  p.groups_per_split = lay.groups_per_split;
+  p.splits = lay.splits;
+  if (lay.splits > 1) {
+    const size_t cells = (size_t)lay.splits * (size_t)N;
+    p.p_best = reinterpret_cast<T*>(ws);
+    p.p_m = p.p_best + cells;
+    p.p_sum = p.p_m + cells;
+    p.p_idx = reinterpret_cast<int*>(p.p_sum + cells);
+  }
+  hipError_t e = hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)((N + GS_ROWS - 1) / GS_ROWS), (unsigned)lay.splits);
+  const int KB = (K + 15) / 16;
+  if (KB == 1) launch_scores<T, 1>(p, grid, stream);
+  else if (KB == 2) launch_scores<T, 2>(p, grid, stream);
+  else if (KB == 3) launch_scores<T, 3>(p, grid, stream);
+  else launch_scores<T, 4>(p, grid, stream);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (lay.splits > 1) {
+    hipLaunchKernelGGL((gauss_merge_kernel<T>), dim3((unsigned)((N + GS_THREADS - 1) / GS_THREADS)), dim3(GS_THREADS), 0,
+                       stream, p);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+}  // namespace sqfa
+
+using namespace sqfa;
+
+extern "C" size_t sqfa_gauss_scores_workspace_bytes(long long N, int C, int K, int dtype) {
+  GsLayout w;
+  if (!gs_layout(N, C, K, dtype, &w)) return 0;
+  return w.total < 16 ? 16 : w.total;
+}
+
+extern "C" int sqfa_gauss_class_factors(const void* means, const void* cov, const double* log_priors, int C, int K, int dtype,
+                                        void* W_out, double* offset_out, int* bad_out, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  set_last_error("");
+  if (cov == nullptr || W_out == nullptr || offset_out == nullptr || bad_out == nullptr || C < 1 || K < 1) {
+    set_last_error("sqfa_gauss_class_factors: null covariances or outputs, C < 1 or K < 1");
+    return SQFA_ERR_BAD_ARGUMENT;
+  }
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
+    set_last_error("sqfa_gauss_class_factors: dtype");
+    return SQFA_ERR_BAD_ARGUMENT;
+  }
+  if (K > GS_KMAX) {
+    set_last_error("sqfa_gauss_class_factors: K > 64");
+    return SQFA_ERR_UNSUPPORTED_M;
+  }
+  if (hipMemsetAsync(bad_out, 0, sizeof(int), stream) != hipSuccess) return SQFA_ERR_LAUNCH;
+  if (dtype == SQFA_F32)
+    hipLaunchKernelGGL((gauss_factor_kernel<float>), dim3(C), dim3(64), 0, stream, static_cast<const float*>(means),
+                       static_cast<const float*>(cov), log_priors, C, K, static_cast<float*>(W_out), offset_out, bad_out);
+  else
+    hipLaunchKernelGGL((gauss_factor_kernel<double>), dim3(C), dim3(64), 0, stream, static_cast<const double*>(means),
+                       static_cast<const double*>(cov), log_priors, C, K, static_cast<double*>(W_out), offset_out, bad_out);
+  return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}
+
+extern "C" int sqfa_gauss_scores(const void* Z, long long N, const void* means, const void* W, const double* offset, int C,
+                                 int K, int dtype, void* scores_out, long long* argmax_out, void* best_out,
+                                 void* logsumexp_out, int* nonfinite_out, void* workspace, size_t workspace_bytes,
+                                 void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  set_last_error("");
+  if (Z == nullptr || W == nullptr || offset == nullptr || nonfinite_out == nullptr || N < 1 || C < 1 || K < 1) {
+    set_last_error("sqfa_gauss_scores: null samples, factors, offsets or counter, N < 1, C < 1 or K < 1");
+    return SQFA_ERR_BAD_ARGUMENT;
+  }
+  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
+    set_last_error("sqfa_gauss_scores: dtype");
+    return SQFA_ERR_BAD_ARGUMENT;
+  }
+  if (best_out != nullptr && argmax_out == nullptr) {
+    set_last_error("sqfa_gauss_scores: best_out without argmax_out");
+    return SQFA_ERR_BAD_ARGUMENT;
+  }
+  if (K > GS_KMAX) {
+    set_last_error("sqfa_gauss_scores: K > 64");
+    return SQFA_ERR_UNSUPPORTED_M;
+  }
+  GsLayout lay;
+  if (!gs_layout(N, C, K, dtype, &lay)) {
+    set_last_error("sqfa_gauss_scores: more than 2^31 - 1 sample tiles or classes");
+    return SQFA_ERR_UNSUPPORTED_M;
+  }
+  if (workspace == nullptr || workspace_bytes < (lay.total < 16 ? 16 : lay.total)) {
+    set_last_error("sqfa_gauss_scores: workspace is null or smaller than sqfa_gauss_scores_workspace_bytes");
+    return SQFA_ERR_WORKSPACE;
+  }
+  const hipError_t e =
+      dtype == SQFA_F32
+          ? run_scores<float>(Z, N, means, W, offset, C, K, scores_out, argmax_out, best_out, logsumexp_out, nonfinite_out,
+                              static_cast<char*>(workspace), lay, stream)
+          : run_scores<double>(Z, N, means, W, offset, C, K, scores_out, argmax_out, best_out, logsumexp_out, nonfinite_out,
+                               static_cast<char*>(workspace), lay, stream);
+  return e == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
+}

@@ -89,7 +89,9 @@ __device__ __forceinline__ float g_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double g_sqrt(double x) { return sqrt(x); }
 
 // D and its partial derivatives from the pair terms: dQ = dD/dQ in total (through Bh too), dBh = dD/dBh (dD/dLD = dBh / 2,
-// dD/dld_c = -dBh / 4).  On the diagonal the log-determinant term is exactly zero, as in the reference.
+// dD/dld_c = -dBh / 4).  On the diagonal the log-determinant term is exactly zero, as in the reference.  The term is >= 0
+// mathematically and the difference of three rounded logarithms: where that comes out negative (near-equal classes) it is
+// taken as 0 with derivative 0, so dBh is 0 there while dQ is not (NaN stays NaN: the comparison is false for it).
 template <typename T>
 __device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi, T ldj, bool diagonal, T& D, T& dQ, T& dBh) {
   if (kind == SQFA_GAUSS_MAHALANOBIS_SQ) {
@@ -97,7 +99,9 @@ __device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi
   } else if (kind == SQFA_GAUSS_MAHALANOBIS) {
     D = g_sqrt(q + eps); dQ = T(0.5) / D; dBh = T(0);
   } else {
-    const T bh = diagonal ? q * T(0.125) : q * T(0.125) + T(0.5) * (ld - T(0.5) * (ldi + ldj));
+    const T det = diagonal ? T(0) : T(0.5) * (ld - T(0.5) * (ldi + ldj));
+    const bool clamped = det < T(0);
+    const T bh = q * T(0.125) + (clamped ? T(0) : det);
     if (kind == SQFA_GAUSS_BHATTACHARYYA) {
       D = bh; dBh = T(1);
     } else {
@@ -106,6 +110,7 @@ __device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi
       dBh = T(0.5) * e / D;
     }
     dQ = T(0.125) * dBh;
+    if (clamped) dBh = T(0);
   }
 }
 

@@ -2,7 +2,7 @@
 // the n class Gaussians N(mu_c, Sigma_c), as the distance_fun of SQFA (with means) and SecondMomentsSQFA (mu == NULL):
 // with the precisions P_c = Sigma_c^-1 and delta = mu_i - mu_j
 //     J_ij = KL(i||j) + KL(j||i) = -1/2 <P_i - P_j, Sigma_i - Sigma_j> + 1/2 delta^T (P_i + P_j) delta
-//     D_ij = J_ij  |  sqrt(J_ij + eps),   loss = sum_{i>j} w_ij D_ij
+//     D_ij = J_ij  |  sqrt(J_ij + eps),  J_ij clamped at 0 from below,   loss = sum_{i>j} w_ij D_ij
 // and its gradient wrt mu and Sigma.  The explicit-difference form is the one computed: the textbook form
 // 1/2 [tr(P_j Sigma_i) + tr(P_i Sigma_j) - 2m] cancels the digits that matter for close classes (the same rule
 // log_euclidean_kernel.hip follows).  A pair costs O(m^2): no per-pair factorisation.
@@ -295,15 +295,18 @@ __global__ __launch_bounds__(256) void jeffreys_pair_kernel(const JeffParams p) 
         }
       }
       if constexpr (MEANS) part += dr * y;
-      const T J = T(0.5) * group_sum<G>(part);   // every lane of the group gets the total
+      const T Jr = T(0.5) * group_sum<G>(part);   // every lane of the group gets the total
+      // J >= 0 mathematically: a rounded negative one (near-equal classes) is taken as 0 with derivative 0; NaN stays NaN
+      const bool clamped = Jr < T(0);
+      const T J = clamped ? T(0) : Jr;
       if (ivalid && jvalid && j != i) {
         T D, cij;
         if (sqrt_mode) {
           D = jf_sqrt(J + eps);
-          cij = T(0.5) * wij / D;
+          cij = clamped ? T(0) : T(0.5) * wij / D;
         } else {
           D = J;
-          cij = wij;
+          cij = clamped ? T(0) : wij;
         }
         if (want_grad) {
           const T h = T(0.5) * cij;

@@ -1,13 +1,15 @@
 // stein_kernel.hip -- fused closure loss of the Stein divergence (Jensen-Bregman log-det divergence, S-divergence) between
 // the n SPD matrices S_c, as the distance_fun of SecondMomentsSQFA:
 //     S_ij = logdet((S_i + S_j)/2) - 1/2 logdet S_i - 1/2 logdet S_j
-//     D_ij = S_ij  |  sqrt(|S_ij| + eps),   loss = sum_{i>j} w_ij D_ij
+//     D_ij = S_ij  |  sqrt(S_ij + eps),  S_ij clamped at 0 from below,   loss = sum_{i>j} w_ij D_ij
 // and its gradient  gradS_i = sum_{j != i} c_ij 1/2 (Sbar_ij^-1 - S_i^-1),  c_ij = w_ij dD/dS.  Cholesky factors only: no
 // eigen-decomposition, no means.
 //
 // Three stages on the caller's stream:
 //   1. stein_class_kernel: per class, Cholesky in double: ld_c = logdet S_c (double) and P_c = S_c^-1 in the dtype, exactly
 //      symmetric (the pattern of jeffreys_precision_kernel).  A pivot that is not positive gives ld_c = NaN and a NaN matrix.
+//   1b. stein_logdet_kernel: ld_c once more, from the pair pass's own factorisation in the dtype (it replaces stage 1's
+//      value: both sides of S_ij then carry the same rounding).
 //   2. stein_pair_kernel: the pass over the ordered pairs.  A 256-thread workgroup owns ONE class i; its NS = 256 / G lane
 //      groups of G lanes (a group never leaves its wave) take the classes j = s, s + NS, ...: NS pairs in flight per
 //      workgroup.  Lane r of a group holds row r of Sbar = (S_i + S_j)/2 in registers (MMAX values; rows and columns beyond
@@ -47,8 +49,6 @@ __device__ __forceinline__ float st_rsqrt(float x) { return 1.0f / sqrtf(x); }
 __device__ __forceinline__ double st_rsqrt(double x) { return 1.0 / sqrt(x); }
 __device__ __forceinline__ float st_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double st_sqrt(double x) { return sqrt(x); }
-__device__ __forceinline__ float st_abs(float x) { return fabsf(x); }
-__device__ __forceinline__ double st_abs(double x) { return fabs(x); }
 template <typename T> __device__ __forceinline__ T st_nan();
 template <> __device__ __forceinline__ float st_nan<float>() { return __builtin_nanf(""); }
 template <> __device__ __forceinline__ double st_nan<double>() { return __builtin_nan(""); }
@@ -227,17 +227,19 @@ __global__ __launch_bounds__(256) void stein_pair_kernel(const SteinParams p) {
     __builtin_amdgcn_sched_barrier(0);
     const double ldbar = group_sum<G>(log((double)pivot));
     const double Sd = ldbar - 0.5 * (ld_i + p.ld[j]);
-    const T Sv = (T)Sd;
+    // S >= 0 mathematically; the difference of three rounded logarithms comes out negative for near-equal classes: taken as
+    // 0 there, with derivative 0 (NaN stays NaN: the comparison is false for it)
+    const bool clamped = Sd < 0.0;
+    const T Sv = clamped ? T(0) : (T)Sd;
     T wij = w;
     if constexpr (WEIGHTED) wij = W[(size_t)i * n + j];
     T D, cij;
     if (sqrt_mode) {
-      D = st_sqrt(st_abs(Sv) + eps);
-      const T sign = Sv > T(0) ? T(1) : (Sv < T(0) ? T(-1) : Sv);   // 0 at 0 and NaN for NaN, as autograd's sign
-      cij = T(0.5) * wij * sign / D;
+      D = st_sqrt(Sv + eps);
+      cij = clamped ? T(0) : T(0.5) * wij / D;
     } else {
       D = Sv;
-      cij = wij;
+      cij = clamped ? T(0) : wij;
     }
     if (want_grad) {   // uniform over the workgroup
       // backward solve U x = y, last row first: x becomes row `lane` of Sbar^-1
@@ -325,6 +327,56 @@ __global__ __launch_bounds__(256) void stein_pair_kernel(const SteinParams p) {
   }
 }
 
+// ---- stage 1b: ld_c again, by the pair pass's own arithmetic ----------------------------------------------------------------
+// The pair pass takes logdet Sbar from its Cholesky in the dtype; ld_c from stage 1's double Cholesky differs from that by
+// the rounding of the dtype's factorisation (float32: eps cond), which does not cancel in S_ij and exceeds S_ij for
+// near-equal classes.  Here one lane group factors S_c = (S_c + S_c)/2 with the statements of the pair pass, so that both
+// sides of the difference carry the same rounding and two bitwise equal classes are exactly 0 apart (the Gaussian pair
+// kernel's pre-pass does the same for Bhattacharyya).  A pivot that is not positive gives NaN or -inf here too.
+template <typename T, int G, int MMAX>
+__global__ __launch_bounds__(256) void stein_logdet_kernel(const SteinParams p, double* __restrict__ ld_out) {
+  constexpr int NS = 256 / G;
+  const int tid = threadIdx.x, n = p.n, m = p.m, mm = m * m;
+  const int lane = tid % G, s = tid / G;
+  const bool rvalid = lane < m;
+  const int lanec = rvalid ? lane : 0;
+  const int cr = blockIdx.x * NS + s;
+  const int cls = cr < n ? cr : n - 1;   // clamped: every group makes the same steps
+  const T* Sc = static_cast<const T*>(p.S) + (size_t)cls * mm + lanec;
+  T a[MMAX];
+#pragma unroll
+  for (int c = 0; c < MMAX; ++c) {
+    const bool ok = rvalid && c < m;
+    const T sj = Sc[ok ? c * m : 0];
+    a[c] = ok ? T(0.5) * (sj + sj) : (c == lane ? T(1) : T(0));
+    if (c % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+  }
+  T pivot = T(1);
+#pragma unroll
+  for (int k = 0; k < MMAX; ++k) {
+    __builtin_amdgcn_sched_barrier(0);
+    const T dk = st_bcast<G>(a[k], k);
+    const T rinv = st_rsqrt(dk);
+    if (lane == k) pivot = dk;
+    const T lrk = lane > k ? a[k] * rinv : T(0);
+#pragma unroll
+    for (int c = k + 1; c < MMAX; ++c) {
+      const T ukc = st_bcast<G>(a[c], k) * rinv;
+      a[c] -= lrk * ukc;
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const double ld = group_sum<G>(log((double)pivot));
+  if (cr < n && lane == 0) ld_out[cr] = ld;
+}
+
+template <typename T, int G, int MMAX>
+static hipError_t launch_stein_logdet(const SteinParams& p, double* ld_out, hipStream_t stream) {
+  constexpr int NS = 256 / G;
+  hipLaunchKernelGGL((stein_logdet_kernel<T, G, MMAX>), dim3((p.n + NS - 1) / NS), dim3(256), 0, stream, p, ld_out);
+  return hipGetLastError();
+}
+
 // ---- stage 3: gradS_i = 1/2 (sym(acc_i) - csum_i P_i) ------------------------------------------------------------------------
 // acc_i: the sum of the `slices` (n,m,m) slices of the pair pass, in the order s = 0, 1, ...
 template <typename T>
@@ -350,6 +402,9 @@ __global__ __launch_bounds__(256) void stein_finish_kernel(const T* __restrict__
 template <typename T, int G, int MMAX>
 static hipError_t launch_stein(const SteinParams& p, hipStream_t stream) {
   if (stein_slices(p.m) != (stein_reg_acc<MMAX>() ? 1 : 256 / G)) return hipErrorInvalidValue;   // the workspace layout's rule
+  // stage 1b, the instantiation of the pair pass that follows: it replaces stage 1's ld_c
+  const hipError_t e = launch_stein_logdet<T, G, MMAX>(p, const_cast<double*>(p.ld), stream);
+  if (e != hipSuccess) return e;
   if (p.W != nullptr) hipLaunchKernelGGL((stein_pair_kernel<T, G, MMAX, true>), dim3(p.n), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL((stein_pair_kernel<T, G, MMAX, false>), dim3(p.n), dim3(256), 0, stream, p);
   return hipGetLastError();

@@ -57,6 +57,13 @@ def _squeeze_pairs(D):
     return D
 
 
+def clamp_nonnegative(x):
+    """x where x >= 0 (and where it is NaN), 0 with derivative 0 where x < 0: for terms that are >= 0 mathematically and
+    come out negative by rounding when two classes are nearly equal -- the log-determinant term of ``bhattacharyya`` and
+    ``logdet.stein``, the Jeffreys divergence.  The fused kernels apply the identical rule."""
+    return torch.where(x < 0, torch.zeros_like(x), x)
+
+
 def _pair_matrix(A, B, scale, sqrt_mode):
     same = A is B
     A3 = _batch_of_matrices(A)
@@ -237,9 +244,11 @@ def _gauss_pair_terms(statistics_A, statistics_B):
 @_fusable("gaussian", _native._lib.SQFA_GAUSS_BHATTACHARYYA, False, "gauss")
 def bhattacharyya(statistics_A, statistics_B):
     """Bhattacharyya distance between Gaussians (reference: src/sqfa/distances.py:240-280):
-    Q/8 + (logdet Sbar - (logdet Sigma_i + logdet Sigma_j)/2)/2."""
+    Q/8 + (logdet Sbar - (logdet Sigma_i + logdet Sigma_j)/2)/2.  The log-determinant term is >= 0 mathematically; for
+    near-equal classes the three rounded logarithms give a negative one, which the reference passes on (and ``hellinger``
+    turns into NaN): here it is clamped to 0 with derivative 0."""
     Q, LD, ldA, ldB = _gauss_pair_terms(statistics_A, statistics_B)
-    det_term = 0.5 * (LD - 0.5 * (ldA[:, None] + ldB[None]))
+    det_term = clamp_nonnegative(0.5 * (LD - 0.5 * (ldA[:, None] + ldB[None])))
     return torch.squeeze(Q / 8 + det_term)
 
 

@@ -13,7 +13,9 @@ With the precisions ``P_c = inv(Sigma_c)`` and ``delta = mu_i - mu_j``
 
 The explicit-difference form is the one evaluated, everywhere: the two traces of the textbook form are each about K and
 cancel the digits that matter when two classes are close (in float32, two classes 1e-3 apart: 3e-3 relative error against
-3e-6).  With the precisions in hand a pair costs O(K^2); no per-pair factorisation.
+3e-6).  With the precisions in hand a pair costs O(K^2); no per-pair factorisation.  ``J >= 0`` mathematically: a rounded
+negative value (not seen on the close, ill-conditioned classes of the tests) is clamped to 0 with derivative 0, by
+``distances.clamp_nonnegative`` here and by the same rule in the kernel.
 
 Called directly the operators are plain torch expressions: any device and dtype, differentiable by autograd, results
 (nA, nB) with unit batch dimensions squeezed as the operators of ``sqfa_amd.distances``.  As a model's ``distance_fun`` in
@@ -24,7 +26,8 @@ pair-kernel operators.
 """
 import torch
 
-from .distances import EPSILON, _batch_of_matrices, _family_spec, _gaussian_inputs, _squeeze_pairs, register_class_pair
+from .distances import (EPSILON, _batch_of_matrices, _family_spec, _gaussian_inputs, _squeeze_pairs, clamp_nonnegative,
+                        register_class_pair)
 
 __all__ = ["jeffreys", "jeffreys_root", "jeffreys_spd", "jeffreys_spd_root"]
 
@@ -46,7 +49,7 @@ def _jeffreys_matrix(muA, covA, muB, covB):
             delta = muA[a:a + rows, None] - muB[None]
             sP = PA[a:a + rows, None] + PB[None]
             J = J + 0.5 * torch.einsum("abk,abkl,abl->ab", delta, sP, delta)
-        out.append(J)
+        out.append(clamp_nonnegative(J))      # J >= 0 mathematically: a rounded negative one is 0 with derivative 0
     return out[0] if len(out) == 1 else torch.cat(out)
 
 

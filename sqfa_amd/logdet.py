@@ -5,15 +5,17 @@ dimensionality reduction for SPD matrices".
     S(A, B) = logdet((A + B)/2) - 1/2 logdet A - 1/2 logdet B
 
     stein(A, B)[i, j]   = S(A_i, B_j)            batches of SPD matrices (nA,K,K), (nB,K,K) -> (nA,nB); for ``SecondMomentsSQFA``
-    stein_root(A, B)    = sqrt(|S| + 1e-6)        sqrt(S) is a metric (Sra 2012)
+    stein_root(A, B)    = sqrt(S + 1e-6)          sqrt(S) is a metric (Sra 2012)
 
 ``S`` needs Cholesky factors only: no eigen-decomposition per pair.  It equals twice the Bhattacharyya distance of the
-zero-mean Gaussians N(0, A), N(0, B).  The absolute value inside the root follows ``transport.bures_wasserstein``: in float32
-the rounding of three log-determinants at K = 64 exceeds 1e-6, so ``sqrt(S + eps)`` would give NaN for near-identical classes.
+zero-mean Gaussians N(0, A), N(0, B).
 
 Numerical limit: ``S`` is second order in the difference of the two matrices while each log-determinant is first order, so
 the three-log form loses digits for close matrices (float32, K = 4: relative error 3e-6 at S = 2e-2, 8e-4 at 2e-4, 4e-2 at
-2e-6).  ``distances.bhattacharyya`` shares this; SQFA pushes the classes apart, so it is not the working regime.
+2e-6) and comes out negative for near-equal ones (float32, classes 1e-3 apart at condition number 1e3: about -2e-5 where
+the true value is 1e-6).  ``S >= 0`` mathematically, so a negative result is clamped to 0 with derivative 0
+(``distances.clamp_nonnegative``; NaN stays NaN), here and in the kernel alike: the root never sees a negative argument
+and the gradient never pulls two such classes together.  ``distances.bhattacharyya`` shares limit and clamp.
 
 Called directly the operators are plain torch expressions (``torch.logdet``, as the torch expression of
 ``distances.bhattacharyya``; NaN where a determinant is negative): any device and dtype, differentiable by autograd, results
@@ -25,7 +27,8 @@ closure for them.
 """
 import torch
 
-from .distances import EPSILON, _batch_of_matrices, _family_spec, _squeeze_pairs, register_class_pair
+from .distances import (EPSILON, _batch_of_matrices, _family_spec, _squeeze_pairs, clamp_nonnegative,
+                        register_class_pair)
 
 __all__ = ["stein", "stein_root"]
 
@@ -41,18 +44,19 @@ def _stein_matrix(A, B):
     out = []
     for a in range(0, nA, rows):
         mid = 0.5 * (A[a:a + rows, None] + B[None])
-        out.append(torch.logdet(mid) - 0.5 * (ldA[a:a + rows, None] + ldB[None]))
+        out.append(clamp_nonnegative(torch.logdet(mid) - 0.5 * (ldA[a:a + rows, None] + ldB[None])))
     return out[0] if len(out) == 1 else torch.cat(out)
 
 
 def stein(A, B):
-    """Stein divergence logdet((A_i + B_j)/2) - (logdet A_i + logdet B_j)/2: (nA,K,K),(nB,K,K) -> (nA,nB)."""
+    """Stein divergence logdet((A_i + B_j)/2) - (logdet A_i + logdet B_j)/2, clamped at 0 from below:
+    (nA,K,K),(nB,K,K) -> (nA,nB)."""
     return _squeeze_pairs(_stein_matrix(_batch_of_matrices(A), _batch_of_matrices(B)))
 
 
 def stein_root(A, B):
-    """sqrt(|stein| + 1e-6)."""
-    return torch.sqrt(torch.abs(stein(A, B)) + EPSILON)
+    """sqrt(stein + 1e-6)."""
+    return torch.sqrt(stein(A, B) + EPSILON)
 
 
 # As SecondMomentsSQFA's distance_fun: per-class Cholesky -> one pass over the class pairs that factors every pair's mean

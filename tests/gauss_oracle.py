@@ -13,9 +13,10 @@ import torch
 EPS = 1e-6
 
 
-def _rows_D(mu_r, cov_r, mu, cov, kind):
+def _rows_D(mu_r, cov_r, mu, cov, kind, clamp=False):
     """(R,C) distances of the classes (mu_r, cov_r) to all classes (mu, cov); the log-determinant term of a class with
-    itself is not special-cased here: callers mask the diagonal."""
+    itself is not special-cased here: callers mask the diagonal.  clamp: a negative log-determinant term counts as 0,
+    with derivative 0 (the yardstick of tests/test_gpu_close_classes.py: finite where the plain expression is NaN)."""
     Sbar = 0.5 * (cov_r[:, None] + cov[None])
     delta = mu_r[:, None] - mu[None]
     sol = torch.linalg.solve(Sbar, delta.unsqueeze(-1)).squeeze(-1)
@@ -24,18 +25,19 @@ def _rows_D(mu_r, cov_r, mu, cov, kind):
         return Q
     if kind == 3:
         return torch.sqrt(Q + EPS)
-    Bh = Q / 8 + 0.5 * (torch.logdet(Sbar) - 0.5 * (torch.logdet(cov_r)[:, None] + torch.logdet(cov)[None]))
+    det = 0.5 * (torch.logdet(Sbar) - 0.5 * (torch.logdet(cov_r)[:, None] + torch.logdet(cov)[None]))
+    Bh = Q / 8 + (torch.where(det < 0, torch.zeros_like(det), det) if clamp else det)
     return Bh if kind == 0 else torch.sqrt(1 - torch.exp(-Bh) + EPS)
 
 
-def _full_expression(mu, cov, kind, weight, dtype=torch.float64):
-    """loss = weight * sum_{i>j} D_ij, its gradients, and D with the reference's diagonal."""
+def _full_expression(mu, cov, kind, weight, dtype=torch.float64, clamp=False, W=None):
+    """loss = weight * sum_{i>j} D_ij (W (C,C): sum_{i>j} W_ij D_ij), its gradients, and D with the reference's diagonal."""
     mu = mu.detach().to(dtype).requires_grad_(True)
     cov = cov.detach().to(dtype).requires_grad_(True)
-    D = _rows_D(mu, cov, mu, cov, kind)
+    D = _rows_D(mu, cov, mu, cov, kind, clamp)
     C = mu.shape[0]
     rows, cols = torch.tril_indices(C, C, offset=-1)
-    loss = weight * D[rows, cols].sum()
+    loss = weight * D[rows, cols].sum() if W is None else (W.to(dtype)[rows, cols] * D[rows, cols]).sum()
     gmu, gcov = torch.autograd.grad(loss, (mu, cov))
     D = D.detach().clone()
     D.fill_diagonal_(0.0 if kind in (0, 2) else EPS ** 0.5)

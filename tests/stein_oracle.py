@@ -56,11 +56,11 @@ def three_logdets(A, B, dtype=np.float64):
     return (np.linalg.slogdet(mid)[1].astype(dtype) - dtype(0.5) * (ldA[:, None] + ldB[None])).astype(dtype)
 
 
-def loss_and_gradient(S, sqrt_mode, weight, W=None, dtype=np.float64, div=None):
+def loss_and_gradient(S, sqrt_mode, weight, W=None, dtype=np.float64, div=None, clamp=False):
     """dict(loss, dist, grad) of sum_{i>j} w_ij D_ij for the classes S (n,m,m): dist the full unweighted (n,n) matrix, the
     diagonal 0 or sqrt(eps); grad (n,m,m) in closed form.  float64: the divergences come from the generalised eigenvalues;
     any other dtype: from three_logdets, and every operation of the gradient runs in that dtype.  `div`: these divergences
-    where the caller has them already."""
+    where the caller has them already.  clamp: a negative divergence counts as 0, with derivative 0."""
     S = np.asarray(S, dtype)
     n = S.shape[0]
     if div is None:
@@ -68,11 +68,15 @@ def loss_and_gradient(S, sqrt_mode, weight, W=None, dtype=np.float64, div=None):
     div = np.array(div, dtype)
     div[np.arange(n), np.arange(n)] = 0
     eps = dtype(EPS)
+    keep = np.ones_like(div)
+    if clamp:
+        keep = np.where(div < 0, dtype(0), dtype(1)).astype(dtype)
+        div = np.where(div < 0, dtype(0), div).astype(dtype)
     if sqrt_mode:
         D = np.sqrt(np.abs(div) + eps).astype(dtype)
-        dD = (np.sign(div) / (dtype(2) * D)).astype(dtype)
+        dD = ((keep if clamp else np.sign(div)) / (dtype(2) * D)).astype(dtype)
     else:
-        D, dD = div, np.ones_like(div)
+        D, dD = div, keep
     Wm = np.full((n, n), weight, dtype) if W is None else np.asarray(W, dtype)
     r, c = np.tril_indices(n, -1)
     loss = (Wm[r, c] * D[r, c]).sum(dtype=dtype)

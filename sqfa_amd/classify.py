@@ -44,7 +44,9 @@ def _log_priors(priors, n_classes, device):
     if isinstance(priors, str):
         raise ValueError(f"priors must be None, 'uniform' or (n_classes,) non-negative weights, got {priors!r}")
     try:
-        w = torch.as_tensor(priors).detach().to(device=device, dtype=torch.float64)
+        # a list of Python floats in float64, not in torch's default dtype (float32 rounds the weights, and 1e-300 to zero)
+        w = priors.detach() if torch.is_tensor(priors) else torch.as_tensor(priors, dtype=torch.float64)
+        w = w.to(device=device, dtype=torch.float64)
     except (TypeError, ValueError, RuntimeError) as err:
         raise ValueError("priors must be None, 'uniform' or (n_classes,) non-negative weights") from err
     if w.shape != (n_classes,):

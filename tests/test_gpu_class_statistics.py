@@ -2,6 +2,8 @@
 float64 oracle tests/class_statistics_oracle.py.  Bounds: the project's own for class statistics
 (test_gpu_model.test_class_statistics_on_gpu_vs_reference): rel_err < 1e-11 in float64, < 2e-5 in float32.
 Shapes are the smallest at which each mechanism can go wrong: the output tile is 64 x 64, a row chunk 32 rows."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +13,7 @@ import model_cases as mc
 from conftest import rel_err
 from sqfa_amd import _native, statistics
 from sqfa_amd.statistics import ClassStatisticsAccumulator
+from sqfa_amd._optim import _no_gc
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -226,7 +229,10 @@ def test_captured_call_equals_the_eager_one(estimator):
     eager = _native.class_moments(X, order, class_start, 5, CODE[estimator], True)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    # torch no longer collects garbage before a capture, and a cyclic collection inside one that finalises device
+    # tensors or an older graph aborts the process (_optim._no_gc): collect now, none while the stream captures
+    gc.collect()
+    with _no_gc(), torch.cuda.graph(graph):
         captured = _native.class_moments(X, order, class_start, 5, CODE[estimator], True)
     for t in captured:
         t.fill_(-1.0)

@@ -7,6 +7,9 @@ Shapes (C, K, N).  The kernel's boundaries: the MFMA k-step of 4 and the 16-row 
 300, a multiple of 4), and the class splits: below 1024 sample tiles the groups are split over up to 16 workgroups whose
 partial reductions a second launch merges ((300, 16, 2000): 15 splits of 5 groups); (5, 3, 65537) has 1025 tiles, the
 smallest N at which several groups run unsplit and the workgroup writes the results itself.
+
+The float32 scores are also held, entry by entry, to the a priori bound of tests/classify_hard.py against its long double
+truth; tests/test_gpu_classify_hard.py does the same on hard inputs at small shapes.
 """
 import functools
 
@@ -14,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import classify_hard
 import classify_oracle
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +45,8 @@ def _np_dtype(dtype):
 def _reference(case, dtype):
     """The problem rounded to `dtype` (what every implementation is given), the float64 oracle on exactly those numbers, and
     for float32 the bound of the project's float32 convention: max(1e-5 (1 + max |score|), 5 x the max abs error of the same
-    formula in float32 torch on the same inputs)."""
+    formula in float32 torch on the same inputs), with the long double truth and the per-entry a priori bound of
+    tests/classify_hard.py (truth_and_bound32) for the scores."""
     C, K, N, sep, means, priors = case
     Z, labels, mu, cov = classify_oracle.problem(C, K, N, sep, seed=C + 7 * K)
     npdt = _np_dtype(dtype)
@@ -72,6 +77,8 @@ def _reference(case, dtype):
         out["torch_err"] = np.abs(St[out["finite"]] - S[out["finite"]]).max()
         out["bound"] = max(1e-5 * (1 + smax), 5 * out["torch_err"])
         out["torch_pred_wrong"] = int((St.argmax(1) != out["pred"]).sum())
+        # per entry: the long double truth and the a priori float32 bound of tests/classify_hard.py
+        out["S_true"], out["entry_bound"] = classify_hard.truth_and_bound32(Z, mu, cov, classify_oracle.log_priors(w, C))
     return out
 
 
@@ -96,6 +103,10 @@ def _check_values(got, want, ref, dtype, what):
         print(f"{what}: max abs error {err.max():.3e}, bound {ref['bound']:.3e}, float32 torch {ref['torch_err']:.3e}, "
               f"ratio to torch {err.max() / max(ref['torch_err'], 1e-30):.2f}")
         assert err.max() <= ref["bound"]
+        if what == "scores":
+            ratio = (np.abs(got[fin].astype(np.longdouble) - ref["S_true"][fin]) / ref["entry_bound"][fin]).max()
+            print(f"{what}: worst error / per-entry bound {float(ratio):.3f}")
+            assert ratio <= 1
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])

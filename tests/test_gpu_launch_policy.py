@@ -12,9 +12,13 @@ class (C=17, C=37: lane groups past the last class sweep a copy of it), several 
 with the kernel (m=12 one column per lane, m=17 a lone column, m=20 and m=24 the 32-lane-wide elimination; m=24 float64 runs on
 a 2-D pair row), sizes below their padded size (m=14 on 16, m=19 on 20, m=22 on 24: the identity fill and every `< m` guard),
 both element types, cross mode (the A side alone takes the fused launch) and both lane geometries of a size."""
+import gc
+
 import numpy as np
 import pytest
 import torch
+
+from sqfa_amd._optim import _no_gc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -123,7 +127,10 @@ def test_captured_call_replayed_on_changed_inputs():
     run(A, None, 0)   # the library is loaded and the workspace query answered before the capture
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    # torch no longer collects garbage before a capture, and a cyclic collection inside one that finalises device
+    # tensors or an older graph aborts the process (_optim._no_gc): collect now, none while the stream captures
+    gc.collect()
+    with _no_gc(), torch.cuda.graph(g):
         out = run(A, None, 0)
     for seed in (4, 5, 6):
         fresh = _inputs(m, C, False, seed=seed)

@@ -1,6 +1,8 @@
 """GPU tests of the native orthogonal constraint (sqfa_orthogonal_forward / _backward, _native.OrthogonalFilters,
 constraints.Orthogonal): kernel parity with torch's _Orthogonal, the golden closures and fits with torch's
 householder_product made to raise, the single-node and graph-captured closures, and the NATIVE_ORTHOGONAL switch."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -8,6 +10,7 @@ import torch
 import model_cases as mc
 import orthogonal_oracle as oo
 from conftest import rel_err
+from sqfa_amd._optim import _no_gc
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -155,7 +158,10 @@ def test_single_node_closure_replays_in_a_graph(dtype, no_householder_product):
             evaluate()
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    # torch no longer collects garbage before a capture, and a cyclic collection inside one that finalises device
+    # tensors or an older graph aborts the process (_optim._no_gc): collect now, none while the stream captures
+    gc.collect()
+    with _no_gc(), torch.cuda.graph(graph):
         g_loss, g_flags, g_grad = evaluate()
     step = torch.tensor(oo.make_case(9, 64, "negative", seed=7)[0], dtype=dtype, device=DEV)
     with torch.no_grad():

@@ -38,12 +38,6 @@
 
 namespace sqfa {
 
-template <typename T> __device__ __forceinline__ T g_rsqrt(T x);
-template <> __device__ __forceinline__ float g_rsqrt<float>(float x) { return 1.0f / sqrtf(x); }
-template <> __device__ __forceinline__ double g_rsqrt<double>(double x) { return 1.0 / sqrt(x); }
-__device__ __forceinline__ float g_log(float x) { return logf(x); }
-__device__ __forceinline__ double g_log(double x) { return log(x); }
-
 // LDS of one wave is processed in program order; this only stops the compiler from moving LDS
 // accesses across the hand-off between lanes of a group (all inside one wave)
 __device__ __forceinline__ void group_sync() {
@@ -83,11 +77,6 @@ struct GaussParams {
 // that the uniform fused kernels stay the code they were
 enum { GAUSS_PLAIN = 0, GAUSS_FUSED = 1, GAUSS_PRE = 2, GAUSS_FUSED_W = 3 };
 
-__device__ __forceinline__ float g_exp(float x) { return expf(x); }
-__device__ __forceinline__ double g_exp(double x) { return exp(x); }
-__device__ __forceinline__ float g_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double g_sqrt(double x) { return sqrt(x); }
-
 // D and its partial derivatives from the pair terms: dQ = dD/dQ in total (through Bh too), dBh = dD/dBh (dD/dLD = dBh / 2,
 // dD/dld_c = -dBh / 4).  On the diagonal the log-determinant term is exactly zero, as in the reference.  The term is >= 0
 // mathematically and the difference of three rounded logarithms: where that comes out negative (near-equal classes) it is
@@ -97,7 +86,7 @@ __device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi
   if (kind == SQFA_GAUSS_MAHALANOBIS_SQ) {
     D = q; dQ = T(1); dBh = T(0);
   } else if (kind == SQFA_GAUSS_MAHALANOBIS) {
-    D = g_sqrt(q + eps); dQ = T(0.5) / D; dBh = T(0);
+    D = math::sqrt(q + eps); dQ = T(0.5) / D; dBh = T(0);
   } else {
     const T det = diagonal ? T(0) : T(0.5) * (ld - T(0.5) * (ldi + ldj));
     const bool clamped = det < T(0);
@@ -105,8 +94,8 @@ __device__ __forceinline__ void gauss_distance(int kind, T eps, T q, T ld, T ldi
     if (kind == SQFA_GAUSS_BHATTACHARYYA) {
       D = bh; dBh = T(1);
     } else {
-      const T e = g_exp(-bh);
-      D = g_sqrt(T(1) - e + eps);
+      const T e = math::exp(-bh);
+      D = math::sqrt(T(1) - e + eps);
       dBh = T(0.5) * e / D;
     }
     dQ = T(0.125) * dBh;
@@ -168,7 +157,7 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
     // ---- Cholesky Sbar = R R^T, in place (lower) --------------------------------------
     for (int k = 0; k < m; ++k) {
       const T piv = a[k * LD_ + k];
-      const T rs = g_rsqrt<T>(piv);   // non-positive pivot -> NaN everywhere downstream, never a fault
+      const T rs = math::rsqrt(piv);   // non-positive pivot -> NaN everywhere downstream, never a fault
       T l = T(0);
       if (active && r >= k) {
         l = a[r * LD_ + k] * rs;
@@ -182,7 +171,7 @@ __global__ void gauss_pair_kernel(const GaussParams p) {
     }
     const T diag = active ? a[r * LD_ + r] : T(1);
     const T rdiag = T(1) / diag;
-    const T ld = T(2) * group_total<G>(active ? g_log(diag) : T(0));
+    const T ld = T(2) * group_total<G>(active ? math::log(diag) : T(0));
     // ---- z = R^-1 delta (column oriented) ----------------------------------------------
     T z = T(0);
     for (int k = 0; k < m; ++k) {
@@ -470,10 +459,10 @@ void gauss_pair_reg_kernel(const GaussParams p) {
       T piv = row[r];
 #pragma unroll
       for (int k = 0; k < r; ++k) piv -= row[k] * row[k];
-      const T rs = g_rsqrt<T>(piv);   // non-positive pivot -> NaN downstream, never a fault
+      const T rs = math::rsqrt(piv);   // non-positive pivot -> NaN downstream, never a fault
       rdiag[r] = rs;
       const T dk = piv * rs;
-      ld += g_log(dk);
+      ld += math::log(dk);
 #pragma unroll
       for (int c = 0; c < r; ++c) a[at(r, c)] = row[c];
       a[at(r, r)] = dk;
@@ -700,12 +689,23 @@ extern "C" int sqfa_gauss_pair_terms(const void* muA, const void* covA, int nA, 
 }
 
 // workspace of sqfa_gauss_pairwise_loss: [logdet Sigma_c (n)] [partial losses (n) double] [counts (n,2) int] [Sigma_c^-1 (n,m,m)]
-extern "C" size_t sqfa_gauss_pairwise_workspace_bytes(int n, int m, int dtype) {
-  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return 0;
-  const size_t elem = dtype == SQFA_F32 ? 4 : 8;
+struct GaussLayout {
+  size_t off_ldc, off_loss, off_cnt, off_sinv, total;   // total 0: no layout for these sizes
+};
+static GaussLayout gauss_layout(int n, int m, int dtype) {
+  GaussLayout w{};
+  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return w;
   const size_t mp = ((size_t)m + 3) & ~(size_t)3;   // the register kernels park Sigma_c^-1 with their padded pitch
-  return 3 * align256((size_t)n * 8) + align256((size_t)n * mp * mp * elem);
+  WorkspaceCursor ws;
+  w.off_ldc = ws.take((size_t)n * 8);   // 8 bytes per class whatever the dtype
+  w.off_loss = ws.take((size_t)n * sizeof(double));
+  w.off_cnt = ws.take((size_t)n * 2 * sizeof(int));
+  w.off_sinv = ws.take((size_t)n * mp * mp * dtype_bytes(dtype));
+  w.total = ws.at;
+  return w;
 }
+
+extern "C" size_t sqfa_gauss_pairwise_workspace_bytes(int n, int m, int dtype) { return gauss_layout(n, m, dtype).total; }
 
 extern "C" int sqfa_gauss_pairwise_loss_weighted(const void* mu, const void* cov, int n, int m, int dtype, int kind,
                                                  double eps, const void* pair_weights, double uniform_weight,
@@ -713,21 +713,21 @@ extern "C" int sqfa_gauss_pairwise_loss_weighted(const void* mu, const void* cov
                                                  int* nonfinite_out, void* workspace, size_t workspace_bytes,
                                                  void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (mu == nullptr || cov == nullptr || n < 2 || m < 1) return SQFA_ERR_BAD_ARGUMENT;
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
-  if (kind < SQFA_GAUSS_BHATTACHARYYA || kind > SQFA_GAUSS_MAHALANOBIS) return SQFA_ERR_BAD_ARGUMENT;
-  if ((gmu_out != nullptr) != (gcov_out != nullptr)) return SQFA_ERR_BAD_ARGUMENT;
-  if (m > 64) return SQFA_ERR_UNSUPPORTED_M;
-  const size_t need = sqfa_gauss_pairwise_workspace_bytes(n, m, dtype);
-  if (workspace == nullptr || workspace_bytes < need) return SQFA_ERR_WORKSPACE;
+  const GaussLayout w = gauss_layout(n, m, dtype);
+  // (no name: this entry point sets no text for sqfa_hip_last_error())
+  const bool grads_ok = (gmu_out != nullptr) == (gcov_out != nullptr);
+  const int rc = check_pair_loss_args(nullptr, nullptr, mu == nullptr || cov == nullptr, n, m, dtype,
+                                      kind >= SQFA_GAUSS_BHATTACHARYYA && kind <= SQFA_GAUSS_MAHALANOBIS,
+                                      grads_ok ? nullptr : "gmu_out and gcov_out go together", w.total, nullptr, workspace,
+                                      workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const size_t block = align256((size_t)n * 8);
   GaussParams p{mu, cov, mu, cov, nullptr, nullptr, nullptr, nullptr, gmu_out, gcov_out, n, n, m, 1};
-  fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + block),
-                        reinterpret_cast<int*>(ws + 2 * block));
+  fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + w.off_loss),
+                        reinterpret_cast<int*>(ws + w.off_cnt));
   p.kind = kind;
-  p.ldc = ws;
-  p.sinv = ws + 3 * block;
+  p.ldc = ws + w.off_ldc;
+  p.sinv = ws + w.off_sinv;
   if (kind <= SQFA_GAUSS_HELLINGER) {   // per-class log-determinants first: every pair needs both of its classes'
     GaussParams pre = p;
     pre.gmuA = pre.gcovA = nullptr;

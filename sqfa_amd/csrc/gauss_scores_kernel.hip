@@ -6,7 +6,7 @@
 //
 // Launches (caller's stream; nothing allocated, synchronised or read back; no float atomics, every sum in a fixed order:
 // bitwise reproducible; every grid a function of (N, C, K) alone):
-//   gauss_factor_kernel   once per classifier, one 64-thread workgroup per class (the pattern of stein_class_kernel):
+//   gauss_factor_kernel   once per classifier, one 64-thread workgroup per class, on the factor stage of spd_class.hpp:
 //                         Cholesky in double in LDS, W_c = L_c^-1 in place, written lower triangular with exact zeros above
 //                         the diagonal; offset_c = -sum log diag L_c - K/2 log 2 pi + log pi_c in double; a class with a
 //                         pivot that is not positive and finite, a mean that is not finite or a log prior that is NaN or
@@ -34,27 +34,17 @@
 #include <type_traits>
 
 #include "../../include/sqfa_hip.h"
+#include "class_pair_loss.hpp"   // namespace math, dispatch_dtype, WorkspaceCursor, set_last_error
 #include "proj_traits.hpp"
+#include "spd_class.hpp"
 
 namespace sqfa {
-
-// sqfa_api.hip: the text sqfa_hip_last_error() returns
-void set_last_error(const char* text);
 
 constexpr int GS_THREADS = 256;
 constexpr int GS_ROWS = 64;         // samples per workgroup
 constexpr int GS_KMAX = 64;
 constexpr int GS_MAX_SPLIT = 16;    // class splits at most
 constexpr int GS_TARGET_WG = 1024;  // workgroups asked for (four per CU) before the classes stop being split
-
-__device__ __forceinline__ float gs_exp(float x) { return expf(x); }
-__device__ __forceinline__ double gs_exp(double x) { return exp(x); }
-__device__ __forceinline__ float gs_log(float x) { return logf(x); }
-__device__ __forceinline__ double gs_log(double x) { return log(x); }
-template <typename T> __device__ __forceinline__ T gs_nan();
-template <> __device__ __forceinline__ float gs_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double gs_nan<double>() { return __builtin_nan(""); }
-template <typename T> __device__ __forceinline__ T gs_ninf() { return -(T)INFINITY; }
 
 // ---- the factor pass --------------------------------------------------------------------------------------------------------
 
@@ -63,18 +53,13 @@ __global__ __launch_bounds__(64) void gauss_factor_kernel(const T* __restrict__ 
                                                           const double* __restrict__ log_prior, int C, int K,
                                                           T* __restrict__ W, double* __restrict__ offset,
                                                           int* __restrict__ bad_out) {
-  constexpr int LD = 65;
-  __shared__ double a[64 * LD];
+  constexpr int LD = SPD_LD;
+  __shared__ double a[SPD_ELEMS];
   __shared__ int s_bad;
   const int r = threadIdx.x, kk = K * K, c = blockIdx.x;
-  const T* S = cov + (size_t)c * kk;
   T* out = W + (size_t)c * kk;
   if (r == 0) s_bad = 0;
-  for (int idx = r; idx < kk; idx += 64) {
-    const int rr = idx / K, cc = idx % K;
-    if (cc <= rr) a[rr * LD + cc] = (double)S[idx];
-  }
-  __syncthreads();
+  spd_load_lower(a, cov + (size_t)c * kk, K, r);
   if (mu != nullptr && r < K) {
     const double v = (double)mu[(size_t)c * K + r];
     if (!(fabs(v) < (double)INFINITY)) s_bad = 1;   // every writer writes 1
@@ -82,46 +67,18 @@ __global__ __launch_bounds__(64) void gauss_factor_kernel(const T* __restrict__ 
   __syncthreads();
   const double lp = log_prior != nullptr ? log_prior[c] : -log((double)C);
   bool bad = s_bad != 0 || !(lp < (double)INFINITY);   // NaN or +inf; -inf is a class that never wins
-  // Cholesky, right-looking: after step k column k holds L[:, k]
-  double logdiag = 0.0;
-  for (int k = 0; k < K && !bad; ++k) {
-    const double d = a[k * LD + k];   // the same value in every thread: the exit is uniform
-    if (!(d > 0.0 && d < (double)INFINITY)) {
-      bad = true;
-      break;
-    }
-    logdiag += 0.5 * log(d);
-    const double root = sqrt(d), inv = 1.0 / root;
-    __syncthreads();
-    if (r == k) a[k * LD + k] = root;
-    if (r > k && r < K) a[r * LD + k] *= inv;
-    __syncthreads();
-    if (r > k && r < K) {
-      const double lrk = a[r * LD + k];
-      for (int cc = k + 1; cc <= r; ++cc) a[r * LD + cc] -= lrk * a[cc * LD + k];
-    }
-    __syncthreads();
-  }
+  double logdet = 0.0;   // sum_k log pivot_k = 2 sum_k log (L_c)_kk
+  if (!bad) bad = !spd_cholesky<true>(a, K, r, logdet);
   if (bad) {
-    for (int idx = r; idx < kk; idx += 64) out[idx] = gs_nan<T>();
+    for (int idx = r; idx < kk; idx += 64) out[idx] = math::nan<T>();
     if (r == 0) {
-      offset[c] = gs_nan<double>();
+      offset[c] = math::nan<double>();
       atomicAdd(bad_out, 1);
     }
     return;
   }
-  if (r == 0) offset[c] = -logdiag - 0.5 * K * 1.8378770664093454835606594728112 + lp;   // log 2 pi
-  // X = L^-1 in place, last column first: X[r][j] L[j][j] = -sum_{k=j+1..r} X[r][k] L[k][j]
-  for (int j = K - 1; j >= 0; --j) {
-    const double xjj = 1.0 / a[j * LD + j];
-    double sum = 0.0;
-    if (r > j && r < K)
-      for (int k = j + 1; k <= r; ++k) sum += a[r * LD + k] * a[k * LD + j];
-    __syncthreads();
-    if (r == j) a[j * LD + j] = xjj;
-    if (r > j && r < K) a[r * LD + j] = -sum * xjj;
-    __syncthreads();
-  }
+  if (r == 0) offset[c] = -(0.5 * logdet) - 0.5 * K * 1.8378770664093454835606594728112 + lp;   // log 2 pi
+  spd_invert_lower(a, K, r);
   for (int idx = r; idx < kk; idx += 64) {
     const int rr = idx / K, cc = idx % K;
     out[idx] = cc <= rr ? (T)a[rr * LD + cc] : (T)0;
@@ -165,11 +122,11 @@ template <typename T> __device__ __forceinline__ void gs_take(GsRun<T>& a, T s, 
     a.idx = c;
   }
   const T d = s - a.m;
-  const T e = gs_exp(d > T(0) ? -d : d);   // exp(-|d|); d is NaN only for -inf - -inf, which neither branch below takes
+  const T e = math::exp(d > T(0) ? -d : d);   // exp(-|d|); d is NaN only for -inf - -inf, which neither branch below takes
   if (s > a.m) {
     a.sum = a.sum * e + T(1);
     a.m = s;
-  } else if (s > gs_ninf<T>()) {
+  } else if (s > math::neg_inf<T>()) {
     a.sum += e;
   }
 }
@@ -181,8 +138,8 @@ template <typename T> __device__ __forceinline__ void gs_merge(GsRun<T>& a, T be
     a.idx = idx;
   }
   const T mx = m > a.m ? m : a.m;
-  if (mx > gs_ninf<T>()) {
-    const T lo = (m > a.m ? a.sum : sum) * gs_exp((m > a.m ? a.m : m) - mx);   // the side with the smaller max, scaled
+  if (mx > math::neg_inf<T>()) {
+    const T lo = (m > a.m ? a.sum : sum) * math::exp((m > a.m ? a.m : m) - mx);   // the side with the smaller max, scaled
     const T hi = m > a.m ? sum : a.sum;
     a.sum = m == a.m ? a.sum + sum : hi + lo;
   }
@@ -257,16 +214,16 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
   if (g_lo < g_hi) load(4 * g_lo);
 
   GsRun<T> run;
-  run.best = gs_ninf<T>();
+  run.best = math::neg_inf<T>();
   run.idx = INT_MAX;
-  run.m = gs_ninf<T>();
+  run.m = math::neg_inf<T>();
   run.sum = T(0);
   run.nan = false;
 
 #pragma unroll 1
   for (int g = g_lo; g < g_hi; ++g) {
     const int c_mine = 4 * g + q;   // the class whose score this lane ends up with
-    const T off = c_mine < C ? (T)p.offset[c_mine] : gs_ninf<T>();
+    const T off = c_mine < C ? (T)p.offset[c_mine] : math::neg_inf<T>();
     if constexpr (CS == 4) {
       __syncthreads();   // the previous stage has been consumed (first pass: the zero fill is done)
       store();
@@ -311,7 +268,7 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
     const T r0 = gs_shfl_xor(hi ? part[0] : part[2], 32), r1 = gs_shfl_xor(hi ? part[1] : part[3], 32);
     const T a0 = (hi ? part[2] : part[0]) + r0, a1 = (hi ? part[3] : part[1]) + r1;
     const T tot = (odd ? a1 : a0) + gs_shfl_xor(odd ? a0 : a1, 16);
-    const T sc = c_mine < C ? T(-0.5) * tot + off : gs_ninf<T>();
+    const T sc = c_mine < C ? T(-0.5) * tot + off : math::neg_inf<T>();
     if (c_mine < C) {
       if (p.scores != nullptr && n < N) p.scores[(size_t)n * C + c_mine] = sc;
       gs_take(run, sc, c_mine);
@@ -338,8 +295,8 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
   }
   if (writer) {
     if (p.argmax != nullptr) p.argmax[n] = run.nan ? -1 : run.idx;
-    if (p.best != nullptr) p.best[n] = run.nan ? gs_nan<T>() : run.best;
-    if (p.lse != nullptr) p.lse[n] = run.nan ? gs_nan<T>() : run.m + gs_log(run.sum);
+    if (p.best != nullptr) p.best[n] = run.nan ? math::nan<T>() : run.best;
+    if (p.lse != nullptr) p.lse[n] = run.nan ? math::nan<T>() : run.m + math::log(run.sum);
   }
   const unsigned long long bal = __ballot(writer && run.nan);
   if (l == 0 && bal != 0) atomicAdd(p.nonfinite, __popcll(bal));
@@ -364,8 +321,8 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_merge_kernel(const GsParams<
     }
     nan = run.nan;
     if (p.argmax != nullptr) p.argmax[n] = nan ? -1 : run.idx;
-    if (p.best != nullptr) p.best[n] = nan ? gs_nan<T>() : run.best;
-    if (p.lse != nullptr) p.lse[n] = nan ? gs_nan<T>() : run.m + gs_log(run.sum);
+    if (p.best != nullptr) p.best[n] = nan ? math::nan<T>() : run.best;
+    if (p.lse != nullptr) p.lse[n] = nan ? math::nan<T>() : run.m + math::log(run.sum);
   }
   const unsigned long long bal = __ballot(nan);
   if ((threadIdx.x & 63) == 0 && bal != 0) atomicAdd(p.nonfinite, __popcll(bal));
@@ -375,7 +332,7 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_merge_kernel(const GsParams<
 
 struct GsLayout {
   int groups_per_split, splits;
-  size_t total;   // splits > 1: four (splits, N) arrays [best T][m T][sum T][idx int]
+  size_t off_best, off_m, off_sum, off_idx, total;   // splits > 1: four (splits, N) arrays [best T][m T][sum T][idx int]
 };
 
 static bool gs_layout(long long N, int C, int K, int dtype, GsLayout* w) {
@@ -391,8 +348,13 @@ static bool gs_layout(long long N, int C, int K, int dtype, GsLayout* w) {
   const int per = (int)((groups + splits - 1) / splits);
   w->groups_per_split = per;
   w->splits = (groups + per - 1) / per;   // no empty split
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8;
-  w->total = w->splits > 1 ? (size_t)w->splits * (size_t)N * (3 * esz + sizeof(int)) : 0;
+  const size_t cells = w->splits > 1 ? (size_t)w->splits * (size_t)N : 0;
+  WorkspaceCursor ws{1};   // the four arrays back to back
+  w->off_best = ws.take(cells * dtype_bytes(dtype));
+  w->off_m = ws.take(cells * dtype_bytes(dtype));
+  w->off_sum = ws.take(cells * dtype_bytes(dtype));
+  w->off_idx = ws.take(cells * sizeof(int));
+  w->total = ws.at;
   return true;
 }
 
@@ -422,11 +384,10 @@ static hipError_t run_scores(const void* Z, long long N, const void* mu, const v
   p.groups_per_split = lay.groups_per_split;
   p.splits = lay.splits;
   if (lay.splits > 1) {
-    const size_t cells = (size_t)lay.splits * (size_t)N;
-    p.p_best = reinterpret_cast<T*>(ws);
-    p.p_m = p.p_best + cells;
-    p.p_sum = p.p_m + cells;
-    p.p_idx = reinterpret_cast<int*>(p.p_sum + cells);
+    p.p_best = reinterpret_cast<T*>(ws + lay.off_best);
+    p.p_m = reinterpret_cast<T*>(ws + lay.off_m);
+    p.p_sum = reinterpret_cast<T*>(ws + lay.off_sum);
+    p.p_idx = reinterpret_cast<int*>(ws + lay.off_idx);
   }
   hipError_t e = hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
   if (e != hipSuccess) return e;
@@ -473,12 +434,11 @@ extern "C" int sqfa_gauss_class_factors(const void* means, const void* cov, cons
     return SQFA_ERR_UNSUPPORTED_M;
   }
   if (hipMemsetAsync(bad_out, 0, sizeof(int), stream) != hipSuccess) return SQFA_ERR_LAUNCH;
-  if (dtype == SQFA_F32)
-    hipLaunchKernelGGL((gauss_factor_kernel<float>), dim3(C), dim3(64), 0, stream, static_cast<const float*>(means),
-                       static_cast<const float*>(cov), log_priors, C, K, static_cast<float*>(W_out), offset_out, bad_out);
-  else
-    hipLaunchKernelGGL((gauss_factor_kernel<double>), dim3(C), dim3(64), 0, stream, static_cast<const double*>(means),
-                       static_cast<const double*>(cov), log_priors, C, K, static_cast<double*>(W_out), offset_out, bad_out);
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((gauss_factor_kernel<T>), dim3(C), dim3(64), 0, stream, static_cast<const T*>(means),
+                       static_cast<const T*>(cov), log_priors, C, K, static_cast<T*>(W_out), offset_out, bad_out);
+  });
   return hipGetLastError() == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }
 
@@ -513,11 +473,9 @@ extern "C" int sqfa_gauss_scores(const void* Z, long long N, const void* means, 
     set_last_error("sqfa_gauss_scores: workspace is null or smaller than sqfa_gauss_scores_workspace_bytes");
     return SQFA_ERR_WORKSPACE;
   }
-  const hipError_t e =
-      dtype == SQFA_F32
-          ? run_scores<float>(Z, N, means, W, offset, C, K, scores_out, argmax_out, best_out, logsumexp_out, nonfinite_out,
-                              static_cast<char*>(workspace), lay, stream)
-          : run_scores<double>(Z, N, means, W, offset, C, K, scores_out, argmax_out, best_out, logsumexp_out, nonfinite_out,
-                               static_cast<char*>(workspace), lay, stream);
+  const hipError_t e = dispatch_dtype(dtype, [&](auto t) {
+    return run_scores<decltype(t)>(Z, N, means, W, offset, C, K, scores_out, argmax_out, best_out, logsumexp_out, nonfinite_out,
+                                   static_cast<char*>(workspace), lay, stream);
+  });
   return e == hipSuccess ? SQFA_OK : SQFA_ERR_LAUNCH;
 }

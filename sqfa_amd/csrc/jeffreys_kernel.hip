@@ -8,9 +8,9 @@
 // log_euclidean_kernel.hip follows).  A pair costs O(m^2): no per-pair factorisation.
 //
 // Three stages on the caller's stream:
-//   1. jeffreys_precision_kernel: P_c by Cholesky and in-place triangular inverse, one 64-thread workgroup per class, double
-//      inside; P_c is written in the dtype, exactly symmetric (one value per unordered index pair).  A pivot that is not
-//      positive gives a NaN matrix.
+//   1. spd_inverse_kernel (spd_class.hip, the per-class factor stage shared with stein_kernel.hip): P_c by Cholesky and
+//      in-place triangular inverse, one 64-thread workgroup per class, double inside; P_c is written in the dtype, exactly
+//      symmetric (one value per unordered index pair).  A pivot that is not positive gives a NaN matrix.
 //   2. jeffreys_pair_kernel: an N-body pass over the ordered pairs.  A 256-thread workgroup owns TI classes i; every class has
 //      NS lane groups of G lanes (TI NS G = 256, a group never leaves its wave).  Lane r of a group holds index r of the
 //      symmetric matrices: the MMAX entries (c, r) of Sigma_i and P_i, and as many accumulators of
@@ -33,11 +33,9 @@
 #include "../../include/sqfa_hip.h"
 #include "class_pair_loss.hpp"
 #include "pair_kernel.hpp"   // group_sum
+#include "spd_class.hpp"     // stage 1
 
 namespace sqfa {
-
-// sqfa_api.hip: the text sqfa_hip_last_error() returns
-void set_last_error(const char* text);
 
 struct JeffParams : PairLossParams {
   const void* mu;     // (n,m) or nullptr
@@ -48,72 +46,6 @@ struct JeffParams : PairLossParams {
   void* gmu;          // (n,m) or nullptr
   int sqrt_mode;
 };
-
-__device__ __forceinline__ float jf_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double jf_sqrt(double x) { return sqrt(x); }
-template <typename T> __device__ __forceinline__ T jf_nan();
-template <> __device__ __forceinline__ float jf_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double jf_nan<double>() { return __builtin_nan(""); }
-
-// ---- stage 1: P_c = Sigma_c^-1 ---------------------------------------------------------------------------------------------
-// One 64-thread workgroup (one wave) per class; thread r owns row r of the lower triangle, held in LDS in double.
-template <typename T>
-__global__ __launch_bounds__(64) void jeffreys_precision_kernel(const T* __restrict__ cov, T* __restrict__ P, int m) {
-  constexpr int LD = 65;
-  __shared__ double a[64 * LD];
-  const int r = threadIdx.x, mm = m * m;
-  const T* S = cov + (size_t)blockIdx.x * mm;
-  T* out = P + (size_t)blockIdx.x * mm;
-  for (int idx = r; idx < mm; idx += 64) {
-    const int rr = idx / m, cc = idx % m;
-    if (cc <= rr) a[rr * LD + cc] = (double)S[idx];
-  }
-  __syncthreads();
-  // Cholesky, right-looking: after step k column k holds L[:, k]
-  bool bad = false;
-  for (int k = 0; k < m; ++k) {
-    const double d = a[k * LD + k];   // the same value in every thread: the exit below is uniform
-    if (!(d > 0.0)) {
-      bad = true;
-      break;
-    }
-    const double root = sqrt(d), inv = 1.0 / root;
-    __syncthreads();
-    if (r == k) a[k * LD + k] = root;
-    if (r > k && r < m) a[r * LD + k] *= inv;
-    __syncthreads();
-    if (r > k && r < m) {
-      const double lrk = a[r * LD + k];
-      for (int c = k + 1; c <= r; ++c) a[r * LD + c] -= lrk * a[c * LD + k];
-    }
-    __syncthreads();
-  }
-  if (bad) {
-    for (int idx = r; idx < mm; idx += 64) out[idx] = jf_nan<T>();
-    return;
-  }
-  // X = L^-1 in place, last column first: X[r][j] L[j][j] = -sum_{k=j+1..r} X[r][k] L[k][j]
-  for (int j = m - 1; j >= 0; --j) {
-    const double xjj = 1.0 / a[j * LD + j];
-    double sum = 0.0;
-    if (r > j && r < m)
-      for (int k = j + 1; k <= r; ++k) sum += a[r * LD + k] * a[k * LD + j];
-    __syncthreads();
-    if (r == j) a[j * LD + j] = xjj;
-    if (r > j && r < m) a[r * LD + j] = -sum * xjj;
-    __syncthreads();
-  }
-  // P = X^T X: thread r computes P[r][b], b <= r, and writes both mirror entries
-  if (r < m) {
-    for (int b = 0; b <= r; ++b) {
-      double acc = 0.0;
-      for (int k = r; k < m; ++k) acc += a[k * LD + r] * a[k * LD + b];
-      const T v = (T)acc;
-      out[r * m + b] = v;
-      out[b * m + r] = v;
-    }
-  }
-}
 
 // ---- stage 2: the pass over the ordered pairs ------------------------------------------------------------------------------
 // Geometry of one row of the dispatch table: G lanes per group, matrices up to MMAX x MMAX (MMAX <= G).
@@ -302,7 +234,7 @@ __global__ __launch_bounds__(256) void jeffreys_pair_kernel(const JeffParams p) 
       if (ivalid && jvalid && j != i) {
         T D, cij;
         if (sqrt_mode) {
-          D = jf_sqrt(J + eps);
+          D = math::sqrt(J + eps);
           cij = clamped ? T(0) : T(0.5) * wij / D;
         } else {
           D = J;
@@ -388,7 +320,7 @@ __global__ __launch_bounds__(256) void jeffreys_pair_kernel(const JeffParams p) 
     p.loss_part[i] = WEIGHTED ? l : p.weight * l;   // weighted: w_ij went into the sum pair by pair
     p.cnt_part[2 * i] = c0;
     p.cnt_part[2 * i + 1] = c1;
-    if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? jf_sqrt(eps) : T(0);   // sqrt(0 + eps), as the torch expression
+    if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? math::sqrt(eps) : T(0);   // sqrt(0 + eps), as the torch expression
   }
   if (!want_grad || !rvalid) return;
   T* gs = static_cast<T*>(p.GS) + (size_t)i * mm + lane;
@@ -469,75 +401,45 @@ static hipError_t dispatch_jeffreys(const JeffParams& p, hipStream_t stream) {
 // workspace: [P (n,m,m) dtype] [GSigma (n,m,m) dtype] [GP (n,m,m) dtype] [Y (n,m,m) double] [partial losses (n) double]
 //            [counts (n,2) int]
 struct JeffLayout {
-  size_t off_p, off_gs, off_gp, off_y, off_loss, off_cnt, total;
+  size_t off_p, off_gs, off_gp, off_y, off_loss, off_cnt, total;   // total 0: no layout for these sizes
 };
-static bool jeffreys_layout(int n, int m, int dtype, JeffLayout* out) {
-  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8, mat = (size_t)n * m * m;
-  JeffLayout w;
-  size_t o = 0;
-  w.off_p = o;    o = align256(o + mat * esz);
-  w.off_gs = o;   o = align256(o + mat * esz);
-  w.off_gp = o;   o = align256(o + mat * esz);
-  w.off_y = o;    o = align256(o + mat * sizeof(double));
-  w.off_loss = o; o = align256(o + (size_t)n * sizeof(double));
-  w.off_cnt = o;  o = align256(o + (size_t)n * 2 * sizeof(int));
-  w.total = o;
-  *out = w;
-  return true;
+static JeffLayout jeffreys_layout(int n, int m, int dtype) {
+  JeffLayout w{};
+  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return w;
+  const size_t mat = (size_t)n * m * m;
+  WorkspaceCursor ws;
+  w.off_p = ws.take(mat * dtype_bytes(dtype));
+  w.off_gs = ws.take(mat * dtype_bytes(dtype));
+  w.off_gp = ws.take(mat * dtype_bytes(dtype));
+  w.off_y = ws.take(mat * sizeof(double));
+  w.off_loss = ws.take((size_t)n * sizeof(double));
+  w.off_cnt = ws.take((size_t)n * 2 * sizeof(int));
+  w.total = ws.at;
+  return w;
 }
 }  // namespace sqfa
 
 using namespace sqfa;
 
-extern "C" size_t sqfa_jeffreys_workspace_bytes(int n, int m, int dtype) {
-  JeffLayout w;
-  return jeffreys_layout(n, m, dtype, &w) ? w.total : 0;
-}
+extern "C" size_t sqfa_jeffreys_workspace_bytes(int n, int m, int dtype) { return jeffreys_layout(n, m, dtype).total; }
 
 extern "C" int sqfa_jeffreys_pairwise_loss(const void* mu, const void* cov, int n, int m, int dtype, int sqrt_mode, double eps,
                                            const void* pair_weights, double uniform_weight, void* loss_out, void* gmu_out,
                                            void* gcov_out, void* dist_out, int* nonfinite_out, void* workspace,
                                            size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  set_last_error("");
-  if (cov == nullptr || n < 2 || m < 1) {
-    set_last_error("sqfa_jeffreys_pairwise_loss: null covariances, n < 2 or m < 1");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
-    set_last_error("sqfa_jeffreys_pairwise_loss: dtype");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (sqrt_mode != 0 && sqrt_mode != 1) {
-    set_last_error("sqfa_jeffreys_pairwise_loss: sqrt_mode outside {0, 1}");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
   // gradients: with means both or neither; without means gcov_out alone
-  if ((mu != nullptr && (gmu_out != nullptr) != (gcov_out != nullptr)) || (mu == nullptr && gmu_out != nullptr)) {
-    set_last_error("sqfa_jeffreys_pairwise_loss: gmu_out and gcov_out go together, and gmu_out needs mu");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (m > 64) {
-    set_last_error("sqfa_jeffreys_pairwise_loss: m > 64");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
-  JeffLayout w;
-  if (!jeffreys_layout(n, m, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) {
-    set_last_error("sqfa_jeffreys_pairwise_loss: workspace is null or smaller than sqfa_jeffreys_workspace_bytes");
-    return SQFA_ERR_WORKSPACE;
-  }
+  const bool grads_ok = mu != nullptr ? (gmu_out != nullptr) == (gcov_out != nullptr) : gmu_out == nullptr;
+  const JeffLayout w = jeffreys_layout(n, m, dtype);
+  const int rc = check_pair_loss_args("sqfa_jeffreys_pairwise_loss", "covariances", cov == nullptr, n, m, dtype,
+                                      sqrt_mode == 0 || sqrt_mode == 1,
+                                      grads_ok ? nullptr : "gmu_out and gcov_out go together, and gmu_out needs mu", w.total,
+                                      "sqfa_jeffreys_workspace_bytes", workspace, workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const bool want_grad = gcov_out != nullptr;
   // 1. per-class precisions
-  if (dtype == SQFA_F32)
-    hipLaunchKernelGGL((jeffreys_precision_kernel<float>), dim3(n), dim3(64), 0, stream, static_cast<const float*>(cov),
-                       reinterpret_cast<float*>(ws + w.off_p), m);
-  else
-    hipLaunchKernelGGL((jeffreys_precision_kernel<double>), dim3(n), dim3(64), 0, stream, static_cast<const double*>(cov),
-                       reinterpret_cast<double*>(ws + w.off_p), m);
-  if (hipGetLastError() != hipSuccess) return SQFA_ERR_LAUNCH;
+  if (launch_spd_inverse(cov, n, m, dtype, ws + w.off_p, nullptr, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   // 2. the pass over the ordered pairs
   JeffParams p{};
   p.mu = mu;
@@ -549,17 +451,16 @@ extern "C" int sqfa_jeffreys_pairwise_loss(const void* mu, const void* cov, int 
   p.sqrt_mode = sqrt_mode;
   fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + w.off_loss),
                         reinterpret_cast<int*>(ws + w.off_cnt));
-  const hipError_t e = dtype == SQFA_F32 ? dispatch_jeffreys<float>(p, stream) : dispatch_jeffreys<double>(p, stream);
-  if (e != hipSuccess) return SQFA_ERR_LAUNCH;
+  if (dispatch_dtype(dtype, [&](auto t) { return dispatch_jeffreys<decltype(t)>(p, stream); }) != hipSuccess)
+    return SQFA_ERR_LAUNCH;
   // 3. the chain rule through the inverse
   if (want_grad) {
-    double* Y = reinterpret_cast<double*>(ws + w.off_y);
-    if (dtype == SQFA_F32)
-      hipLaunchKernelGGL((jeffreys_finish_kernel<float>), dim3(n), dim3(256), 0, stream, static_cast<const float*>(p.P),
-                         static_cast<const float*>(p.GS), static_cast<const float*>(p.GP), Y, static_cast<float*>(gcov_out), m);
-    else
-      hipLaunchKernelGGL((jeffreys_finish_kernel<double>), dim3(n), dim3(256), 0, stream, static_cast<const double*>(p.P),
-                         static_cast<const double*>(p.GS), static_cast<const double*>(p.GP), Y, static_cast<double*>(gcov_out), m);
+    dispatch_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((jeffreys_finish_kernel<T>), dim3(n), dim3(256), 0, stream, static_cast<const T*>(p.P),
+                         static_cast<const T*>(p.GS), static_cast<const T*>(p.GP), reinterpret_cast<double*>(ws + w.off_y),
+                         static_cast<T*>(gcov_out), m);
+    });
     if (hipGetLastError() != hipSuccess) return SQFA_ERR_LAUNCH;
   }
   // 4. loss and counters

@@ -35,9 +35,6 @@ struct LogEucParams : PairLossParams {
   int sqrt_mode;
 };
 
-__device__ __forceinline__ float le_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double le_sqrt(double x) { return sqrt(x); }
-
 // Geometry of one row of the table below: G lanes per group, matrices up to MMAX x MMAX.
 template <typename T, int G_, int MMAX_>
 struct LogEucCfg {
@@ -175,7 +172,7 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
       if (ivalid && j < n && j != i) {
         T D, c;
         if (sqrt_mode) {
-          D = le_sqrt(d2 + eps);
+          D = math::sqrt(d2 + eps);
           c = wij / D;
         } else {
           D = d2;
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(256) void log_euclidean_pair_kernel(const LogEucPar
     p.loss_part[i] = WEIGHTED ? l : p.weight * l;   // weighted: w_ij went into the sum pair by pair
     p.cnt_part[2 * i] = c0;
     p.cnt_part[2 * i + 1] = c1;
-    if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? le_sqrt(eps) : T(0);   // as the reference: sqrt(0 + eps)
+    if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? math::sqrt(eps) : T(0);   // as the reference: sqrt(0 + eps)
   }
   if (!want_grad) return;
   T* gout = static_cast<T*>(p.G) + (size_t)i * mm;
@@ -262,32 +259,31 @@ static hipError_t dispatch_log_euclidean(const LogEucParams& p, hipStream_t stre
 // workspace: [sqfa_spd_function's] [L (n,m,m) dtype] [U (n,m,m) double] [lambda (n,m) double] [G (n,m,m) dtype]
 //            [partial losses (n) double] [counts (n,2) int]
 struct LogEucLayout {
-  size_t spd_bytes, off_l, off_u, off_lam, off_g, off_loss, off_cnt, total;
+  size_t spd_bytes, off_l, off_u, off_lam, off_g, off_loss, off_cnt, total;   // total 0: no layout for these sizes
 };
-static bool log_euclidean_layout(int n, int m, int dtype, LogEucLayout* out) {
-  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
-  LogEucLayout w;
+static LogEucLayout log_euclidean_layout(int n, int m, int dtype) {
+  LogEucLayout w{};
+  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return w;
   w.spd_bytes = sqfa_spd_function_workspace_bytes(n, m, dtype);
-  if (w.spd_bytes == 0) return false;
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8, mat = (size_t)n * m * m;
-  size_t o = align256(w.spd_bytes);
-  w.off_l = o;    o = align256(o + mat * esz);
-  w.off_u = o;    o = align256(o + mat * sizeof(double));
-  w.off_lam = o;  o = align256(o + (size_t)n * m * sizeof(double));
-  w.off_g = o;    o = align256(o + mat * esz);
-  w.off_loss = o; o = align256(o + (size_t)n * sizeof(double));
-  w.off_cnt = o;  o = align256(o + (size_t)n * 2 * sizeof(int));
-  w.total = o;
-  *out = w;
-  return true;
+  if (w.spd_bytes == 0) return w;
+  const size_t mat = (size_t)n * m * m;
+  WorkspaceCursor ws;
+  ws.take(w.spd_bytes);   // sqfa_spd_function's own workspace comes first
+  w.off_l = ws.take(mat * dtype_bytes(dtype));
+  w.off_u = ws.take(mat * sizeof(double));
+  w.off_lam = ws.take((size_t)n * m * sizeof(double));
+  w.off_g = ws.take(mat * dtype_bytes(dtype));
+  w.off_loss = ws.take((size_t)n * sizeof(double));
+  w.off_cnt = ws.take((size_t)n * 2 * sizeof(int));
+  w.total = ws.at;
+  return w;
 }
 }  // namespace sqfa
 
 using namespace sqfa;
 
 extern "C" size_t sqfa_log_euclidean_workspace_bytes(int n, int m, int dtype) {
-  LogEucLayout w;
-  return log_euclidean_layout(n, m, dtype, &w) ? w.total : 0;
+  return log_euclidean_layout(n, m, dtype).total;
 }
 
 extern "C" int sqfa_log_euclidean_pairwise_loss_weighted(const void* S, int n, int m, int dtype, int sqrt_mode, double eps,
@@ -295,18 +291,16 @@ extern "C" int sqfa_log_euclidean_pairwise_loss_weighted(const void* S, int n, i
                                                          void* gradS_out, void* dist_out, int* nonfinite_out,
                                                          void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (S == nullptr || n < 2 || m < 1) return SQFA_ERR_BAD_ARGUMENT;
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) return SQFA_ERR_BAD_ARGUMENT;
-  if (sqrt_mode != 0 && sqrt_mode != 1) return SQFA_ERR_BAD_ARGUMENT;
-  if (m > 64) return SQFA_ERR_UNSUPPORTED_M;
-  LogEucLayout w;
-  if (!log_euclidean_layout(n, m, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) return SQFA_ERR_WORKSPACE;
+  const LogEucLayout w = log_euclidean_layout(n, m, dtype);
+  // (no name: this entry point leaves the text of sqfa_hip_last_error() to sqfa_spd_function)
+  int rc = check_pair_loss_args(nullptr, nullptr, S == nullptr, n, m, dtype, sqrt_mode == 0 || sqrt_mode == 1, nullptr,
+                                w.total, nullptr, workspace, workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   double* U = reinterpret_cast<double*>(ws + w.off_u);
   double* lam = reinterpret_cast<double*>(ws + w.off_lam);
   // 1. L = log S per class (Cholesky, class_eig_kernel, spd_function_kernel), U and lambda kept for the backward
-  int rc = sqfa_spd_function(S, n, m, dtype, SQFA_SPD_LOG, ws + w.off_l, U, lam, ws, w.spd_bytes, stream_);
+  rc = sqfa_spd_function(S, n, m, dtype, SQFA_SPD_LOG, ws + w.off_l, U, lam, ws, w.spd_bytes, stream_);
   if (rc != SQFA_OK) return rc;
   // 2. the pass over the ordered pairs
   LogEucParams p{};
@@ -315,8 +309,8 @@ extern "C" int sqfa_log_euclidean_pairwise_loss_weighted(const void* S, int n, i
   p.sqrt_mode = sqrt_mode;
   fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + w.off_loss),
                         reinterpret_cast<int*>(ws + w.off_cnt));
-  const hipError_t e = dtype == SQFA_F32 ? dispatch_log_euclidean<float>(p, stream) : dispatch_log_euclidean<double>(p, stream);
-  if (e != hipSuccess) return SQFA_ERR_LAUNCH;
+  if (dispatch_dtype(dtype, [&](auto t) { return dispatch_log_euclidean<decltype(t)>(p, stream); }) != hipSuccess)
+    return SQFA_ERR_LAUNCH;
   // 3. d loss / d S = Daleckii-Krein backward of the logarithm on G
   if (gradS_out != nullptr) {
     rc = sqfa_spd_function_backward(U, lam, p.G, n, m, dtype, SQFA_SPD_LOG, gradS_out, stream_);

@@ -6,8 +6,9 @@
 // eigen-decomposition, no means.
 //
 // Three stages on the caller's stream:
-//   1. stein_class_kernel: per class, Cholesky in double: ld_c = logdet S_c (double) and P_c = S_c^-1 in the dtype, exactly
-//      symmetric (the pattern of jeffreys_precision_kernel).  A pivot that is not positive gives ld_c = NaN and a NaN matrix.
+//   1. spd_inverse_kernel (spd_class.hip, the per-class factor stage shared with jeffreys_kernel.hip): per class, Cholesky
+//      in double: ld_c = logdet S_c (double) and P_c = S_c^-1 in the dtype, exactly symmetric.  A pivot that is not positive
+//      gives ld_c = NaN and a NaN matrix.
 //   1b. stein_logdet_kernel: ld_c once more, from the pair pass's own factorisation in the dtype (it replaces stage 1's
 //      value: both sides of S_ij then carry the same rounding).
 //   2. stein_pair_kernel: the pass over the ordered pairs.  A 256-thread workgroup owns ONE class i; its NS = 256 / G lane
@@ -31,11 +32,9 @@
 #include "../../include/sqfa_hip.h"
 #include "class_pair_loss.hpp"
 #include "pair_kernel.hpp"   // group_sum
+#include "spd_class.hpp"     // stage 1
 
 namespace sqfa {
-
-// sqfa_api.hip: the text sqfa_hip_last_error() returns
-void set_last_error(const char* text);
 
 struct SteinParams : PairLossParams {
   const void* S;      // (n,m,m)
@@ -44,14 +43,6 @@ struct SteinParams : PairLossParams {
   double* csum;       // (n) sum_j c_ij
   int sqrt_mode;
 };
-
-__device__ __forceinline__ float st_rsqrt(float x) { return 1.0f / sqrtf(x); }
-__device__ __forceinline__ double st_rsqrt(double x) { return 1.0 / sqrt(x); }
-__device__ __forceinline__ float st_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double st_sqrt(double x) { return sqrt(x); }
-template <typename T> __device__ __forceinline__ T st_nan();
-template <> __device__ __forceinline__ float st_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double st_nan<double>() { return __builtin_nan(""); }
 
 // The value is computed here and now.  x is read only where a gradient is asked for, and without this the compiler moves
 // the forward solve behind that branch and keeps every broadcast of the factorisation alive for it (hundreds of registers).
@@ -67,71 +58,6 @@ template <int G> __device__ __forceinline__ double st_bcast(double v, int k) {
   if constexpr (G == 64)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
   else return __shfl(v, k, G);
-}
-
-// ---- stage 1: ld_c = logdet S_c, P_c = S_c^-1 --------------------------------------------------------------------------------
-// One 64-thread workgroup (one wave) per class; thread r owns row r of the lower triangle, held in LDS in double.
-template <typename T>
-__global__ __launch_bounds__(64) void stein_class_kernel(const T* __restrict__ Sin, T* __restrict__ P, double* __restrict__ ld,
-                                                          int m) {
-  constexpr int LD = 65;
-  __shared__ double a[64 * LD];
-  const int r = threadIdx.x, mm = m * m;
-  const T* S = Sin + (size_t)blockIdx.x * mm;
-  T* out = P + (size_t)blockIdx.x * mm;
-  for (int idx = r; idx < mm; idx += 64) {
-    const int rr = idx / m, cc = idx % m;
-    if (cc <= rr) a[rr * LD + cc] = (double)S[idx];
-  }
-  __syncthreads();
-  // Cholesky, right-looking: after step k column k holds L[:, k]
-  bool bad = false;
-  double logdet = 0.0;
-  for (int k = 0; k < m; ++k) {
-    const double d = a[k * LD + k];   // the same value in every thread: the exit below is uniform
-    if (!(d > 0.0)) {
-      bad = true;
-      break;
-    }
-    logdet += log(d);
-    const double root = sqrt(d), inv = 1.0 / root;
-    __syncthreads();
-    if (r == k) a[k * LD + k] = root;
-    if (r > k && r < m) a[r * LD + k] *= inv;
-    __syncthreads();
-    if (r > k && r < m) {
-      const double lrk = a[r * LD + k];
-      for (int c = k + 1; c <= r; ++c) a[r * LD + c] -= lrk * a[c * LD + k];
-    }
-    __syncthreads();
-  }
-  if (bad) {
-    for (int idx = r; idx < mm; idx += 64) out[idx] = st_nan<T>();
-    if (r == 0) ld[blockIdx.x] = st_nan<double>();
-    return;
-  }
-  if (r == 0) ld[blockIdx.x] = logdet;
-  // X = L^-1 in place, last column first: X[r][j] L[j][j] = -sum_{k=j+1..r} X[r][k] L[k][j]
-  for (int j = m - 1; j >= 0; --j) {
-    const double xjj = 1.0 / a[j * LD + j];
-    double sum = 0.0;
-    if (r > j && r < m)
-      for (int k = j + 1; k <= r; ++k) sum += a[r * LD + k] * a[k * LD + j];
-    __syncthreads();
-    if (r == j) a[j * LD + j] = xjj;
-    if (r > j && r < m) a[r * LD + j] = -sum * xjj;
-    __syncthreads();
-  }
-  // P = X^T X: thread r computes P[r][b], b <= r, and writes both mirror entries
-  if (r < m) {
-    for (int b = 0; b <= r; ++b) {
-      double acc = 0.0;
-      for (int k = r; k < m; ++k) acc += a[k * LD + r] * a[k * LD + b];
-      const T v = (T)acc;
-      out[r * m + b] = v;
-      out[b * m + r] = v;
-    }
-  }
 }
 
 // ---- stage 2: the pass over the ordered pairs ------------------------------------------------------------------------------
@@ -208,7 +134,7 @@ __global__ __launch_bounds__(256) void stein_pair_kernel(const SteinParams p) {
     for (int k = 0; k < MMAX; ++k) {
       __builtin_amdgcn_sched_barrier(0);   // one step's broadcasts in flight, not the whole factorisation's
       const T dk = st_bcast<G>(a[k], k);
-      const T rinv = st_rsqrt(dk);   // 1 / U[k][k]; NaN for a negative pivot, inf for a zero one
+      const T rinv = math::rsqrt(dk);   // 1 / U[k][k]; NaN for a negative pivot, inf for a zero one
       if (lane == k) {
         pivot = dk;
         invd = rinv;
@@ -235,7 +161,7 @@ __global__ __launch_bounds__(256) void stein_pair_kernel(const SteinParams p) {
     if constexpr (WEIGHTED) wij = W[(size_t)i * n + j];
     T D, cij;
     if (sqrt_mode) {
-      D = st_sqrt(Sv + eps);
+      D = math::sqrt(Sv + eps);
       cij = clamped ? T(0) : T(0.5) * wij / D;
     } else {
       D = Sv;
@@ -317,7 +243,7 @@ __global__ __launch_bounds__(256) void stein_pair_kernel(const SteinParams p) {
     p.cnt_part[2 * i] = c0;
     p.cnt_part[2 * i + 1] = c1;
     p.csum[i] = cs;
-    if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? st_sqrt(eps) : T(0);   // sqrt(|0| + eps), as the torch expression
+    if (dist != nullptr) dist[(size_t)i * n + i] = sqrt_mode ? math::sqrt(eps) : T(0);   // sqrt(|0| + eps), as the torch expression
   }
   if constexpr (REG_ACC) {
     if (!want_grad || !rvalid) return;
@@ -356,7 +282,7 @@ __global__ __launch_bounds__(256) void stein_logdet_kernel(const SteinParams p, 
   for (int k = 0; k < MMAX; ++k) {
     __builtin_amdgcn_sched_barrier(0);
     const T dk = st_bcast<G>(a[k], k);
-    const T rinv = st_rsqrt(dk);
+    const T rinv = math::rsqrt(dk);
     if (lane == k) pivot = dk;
     const T lrk = lane > k ? a[k] * rinv : T(0);
 #pragma unroll
@@ -426,71 +352,43 @@ static hipError_t dispatch_stein(const SteinParams& p, hipStream_t stream) {
 // workspace: [P (n,m,m) dtype] [acc (slices,n,m,m) dtype] [ld (n) double] [csum (n) double] [partial losses (n) double]
 //            [counts (n,2) int]
 struct SteinLayout {
-  size_t off_p, off_acc, off_ld, off_csum, off_loss, off_cnt, total;
+  size_t off_p, off_acc, off_ld, off_csum, off_loss, off_cnt, total;   // total 0: no layout for these sizes
 };
-static bool stein_layout(int n, int m, int dtype, SteinLayout* out) {
-  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
-  const size_t esz = dtype == SQFA_F32 ? 4 : 8, mat = (size_t)n * m * m;
-  SteinLayout w;
-  size_t o = 0;
-  w.off_p = o;    o = align256(o + mat * esz);
-  w.off_acc = o;  o = align256(o + stein_slices(m) * mat * esz);
-  w.off_ld = o;   o = align256(o + (size_t)n * sizeof(double));
-  w.off_csum = o; o = align256(o + (size_t)n * sizeof(double));
-  w.off_loss = o; o = align256(o + (size_t)n * sizeof(double));
-  w.off_cnt = o;  o = align256(o + (size_t)n * 2 * sizeof(int));
-  w.total = o;
-  *out = w;
-  return true;
+static SteinLayout stein_layout(int n, int m, int dtype) {
+  SteinLayout w{};
+  if (n < 2 || m < 1 || m > 64 || (dtype != SQFA_F32 && dtype != SQFA_F64)) return w;
+  const size_t mat = (size_t)n * m * m;
+  WorkspaceCursor ws;
+  w.off_p = ws.take(mat * dtype_bytes(dtype));
+  w.off_acc = ws.take(stein_slices(m) * mat * dtype_bytes(dtype));
+  w.off_ld = ws.take((size_t)n * sizeof(double));
+  w.off_csum = ws.take((size_t)n * sizeof(double));
+  w.off_loss = ws.take((size_t)n * sizeof(double));
+  w.off_cnt = ws.take((size_t)n * 2 * sizeof(int));
+  w.total = ws.at;
+  return w;
 }
 }  // namespace sqfa
 
 using namespace sqfa;
 
-extern "C" size_t sqfa_stein_workspace_bytes(int n, int m, int dtype) {
-  SteinLayout w;
-  return stein_layout(n, m, dtype, &w) ? w.total : 0;
-}
+extern "C" size_t sqfa_stein_workspace_bytes(int n, int m, int dtype) { return stein_layout(n, m, dtype).total; }
 
 extern "C" int sqfa_stein_pairwise_loss(const void* S, int n, int m, int dtype, int sqrt_mode, double eps,
                                         const void* pair_weights, double uniform_weight, void* loss_out, void* gradS_out,
                                         void* dist_out, int* nonfinite_out, void* workspace, size_t workspace_bytes,
                                         void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  set_last_error("");
-  if (S == nullptr || n < 2 || m < 1) {
-    set_last_error("sqfa_stein_pairwise_loss: null matrices, n < 2 or m < 1");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
-    set_last_error("sqfa_stein_pairwise_loss: dtype");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (sqrt_mode != 0 && sqrt_mode != 1) {
-    set_last_error("sqfa_stein_pairwise_loss: sqrt_mode outside {0, 1}");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (m > 64) {
-    set_last_error("sqfa_stein_pairwise_loss: m > 64");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
-  SteinLayout w;
-  if (!stein_layout(n, m, dtype, &w)) return SQFA_ERR_UNSUPPORTED_M;
-  if (workspace == nullptr || workspace_bytes < w.total) {
-    set_last_error("sqfa_stein_pairwise_loss: workspace is null or smaller than sqfa_stein_workspace_bytes");
-    return SQFA_ERR_WORKSPACE;
-  }
+  const SteinLayout w = stein_layout(n, m, dtype);
+  const int rc = check_pair_loss_args("sqfa_stein_pairwise_loss", "matrices", S == nullptr, n, m, dtype,
+                                      sqrt_mode == 0 || sqrt_mode == 1, nullptr, w.total, "sqfa_stein_workspace_bytes",
+                                      workspace, workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const bool want_grad = gradS_out != nullptr;
   double* ld = reinterpret_cast<double*>(ws + w.off_ld);
-  // 1. per-class log-determinants and inverses
-  if (dtype == SQFA_F32)
-    hipLaunchKernelGGL((stein_class_kernel<float>), dim3(n), dim3(64), 0, stream, static_cast<const float*>(S),
-                       reinterpret_cast<float*>(ws + w.off_p), ld, m);
-  else
-    hipLaunchKernelGGL((stein_class_kernel<double>), dim3(n), dim3(64), 0, stream, static_cast<const double*>(S),
-                       reinterpret_cast<double*>(ws + w.off_p), ld, m);
-  if (hipGetLastError() != hipSuccess) return SQFA_ERR_LAUNCH;
+  // 1. per-class inverses, and log-determinants (stage 1b writes them again: ld holds defined values whatever the dispatch)
+  if (launch_spd_inverse(S, n, m, dtype, ws + w.off_p, ld, stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   // 2. the pass over the ordered pairs
   SteinParams p{};
   p.S = S;
@@ -500,18 +398,15 @@ extern "C" int sqfa_stein_pairwise_loss(const void* S, int n, int m, int dtype, 
   p.sqrt_mode = sqrt_mode;
   fill_pair_loss_params(p, n, m, eps, pair_weights, uniform_weight, dist_out, reinterpret_cast<double*>(ws + w.off_loss),
                         reinterpret_cast<int*>(ws + w.off_cnt));
-  const hipError_t e = dtype == SQFA_F32 ? dispatch_stein<float>(p, stream) : dispatch_stein<double>(p, stream);
-  if (e != hipSuccess) return SQFA_ERR_LAUNCH;
+  if (dispatch_dtype(dtype, [&](auto t) { return dispatch_stein<decltype(t)>(p, stream); }) != hipSuccess)
+    return SQFA_ERR_LAUNCH;
   // 3. the per-class finish
   if (want_grad) {
-    if (dtype == SQFA_F32)
-      hipLaunchKernelGGL((stein_finish_kernel<float>), dim3(n), dim3(256), 0, stream,
-                         reinterpret_cast<const float*>(ws + w.off_p), static_cast<const float*>(p.acc), stein_slices(m), p.csum,
-                         static_cast<float*>(gradS_out), m);
-    else
-      hipLaunchKernelGGL((stein_finish_kernel<double>), dim3(n), dim3(256), 0, stream,
-                         reinterpret_cast<const double*>(ws + w.off_p), static_cast<const double*>(p.acc), stein_slices(m), p.csum,
-                         static_cast<double*>(gradS_out), m);
+    dispatch_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((stein_finish_kernel<T>), dim3(n), dim3(256), 0, stream, reinterpret_cast<const T*>(ws + w.off_p),
+                         static_cast<const T*>(p.acc), stein_slices(m), p.csum, static_cast<T*>(gradS_out), m);
+    });
     if (hipGetLastError() != hipSuccess) return SQFA_ERR_LAUNCH;
   }
   // 4. loss and counters

@@ -1,6 +1,8 @@
 """Every host-side decision of the pairwise C ABI as a text table: tilings, workspace sizes, and the return code and
-message of each argument rejection.  Needs no GPU (without one the library assumes 256 CUs, the MI355X's count; every
-call below is rejected before it launches anything).  The check is the diff of two runs:
+message of each argument rejection -- the affine-invariant, Bures-Wasserstein and SPD-function entry points, the four fused
+class-pair losses (Gaussian, log-Euclidean, Jeffreys, Stein), the Gaussian class factors and scores.  Needs no GPU (without
+one the library assumes 256 CUs, the MI355X's count; every call below is rejected before it launches anything).  The check is
+the diff of two runs:
 
     SQFA_HIP_LIBRARY=/path/to/other/libsqfa_hip.so python tools/host_decisions.py > a.txt
     python tools/host_decisions.py > b.txt && diff a.txt b.txt
@@ -94,8 +96,116 @@ def rejections(lib):
     report("sqfa_spd_function_backward", "m=65", lib.sqfa_spd_function_backward(ptr, ptr, ptr, 30, 65, 0, 0, ptr, None))
 
 
+CP_N = (1, 2, 1000)
+CP_M = (1, 16, 17, 32, 33, 64, 65)
+CP_QUERIES = ("sqfa_gauss_pairwise_workspace_bytes", "sqfa_log_euclidean_workspace_bytes", "sqfa_jeffreys_workspace_bytes",
+              "sqfa_stein_workspace_bytes")
+
+
+def class_pair_sizes(lib):
+    for n, m, dtype in itertools.product(CP_N, CP_M, (_lib.SQFA_F32, _lib.SQFA_F64, 7)):
+        print(f"class pairs n={n} m={m} dtype={dtype}: " + " ".join(f"{q}={getattr(lib, q)(n, m, dtype)}" for q in CP_QUERIES))
+    for N, C, K, dtype in itertools.product((0, 1, 64, 1000, 100000, 1 << 40), (0, 1, 3, 37, 1000), (0, 1, 16, 17, 64, 65),
+                                            (_lib.SQFA_F32, _lib.SQFA_F64, 7)):
+        print(f"scores N={N} C={C} K={K} dtype={dtype}: ws={lib.sqfa_gauss_scores_workspace_bytes(N, C, K, dtype)}")
+
+
+def class_pair_rejections(lib):
+    """The four fused class-pair losses, the class factors and the class scores: every call is rejected before a launch."""
+    buf = ctypes.create_string_buffer(64)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    BIG = 1 << 40
+
+    def report(fn, name, rc):
+        print(f"{fn} [{name}]: rc={rc} error={lib.sqfa_hip_last_error().decode()!r}")
+
+    # one caller per entry point over the same keywords; `mode` is sqrt_mode, or the Gaussian kind
+    def stein(S=ptr, mu=ptr, n=7, m=16, dtype=0, mode=1, gmu=None, gcov=None, ws=ptr, nbytes=BIG):
+        return lib.sqfa_stein_pairwise_loss(S, n, m, dtype, mode, 1e-6, None, 1.0, ptr, gcov, None, None, ws, nbytes, None)
+
+    def jeffreys(S=ptr, mu=ptr, n=7, m=16, dtype=0, mode=1, gmu=None, gcov=None, ws=ptr, nbytes=BIG):
+        return lib.sqfa_jeffreys_pairwise_loss(mu, S, n, m, dtype, mode, 1e-6, None, 1.0, ptr, gmu, gcov, None, None, ws, nbytes, None)
+
+    def log_euclidean(S=ptr, mu=ptr, n=7, m=16, dtype=0, mode=1, gmu=None, gcov=None, ws=ptr, nbytes=BIG):
+        return lib.sqfa_log_euclidean_pairwise_loss(S, n, m, dtype, mode, 1e-6, 1.0, ptr, gcov, None, None, ws, nbytes, None)
+
+    def log_euclidean_w(S=ptr, mu=ptr, n=7, m=16, dtype=0, mode=1, gmu=None, gcov=None, ws=ptr, nbytes=BIG):
+        return lib.sqfa_log_euclidean_pairwise_loss_weighted(S, n, m, dtype, mode, 1e-6, ptr, 1.0, ptr, gcov, None, None, ws, nbytes, None)
+
+    def gauss(S=ptr, mu=ptr, n=7, m=16, dtype=0, mode=1, gmu=None, gcov=None, ws=ptr, nbytes=BIG):
+        return lib.sqfa_gauss_pairwise_loss(mu, S, n, m, dtype, mode, 1e-6, 1.0, ptr, gmu, gcov, None, None, ws, nbytes, None)
+
+    def gauss_w(S=ptr, mu=ptr, n=7, m=16, dtype=0, mode=1, gmu=None, gcov=None, ws=ptr, nbytes=BIG):
+        return lib.sqfa_gauss_pairwise_loss_weighted(mu, S, n, m, dtype, mode, 1e-6, ptr, 1.0, ptr, gmu, gcov, None, None, ws, nbytes, None)
+
+    entries = {
+        "sqfa_stein_pairwise_loss": (stein, "sqfa_stein_workspace_bytes"),
+        "sqfa_jeffreys_pairwise_loss": (jeffreys, "sqfa_jeffreys_workspace_bytes"),
+        "sqfa_log_euclidean_pairwise_loss": (log_euclidean, "sqfa_log_euclidean_workspace_bytes"),
+        "sqfa_log_euclidean_pairwise_loss_weighted": (log_euclidean_w, "sqfa_log_euclidean_workspace_bytes"),
+        "sqfa_gauss_pairwise_loss": (gauss, "sqfa_gauss_pairwise_workspace_bytes"),
+        "sqfa_gauss_pairwise_loss_weighted": (gauss_w, "sqfa_gauss_pairwise_workspace_bytes"),
+    }
+    # single faults, then several at once: the later ones show the order of the checks (a case that some entry point has
+    # nothing against also has a null workspace)
+    cases = {
+        "null matrices": dict(S=None),
+        "null means": dict(mu=None, ws=None),
+        "n=1": dict(n=1),
+        "m=0": dict(m=0),
+        "bad dtype": dict(dtype=7),
+        "mode=2": dict(mode=2, ws=None),
+        "mode=9": dict(mode=9),
+        "mode=-1": dict(mode=-1),
+        "gmu without gcov": dict(gmu=ptr, ws=None),
+        "gcov without gmu": dict(gcov=ptr, ws=None),
+        "gmu without means": dict(mu=None, gmu=ptr, gcov=ptr, ws=None),
+        "m=65": dict(m=65),
+        "null workspace": dict(ws=None),
+        "no bytes": dict(nbytes=0),
+        "null matrices, bad dtype": dict(S=None, dtype=7),
+        "bad dtype, mode=9": dict(dtype=7, mode=9),
+        "mode=9, gmu without gcov": dict(mode=9, gmu=ptr),
+        "gmu without gcov, m=65": dict(gmu=ptr, m=65),
+        "m=65, null workspace": dict(m=65, ws=None),
+        "bad dtype, m=65, null workspace": dict(dtype=7, m=65, ws=None),
+    }
+    for fn, (call, query) in entries.items():
+        for name, kw in cases.items():
+            report(fn, name, call(**kw))
+        for n, m, dtype in itertools.product(CP_N, CP_M, (_lib.SQFA_F32, _lib.SQFA_F64)):
+            need = getattr(lib, query)(n, m, dtype)
+            report(fn, f"workspace one byte short n={n} m={m} dtype={dtype}", call(n=n, m=m, dtype=dtype, nbytes=max(need, 1) - 1))
+
+    def factors(mu=ptr, cov=ptr, C=3, K=16, dtype=0, W=ptr, offset=ptr, bad=ptr):
+        return lib.sqfa_gauss_class_factors(mu, cov, None, C, K, dtype, W, offset, bad, None)
+
+    for name, kw in {"null covariances": dict(cov=None), "null factors": dict(W=None), "null offsets": dict(offset=None),
+                     "null counter": dict(bad=None), "C=0": dict(C=0), "K=0": dict(K=0), "bad dtype": dict(dtype=7),
+                     "K=65": dict(K=65), "bad dtype, K=65": dict(dtype=7, K=65), "C=0, K=65": dict(C=0, K=65)}.items():
+        report("sqfa_gauss_class_factors", name, factors(**kw))
+
+    def scores(Z=ptr, N=17, W=ptr, offset=ptr, C=3, K=16, dtype=0, argmax=ptr, best=ptr, counter=ptr, ws=ptr, nbytes=BIG):
+        return lib.sqfa_gauss_scores(Z, N, ptr, W, offset, C, K, dtype, None, argmax, best, None, counter, ws, nbytes, None)
+
+    for name, kw in {"null samples": dict(Z=None), "null factors": dict(W=None), "null offsets": dict(offset=None),
+                     "null counter": dict(counter=None), "N=0": dict(N=0), "C=0": dict(C=0), "K=0": dict(K=0),
+                     "bad dtype": dict(dtype=7), "best without argmax": dict(argmax=None), "K=65": dict(K=65),
+                     "too many tiles": dict(N=1 << 40), "too many classes": dict(C=(1 << 31) - 2),
+                     "null workspace": dict(ws=None), "no bytes": dict(nbytes=0),
+                     "bad dtype, best without argmax": dict(dtype=7, argmax=None),
+                     "best without argmax, K=65": dict(argmax=None, K=65), "K=65, null workspace": dict(K=65, ws=None)}.items():
+        report("sqfa_gauss_scores", name, scores(**kw))
+    for N, C, K, dtype in itertools.product((17, 1000), (3, 37), (16, 64), (_lib.SQFA_F32, _lib.SQFA_F64)):
+        need = lib.sqfa_gauss_scores_workspace_bytes(N, C, K, dtype)
+        report("sqfa_gauss_scores", f"workspace one byte short N={N} C={C} K={K} dtype={dtype}",
+               scores(N=N, C=C, K=K, dtype=dtype, nbytes=need - 1))
+
+
 if __name__ == "__main__":
     library = _lib.load()
     print(f"# version {library.sqfa_hip_version()} arch {library.sqfa_hip_arch().decode()} max_dim {library.sqfa_hip_max_dim()}")
     sizes(library)
     rejections(library)
+    class_pair_sizes(library)
+    class_pair_rejections(library)

@@ -526,6 +526,62 @@ int sqfa_gauss_scores(const void *Z, long long N, const void *means, const void 
                       int *nonfinite_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The log-loss of the Gaussian class scores and its gradients (gauss_log_loss_kernel.hip).  In the notation above, with
+ * W_c = L_c^-1, y_nc = W_c (z_n - mu_c), s_nc = -1/2 |y_nc|^2 + offset_c, lse_n = logsumexp_c s_nc and labels y_n in [0, C):
+ *     ll_n = s_{n, y_n} - lse_n  (<= 0),     loss = -1/N sum_n ll_n
+ *     p_nc = exp(s_nc - lse_n),  r_nc = g (p_nc - [c == y_n]) / N       (g: the upstream scalar)
+ *     dloss/dz_n = - sum_c W_c^T (r_nc y_nc),   dloss/dmu_c = W_c^T sum_n r_nc y_nc,
+ *     dloss/dSigma_c = 1/2 W_c^T ( sum_n r_nc (y_nc y_nc^T - I) ) W_c   (symmetric)
+ * Priors enter through offset_c only and get no gradient; a class with offset -inf has p_nc = 0.  With C = 1 the posterior
+ * is 1 by definition: ll_n = 0 and every gradient is 0 exactly.  Both entries run on the caller's stream, allocate,
+ * synchronise and read back nothing, use no float atomics (every sum in a fixed order: bitwise reproducible), and choose
+ * every grid and split from (N, C, K, dtype) alone.  Nothing of size N C or C N K is formed.
+ *
+ * sqfa_gauss_log_loss -- the scores pass (log-sum-exp only), a label pass (one sample per lane, y = W_y (z - mu_y) in
+ *   double) and a one-workgroup reduction.
+ *   Z (N,K) dtype; labels (N) int64; means (C,K) or NULL; W (C,K,K) and offset (C) FLOAT64 as written by
+ *   sqfa_gauss_class_factors
+ *   loss_out (1) dtype: the sum over the samples is accumulated in double; NaN when any flag is non-zero
+ *   label_log_proba_out (N) dtype or NULL: ll_n (NaN for a flagged sample)
+ *   logsumexp_out (N) dtype, required: the backward reads it
+ *   flags_out (3) int32 (the call sets them): samples whose score row holds a NaN, labels outside [0, C), labels whose
+ *   class has offset -inf.  Labels are data: a label is range-checked before anything is addressed with it, an out-of-range
+ *   label is counted and its gathers go to class 0.
+ *   workspace: sqfa_gauss_log_loss_workspace_bytes(N, C, K, dtype) bytes: that of the scores pass and 8 bytes per 64 samples.
+ *
+ * sqfa_gauss_log_loss_backward -- the same inputs, logsumexp (N) as written by the forward call and upstream (1) dtype ON
+ *   THE DEVICE, or NULL for 1.  Each of gradZ_out (N,K), grad_means_out (C,K), grad_cov_out (C,K,K) may be NULL (at least
+ *   one is not; grad_means_out needs means); the outputs are the same bits whichever subset is asked for, and grad_cov_out
+ *   is exactly symmetric.  The r of the labelled class is formed as -g P_n / N with P_n = sum_{c != y_n} p_nc, never as p - 1
+ *   (which is all rounding where the posterior is nearly 1).  gradZ: a workgroup owns 64 samples and a split of the classes,
+ *   recomputes y on the exact MFMA and feeds its accumulators, scaled by r, to the second product W_c^T (r y) as they stand;
+ *   class splits are merged in split order, and the labelled class's term is added per sample (its label range-checked first).
+ *   This pass runs whichever subset is asked for: it yields P_n.  grad_means / grad_cov: a workgroup owns a class and a split of the samples, y^T = (Z - mu)^T W^T with the
+ *   samples on the rows, M_c = sum r y y^T on the MFMA with the samples as the contraction index; the partials
+ *   (sample splits, C, K^2 + K + 1) are summed per class in split order, in double, and W_c^T (.) W_c applied.
+ *   Samples the forward call flagged are the caller's to refuse: they give NaN or meaningless gradients, never a fault.
+ *   workspace: sqfa_gauss_log_loss_backward_workspace_bytes(N, C, K, dtype) bytes, whatever subset is asked for.
+ *
+ * sqfa_gauss_log_loss_layout -- informational: the class splits (and groups of 4 classes per split) of the sample-owned
+ *   pass and the sample splits (and 16-sample tiles per split) of the class-owned pass.
+ * 1 <= K <= 64, C >= 1, N >= 1.  Return SQFA_ERR_BAD_ARGUMENT (null input or required output, sizes < 1, dtype, no gradient
+ * asked for, grad_means_out without means), SQFA_ERR_UNSUPPORTED_M (K > 64, or more than 2^31 - 1 sample tiles),
+ * SQFA_ERR_WORKSPACE, checked in that order; every argument check runs before the first HIP call.  The workspace queries
+ * return 0 for an unsupported shape or dtype.
+ */
+size_t sqfa_gauss_log_loss_workspace_bytes(long long N, int C, int K, int dtype);
+size_t sqfa_gauss_log_loss_backward_workspace_bytes(long long N, int C, int K, int dtype);
+int sqfa_gauss_log_loss_layout(long long N, int C, int K, int dtype, int *class_splits, int *groups_per_split,
+                               int *sample_splits, long long *tiles_per_split);
+int sqfa_gauss_log_loss(const void *Z, const long long *labels, long long N, const void *means, const void *W,
+                        const double *offset, int C, int K, int dtype, void *loss_out, void *label_log_proba_out,
+                        void *logsumexp_out, int *flags_out, void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_gauss_log_loss_backward(const void *Z, const long long *labels, long long N, const void *means, const void *W,
+                                 const double *offset, int C, int K, int dtype, const void *logsumexp,
+                                 const void *upstream, void *gradZ_out, void *grad_means_out, void *grad_cov_out,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the
  * reference (src/sqfa/linalg.py:165-183, 121-141: torch.linalg.eigh + einsum), as used by log_euclidean[_sq]
  * (src/sqfa/distances.py:92-138).  The eigen-decomposition is one-sided Jacobi, run to convergence, on the Cholesky

@@ -121,6 +121,24 @@ PROTOTYPES = {
          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_size_t, ctypes.c_void_p],
     ),
+    "sqfa_gauss_log_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong] + [ctypes.c_int] * 3),
+    "sqfa_gauss_log_loss_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong] + [ctypes.c_int] * 3),
+    "sqfa_gauss_log_loss_layout": (
+        ctypes.c_int,
+        [ctypes.c_longlong] + [ctypes.c_int] * 3 + [_c_int_p] * 3 + [ctypes.POINTER(ctypes.c_longlong)],
+    ),
+    "sqfa_gauss_log_loss": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_size_t, ctypes.c_void_p],
+    ),
+    "sqfa_gauss_log_loss_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
+    ),
     "sqfa_project_scatters": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

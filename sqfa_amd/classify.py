@@ -11,6 +11,9 @@ evaluated in this whitened-difference form (the expanded quadratic z^T P z - 2 b
     GaussianClassifier(means, covariances, priors=None)            scores / predict / log_evidence / predict_log_proba /
                                                                    predict_proba / accuracy of features Z (N, K)
     FeatureClassifier.from_model(model, X, y | data_statistics)    the same of raw points X (N, D), through the model's filters
+    gaussian_log_loss(Z, y, means, covariances, priors=None)       -1/N sum_n log p(y_n | z_n), differentiable in Z, means
+                                                                   and covariances
+    feature_log_loss(model, X, y, ...) / fit_log_loss(model, X, y, ...)   that loss of a model's current filters, and L-BFGS on it
 
 float32 / float64 GPU tensors with K <= 64 run on the native kernels (gauss_scores_kernel.hip): a factor pass once per
 classifier (sqfa_gauss_class_factors) and one pass per batch of samples (sqfa_gauss_scores) that carries the argmax and the
@@ -19,17 +22,28 @@ form anything of size (N, C).  Native results carry no graph.  CPU tensors, othe
 ``NATIVE_CLASS_SCORES = False`` and any input that requires grad while grad is enabled evaluate the same formula as a torch
 expression, chunked over the classes so that its (classes, N, K) temporary stays under ``FALLBACK_BYTES``; that expression is
 differentiable.
+
+The log-loss (``label_log_proba``, ``log_loss``, ``gaussian_log_loss``) runs natively under the same conditions
+(gauss_log_loss_kernel.hip; switch ``NATIVE_LOG_LOSS``), also where an input asks for a gradient: sqfa_gauss_log_loss and
+sqfa_gauss_log_loss_backward form nothing of size (N, C) or (C, N, K), and the forward costs one read from the device (the
+bad-class count and the three flags together), the backward none.  Elsewhere the torch expression applies, chunked over the
+classes for the forward; with a gradient wanted it holds what autograd holds: the (classes, N, K) whitened differences of
+every chunk.
 """
 import math
+import time
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, _native
 from .statistics import ClassPoints, class_statistics
 
-__all__ = ["gaussian_class_scores", "GaussianClassifier", "FeatureClassifier"]
+__all__ = ["gaussian_class_scores", "GaussianClassifier", "FeatureClassifier"]   # the star-import surface stays as it was
+# also public, by their module path: gaussian_log_loss, feature_log_loss, fit_log_loss
 
 NATIVE_CLASS_SCORES = True
+NATIVE_LOG_LOSS = True
 NATIVE_MAX_FEATURES = 64
 # the torch expression's (classes, N, K) temporaries (the differences and the solve's result) stay below this many bytes
 FALLBACK_BYTES = 1 << 28
@@ -69,6 +83,63 @@ def _native_applies(*tensors):
                 and not _grad_wanted(*tensors))
 
 
+def _native_class_factors(mu, cov, log_priors):
+    """sqfa_gauss_class_factors on contiguous tensors without a graph: (W (C,K,K), offset (C,) float64, the number of bad
+    classes as a (1,) int32 device tensor)."""
+    lib = _lib.load()
+    C, K = cov.shape[0], cov.shape[-1]
+    with _native._on_stream(cov.device) as stream:
+        W = torch.empty_like(cov)
+        offset = torch.empty(C, dtype=torch.float64, device=cov.device)
+        bad = torch.empty(1, dtype=torch.int32, device=cov.device)
+        lp = log_priors.contiguous()
+        _lib.check(lib.sqfa_gauss_class_factors(_native._ptr(mu), _native._ptr(cov), _native._ptr(lp), C, K,
+                                                _native._dtype_code(cov), _native._ptr(W), _native._ptr(offset),
+                                                _native._ptr(bad), stream), "sqfa_gauss_class_factors")
+    return W, offset, bad
+
+
+def _native_log_loss(Z, y, mu, W, offset, want_ll=False):
+    """One sqfa_gauss_log_loss call: (loss (1,), ll (N,) | None, logsumexp (N,), flags (3,) int32 on the device: samples
+    with a NaN in their score row, labels outside [0, C), labels on a class of prior 0)."""
+    lib = _lib.load()
+    N, K, C = Z.shape[0], Z.shape[1], W.shape[0]
+    code = _native._dtype_code(Z)
+    with _native._on_stream(Z.device) as stream:
+        ws, nbytes = _native._workspace(lib.sqfa_gauss_log_loss_workspace_bytes, N, C, K, code)
+        loss = torch.empty(1, dtype=Z.dtype, device=Z.device)
+        ll = torch.empty(N, dtype=Z.dtype, device=Z.device) if want_ll else None
+        lse = torch.empty(N, dtype=Z.dtype, device=Z.device)
+        flags = torch.empty(3, dtype=torch.int32, device=Z.device)
+        _lib.check(lib.sqfa_gauss_log_loss(_native._ptr(Z), _native._ptr(y), N, _native._ptr(mu), _native._ptr(W),
+                                           _native._ptr(offset), C, K, code, _native._ptr(loss), _native._ptr(ll),
+                                           _native._ptr(lse), _native._ptr(flags), _native._ptr(ws), nbytes, stream),
+                   "sqfa_gauss_log_loss")
+    return loss, ll, lse, flags
+
+
+def _labels(y, n_samples, device):
+    """(N,) int64 labels on `device`; ValueError for another shape or a dtype that is not an integer."""
+    y = torch.as_tensor(y)
+    if y.is_floating_point() or y.is_complex() or y.dtype == torch.bool or y.shape != (n_samples,):
+        raise ValueError(f"labels must be integers of shape ({n_samples},), got {y.dtype} of shape {tuple(y.shape)}")
+    return y.detach().to(device=device, dtype=torch.int64).contiguous()
+
+
+def _refuse_bad_classes(bad, n_classes):
+    if bad:
+        raise ValueError(f"{bad} of {n_classes} classes are not symmetric positive definite or not finite")
+
+
+def _refuse_labelled(n_nan, n_outside, n_prior0, n_classes):
+    """The refusals of the log-loss, from the three counts of sqfa_gauss_log_loss's flags."""
+    if n_outside:
+        raise ValueError(f"{n_outside} labels are outside [0, {n_classes})")
+    if n_prior0:
+        raise ValueError(f"{n_prior0} labels belong to a class with prior 0")
+    GaussianClassifier._refuse(n_nan)
+
+
 class GaussianClassifier:
     """Quadratic classifier of features from the class Gaussians N(mu_c, Sigma_c) and priors pi_c.
 
@@ -97,8 +168,7 @@ class GaussianClassifier:
             bad = self._native_factors()
         else:
             bad = self._torch_factors()
-        if bad:
-            raise ValueError(f"{bad} of {C} classes are not symmetric positive definite or not finite")
+        _refuse_bad_classes(bad, C)
 
     @property
     def dtype(self):
@@ -110,18 +180,9 @@ class GaussianClassifier:
 
     # ------------------------------------------------------------------ factors
     def _native_factors(self):
-        lib = _lib.load()
         cov = self.covariances.detach().contiguous()
         mu = self.means.detach().contiguous() if self.means is not None else None
-        C, K = self.n_classes, self.n_features
-        with _native._on_stream(cov.device) as stream:
-            W = torch.empty_like(cov)
-            offset = torch.empty(C, dtype=torch.float64, device=cov.device)
-            bad = torch.empty(1, dtype=torch.int32, device=cov.device)
-            lp = self.log_priors.contiguous()
-            _lib.check(lib.sqfa_gauss_class_factors(_native._ptr(mu), _native._ptr(cov), _native._ptr(lp), C, K,
-                                                    _native._dtype_code(cov), _native._ptr(W), _native._ptr(offset),
-                                                    _native._ptr(bad), stream), "sqfa_gauss_class_factors")
+        W, offset, bad = _native_class_factors(mu, cov, self.log_priors)
         self._means_native = mu
         self._factors = (W, offset)
         return int(bad.item())
@@ -242,12 +303,196 @@ class GaussianClassifier:
         self._refuse(n_bad)
         return correct / A.shape[0]
 
+    # ------------------------------------------------------------------ log-loss
+    def _torch_label_log_proba(self, Z, y):
+        """ll_n = score[n, y_n] - logsumexp_c score[n, c] as a torch expression (differentiable), with the refusals of the
+        native pass from one read."""
+        S = self._torch_scores(Z)
+        C = self.n_classes
+        inside = (y >= 0) & (y < C)
+        yc = y.clamp(0, C - 1)
+        prior0 = inside & (self.log_priors[yc] == -math.inf)
+        n_nan, n_outside, n_prior0 = torch.stack((torch.isnan(S).any(1).sum(), (~inside).sum(), prior0.sum())).tolist()
+        _refuse_labelled(n_nan, n_outside, n_prior0, C)
+        return S.gather(1, yc[:, None])[:, 0] - torch.logsumexp(S, 1)
+
+    def _labelled(self, Z, y):
+        """(ll (N,) without a graph, the log-loss as a 0-dim float64 tensor) on whichever path applies."""
+        Z = self._samples(Z).detach()
+        y = _labels(y, Z.shape[0], self.device)
+        if NATIVE_LOG_LOSS and self._factors is not None and Z.is_cuda and Z.dtype in _NATIVE_DTYPES:
+            W, offset = self._factors
+            loss, ll, _, flags = _native_log_loss(Z.contiguous(), y, self._means_native, W, offset, want_ll=True)
+            value, n_nan, n_outside, n_prior0 = torch.cat((loss.double(), flags.double())).tolist()   # one read
+            _refuse_labelled(int(n_nan), int(n_outside), int(n_prior0), self.n_classes)
+            return ll, value
+        with torch.no_grad():
+            ll = self._torch_label_log_proba(Z, y)
+            return ll, -ll.double().mean().item()
+
+    def label_log_proba(self, Z, y):
+        """(N,) log posteriors of the labelled classes, log p(y_n | z_n) <= 0, without a graph: the labelled entries of
+        ``predict_log_proba`` with nothing of size (N, C) formed on the native path.  ValueError, naming the count, for
+        labels that are not (N,) integers, lie outside [0, C) or belong to a class of prior 0, and for samples with a
+        non-finite score row."""
+        return self._labelled(Z, y)[0]
+
+    def log_loss(self, Z, y):
+        """The log-loss -1/N sum_n log p(y_n | z_n), a Python float (one read from the device)."""
+        return self._labelled(Z, y)[1]
+
 
 def gaussian_class_scores(Z, means, covariances, priors=None):
     """(N, C) scores log p(z_n, c) of the samples Z (N, K) under the class Gaussians: means (C, K) or None (zero means),
     covariances (C, K, K), priors None / "uniform" / (C,) non-negative weights.  Differentiable where an input asks for it
     (the torch expression)."""
     return GaussianClassifier(means, covariances, priors).scores(Z)
+
+
+class _GaussLogLoss(torch.autograd.Function):
+    """The native log-loss: the factor pass and sqfa_gauss_log_loss forward (one read: the bad-class count and the three
+    flags), sqfa_gauss_log_loss_backward for whichever of Z, means, covariances asks for a gradient (no read)."""
+
+    @staticmethod
+    def forward(ctx, Z, means, covariances, y, log_priors):
+        Zc, cov = Z.detach().contiguous(), covariances.detach().contiguous()
+        mu = means.detach().contiguous() if means is not None else None
+        W, offset, bad = _native_class_factors(mu, cov, log_priors)
+        loss, _, lse, flags = _native_log_loss(Zc, y, mu, W, offset)
+        n_bad, n_nan, n_outside, n_prior0 = torch.cat((bad, flags)).tolist()
+        _refuse_bad_classes(n_bad, cov.shape[0])
+        _refuse_labelled(n_nan, n_outside, n_prior0, cov.shape[0])
+        ctx.save_for_backward(Zc, y, mu, W, offset, lse)
+        return loss.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        Z, y, mu, W, offset, lse = ctx.saved_tensors
+        want_z, want_mu, want_cov = ctx.needs_input_grad[:3]
+        lib = _lib.load()
+        N, K, C = Z.shape[0], Z.shape[1], W.shape[0]
+        code = _native._dtype_code(Z)
+        with _native._on_stream(Z.device) as stream:
+            ws, nbytes = _native._workspace(lib.sqfa_gauss_log_loss_backward_workspace_bytes, N, C, K, code)
+            up = g.detach().to(Z.dtype).reshape(1).contiguous()   # stays on the device
+            gZ = torch.empty_like(Z) if want_z else None
+            gmu = torch.empty_like(mu) if want_mu and mu is not None else None
+            gcov = torch.empty_like(W) if want_cov else None
+            _lib.check(lib.sqfa_gauss_log_loss_backward(_native._ptr(Z), _native._ptr(y), N, _native._ptr(mu),
+                                                        _native._ptr(W), _native._ptr(offset), C, K, code,
+                                                        _native._ptr(lse), _native._ptr(up), _native._ptr(gZ),
+                                                        _native._ptr(gmu), _native._ptr(gcov), _native._ptr(ws), nbytes,
+                                                        stream), "sqfa_gauss_log_loss_backward")
+        return gZ, gmu, gcov, None, None
+
+
+def gaussian_log_loss(Z, y, means, covariances, priors=None):
+    """The log-loss -1/N sum_n log p(y_n | z_n) of the samples Z (N, K) with labels y (N,) integers under the class
+    Gaussians (means (C, K) or None, covariances (C, K, K), priors as in GaussianClassifier): a 0-dim tensor,
+    differentiable in Z, means and covariances (priors get no gradient).  float32 / float64 tensors on one GPU with K <= 64
+    run on the native kernels, gradients included; elsewhere the torch expression.  Both refuse the same things with a
+    ValueError that names the count: labels that are not (N,) integers, lie outside [0, C) or belong to a class of prior 0,
+    samples with a non-finite score row, classes that are not symmetric positive definite or not finite."""
+    cov = torch.as_tensor(covariances)
+    if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2] or not cov.is_floating_point() or 0 in cov.shape:
+        raise ValueError("covariances must be a floating-point tensor of shape (n_classes, n_features, n_features)")
+    C, K = cov.shape[0], cov.shape[-1]
+    mu = None
+    if means is not None:
+        mu = torch.as_tensor(means).to(device=cov.device, dtype=cov.dtype)
+        if mu.shape != (C, K):
+            raise ValueError(f"means must have shape ({C}, {K}), got {tuple(mu.shape)}")
+    Z = torch.as_tensor(Z)
+    if Z.dim() != 2 or Z.shape[1] != K or Z.shape[0] < 1:
+        raise ValueError(f"samples must have shape (n_samples >= 1, {K}), got {tuple(Z.shape)}")
+    Z = Z.to(device=cov.device, dtype=cov.dtype)
+    y = _labels(y, Z.shape[0], cov.device)
+    if NATIVE_LOG_LOSS and K <= NATIVE_MAX_FEATURES and cov.is_cuda and cov.dtype in _NATIVE_DTYPES:
+        return _GaussLogLoss.apply(Z, mu, cov, y, _log_priors(priors, C, cov.device))
+    clf = GaussianClassifier(mu, cov, priors)
+    return -clf._torch_label_log_proba(Z, y).mean()
+
+
+def _statistics_and_priors(X, y, data_statistics, priors, estimator):
+    """What from_model and feature_log_loss are given, resolved: (data_statistics, priors) with ``class_statistics`` of
+    ``X, y`` where no statistics are given and "empirical" replaced by the class counts of ``y`` or of the ClassPoints."""
+    counts = None
+    if data_statistics is None:
+        if X is None or y is None:
+            raise ValueError("Either data_statistics or X and y must be provided.")
+        data_statistics = class_statistics(X, y, estimator=estimator)
+    if y is not None:
+        counts = torch.bincount(torch.as_tensor(y).long().flatten())
+    elif isinstance(data_statistics, ClassPoints):
+        counts = data_statistics.counts
+    if isinstance(priors, str) and priors == "empirical":
+        if counts is None:
+            raise ValueError("priors='empirical' needs the labels y or a ClassPoints (its class counts)")
+        priors = counts
+    return data_statistics, priors
+
+
+def _class_gaussians(model, data_statistics, regularized):
+    """(means | None, covariances (C,K,K)) of the class Gaussians in the feature space of ``model`` (SQFA: means and
+    covariances; SecondMomentsSQFA: zero means and second moments), with whatever graph the model's methods build."""
+    if hasattr(model, "_feature_statistics"):   # SQFA: the class Gaussians themselves
+        stats = model._feature_statistics(data_statistics, regularized)
+        means, cov = stats["means"], stats["covariances"]
+    else:                                        # SecondMomentsSQFA: zero-mean Gaussians of the second moments
+        means, cov = None, model._feature_scatters(data_statistics, regularized)
+    if cov.dim() == 2:
+        cov = cov[None]
+    return means, cov
+
+
+def _pad_priors(priors, n_classes):
+    if torch.is_tensor(priors) and priors.shape[0] < n_classes:   # labels that stop short of the last class
+        priors = torch.nn.functional.pad(priors, (0, n_classes - priors.shape[0]))
+    return priors
+
+
+def _feature_log_loss(model, X, y, data_statistics, priors, regularized):
+    X = torch.as_tensor(X).to(device=model.filters.device, dtype=model.filters.dtype)
+    means, cov = _class_gaussians(model, data_statistics, regularized)
+    return gaussian_log_loss(model.transform(X), y, means, cov, _pad_priors(priors, cov.shape[0]))
+
+
+def feature_log_loss(model, X, y, data_statistics=None, priors="uniform", regularized=True, estimator="empirical"):
+    """The log-loss of the labelled points X (N, D), y (N,) under the class Gaussians in the feature space of the model's
+    CURRENT filters, differentiable in the model's parameters: Z = model.transform(X) and the class Gaussians chosen as
+    ``FeatureClassifier.from_model`` chooses them (``data_statistics``: a dict, a ClassPoints, for SecondMomentsSQFA a
+    (C,D,D) tensor; None: class_statistics of ``X, y`` with ``estimator``), with the graph kept."""
+    data_statistics, priors = _statistics_and_priors(X, y, data_statistics, priors, estimator)
+    return _feature_log_loss(model, X, y, data_statistics, priors, regularized)
+
+
+def fit_log_loss(model, X, y, data_statistics=None, priors="uniform", max_epochs=50, lr=0.1, atol=1e-6, **lbfgs_kwargs):
+    """Refine the model's filters by L-BFGS on ``feature_log_loss`` (the Gaussian-likelihood objective; SQFA filters are its
+    natural starting point).  The statistics are built once; the closure is eager.  Stops as the model's fit does: when the
+    loss changes by less than ``atol`` for three consecutive epochs.  Extra keyword arguments go to torch.optim.LBFGS.
+    Returns (losses, times), one entry per epoch."""
+    data_statistics, priors = _statistics_and_priors(X, y, data_statistics, priors, "empirical")
+    optimizer = torch.optim.LBFGS(list(model.parameters()), lr=lr, **lbfgs_kwargs)
+
+    def closure():
+        optimizer.zero_grad()
+        loss = _feature_log_loss(model, X, y, data_statistics, priors, True)
+        loss.backward()
+        return loss
+
+    losses, times = [], []
+    start = time.time()
+    previous, streak = 0.0, 0
+    for _ in range(max_epochs):
+        value = optimizer.step(closure).item()
+        times.append(time.time() - start)
+        losses.append(value)
+        streak = streak + 1 if abs(previous - value) < atol else 0
+        previous = value
+        if streak >= 3:
+            break
+    return torch.tensor(losses), torch.tensor(times)
 
 
 class FeatureClassifier:
@@ -266,31 +511,12 @@ class FeatureClassifier:
         model's fit takes: a dict, a ClassPoints, or for SecondMomentsSQFA a (C,D,D) tensor).  ``regularized`` adds the
         model's noise_mat, as the closures do.  priors: "uniform" (None), "empirical" (the class counts of ``y`` or of the
         ClassPoints) or (C,) weights."""
-        counts = None
-        if data_statistics is None:
-            if X is None or y is None:
-                raise ValueError("Either data_statistics or X and y must be provided.")
-            data_statistics = class_statistics(X, y, estimator=estimator)
-        if y is not None:
-            counts = torch.bincount(torch.as_tensor(y).long().flatten())
-        elif isinstance(data_statistics, ClassPoints):
-            counts = data_statistics.counts
-        if isinstance(priors, str) and priors == "empirical":
-            if counts is None:
-                raise ValueError("priors='empirical' needs the labels y or a ClassPoints (its class counts)")
-            priors = counts
+        data_statistics, priors = _statistics_and_priors(X, y, data_statistics, priors, estimator)
         with torch.no_grad():
             filters = model.filters.detach().clone()
-            if hasattr(model, "_feature_statistics"):   # SQFA: the class Gaussians themselves
-                stats = model._feature_statistics(data_statistics, regularized)
-                means, cov = stats["means"], stats["covariances"]
-            else:                                        # SecondMomentsSQFA: zero-mean Gaussians of the second moments
-                means, cov = None, model._feature_scatters(data_statistics, regularized)
-            if cov.dim() == 2:
-                cov = cov[None]
-            if torch.is_tensor(priors) and priors.shape[0] < cov.shape[0]:   # labels that stop short of the last class
-                priors = torch.nn.functional.pad(priors, (0, cov.shape[0] - priors.shape[0]))
-            classifier = GaussianClassifier(means.detach() if means is not None else None, cov.detach(), priors)
+            means, cov = _class_gaussians(model, data_statistics, regularized)
+            classifier = GaussianClassifier(means.detach() if means is not None else None, cov.detach(),
+                                            _pad_priors(priors, cov.shape[0]))
         return cls(filters, classifier)
 
     n_classes = property(lambda self: self.classifier.n_classes)
@@ -319,3 +545,9 @@ class FeatureClassifier:
 
     def accuracy(self, X, y):
         return self.classifier.accuracy(self.transform(X), y)
+
+    def label_log_proba(self, X, y):
+        return self.classifier.label_log_proba(self.transform(X), y)
+
+    def log_loss(self, X, y):
+        return self.classifier.log_loss(self.transform(X), y)

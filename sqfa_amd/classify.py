@@ -126,6 +126,28 @@ def _labels(y, n_samples, device):
     return y.detach().to(device=device, dtype=torch.int64).contiguous()
 
 
+def _class_inputs(means, covariances):
+    """(means (C, K) in the covariances' dtype and device | None, covariances (C, K, K)), or ValueError."""
+    cov = torch.as_tensor(covariances)
+    if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2] or not cov.is_floating_point() or 0 in cov.shape:
+        raise ValueError("covariances must be a floating-point tensor of shape (n_classes, n_features, n_features)")
+    C, K = cov.shape[0], cov.shape[-1]
+    mu = None
+    if means is not None:
+        mu = torch.as_tensor(means).to(device=cov.device, dtype=cov.dtype)
+        if mu.shape != (C, K):
+            raise ValueError(f"means must have shape ({C}, {K}), got {tuple(mu.shape)}")
+    return mu, cov
+
+
+def _samples(Z, like):
+    """(N >= 1, K) samples in the dtype and on the device of the covariances `like` (C, K, K), or ValueError."""
+    Z = torch.as_tensor(Z)
+    if Z.dim() != 2 or Z.shape[1] != like.shape[-1] or Z.shape[0] < 1:
+        raise ValueError(f"samples must have shape (n_samples >= 1, {like.shape[-1]}), got {tuple(Z.shape)}")
+    return Z.to(device=like.device, dtype=like.dtype)
+
+
 def _refuse_bad_classes(bad, n_classes):
     if bad:
         raise ValueError(f"{bad} of {n_classes} classes are not symmetric positive definite or not finite")
@@ -150,15 +172,8 @@ class GaussianClassifier:
     """
 
     def __init__(self, means, covariances, priors=None):
-        cov = torch.as_tensor(covariances)
-        if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2] or not cov.is_floating_point() or 0 in cov.shape:
-            raise ValueError("covariances must be a floating-point tensor of shape (n_classes, n_features, n_features)")
+        mu, cov = _class_inputs(means, covariances)
         C, K = cov.shape[0], cov.shape[-1]
-        mu = None
-        if means is not None:
-            mu = torch.as_tensor(means).to(device=cov.device, dtype=cov.dtype)
-            if mu.shape != (C, K):
-                raise ValueError(f"means must have shape ({C}, {K}), got {tuple(mu.shape)}")
         self.n_classes, self.n_features = C, K
         self.means, self.covariances = mu, cov
         self.log_priors = _log_priors(priors, C, cov.device)
@@ -204,12 +219,6 @@ class GaussianClassifier:
         return bad
 
     # ------------------------------------------------------------------ evaluation
-    def _samples(self, Z):
-        Z = torch.as_tensor(Z)
-        if Z.dim() != 2 or Z.shape[1] != self.n_features or Z.shape[0] < 1:
-            raise ValueError(f"samples must have shape (n_samples >= 1, {self.n_features}), got {tuple(Z.shape)}")
-        return Z.to(device=self.device, dtype=self.dtype)
-
     def _use_native(self, Z):
         return self._factors is not None and _native_applies(Z)
 
@@ -258,7 +267,7 @@ class GaussianClassifier:
 
     def _evaluate(self, Z, scores=False, argmax=False, logsumexp=False):
         """(scores, argmax, logsumexp, count of NaN rows as a device tensor) on whichever path applies."""
-        Z = self._samples(Z)
+        Z = _samples(Z, self.covariances)
         if self._use_native(Z):
             return self._native_call(Z, scores, argmax, logsumexp)
         S = self._torch_scores(Z)
@@ -318,7 +327,7 @@ class GaussianClassifier:
 
     def _labelled(self, Z, y):
         """(ll (N,) without a graph, the log-loss as a 0-dim float64 tensor) on whichever path applies."""
-        Z = self._samples(Z).detach()
+        Z = _samples(Z, self.covariances).detach()
         y = _labels(y, Z.shape[0], self.device)
         if NATIVE_LOG_LOSS and self._factors is not None and Z.is_cuda and Z.dtype in _NATIVE_DTYPES:
             W, offset = self._factors
@@ -394,19 +403,9 @@ def gaussian_log_loss(Z, y, means, covariances, priors=None):
     run on the native kernels, gradients included; elsewhere the torch expression.  Both refuse the same things with a
     ValueError that names the count: labels that are not (N,) integers, lie outside [0, C) or belong to a class of prior 0,
     samples with a non-finite score row, classes that are not symmetric positive definite or not finite."""
-    cov = torch.as_tensor(covariances)
-    if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2] or not cov.is_floating_point() or 0 in cov.shape:
-        raise ValueError("covariances must be a floating-point tensor of shape (n_classes, n_features, n_features)")
+    mu, cov = _class_inputs(means, covariances)
     C, K = cov.shape[0], cov.shape[-1]
-    mu = None
-    if means is not None:
-        mu = torch.as_tensor(means).to(device=cov.device, dtype=cov.dtype)
-        if mu.shape != (C, K):
-            raise ValueError(f"means must have shape ({C}, {K}), got {tuple(mu.shape)}")
-    Z = torch.as_tensor(Z)
-    if Z.dim() != 2 or Z.shape[1] != K or Z.shape[0] < 1:
-        raise ValueError(f"samples must have shape (n_samples >= 1, {K}), got {tuple(Z.shape)}")
-    Z = Z.to(device=cov.device, dtype=cov.dtype)
+    Z = _samples(Z, cov)
     y = _labels(y, Z.shape[0], cov.device)
     if NATIVE_LOG_LOSS and K <= NATIVE_MAX_FEATURES and cov.is_cuda and cov.dtype in _NATIVE_DTYPES:
         return _GaussLogLoss.apply(Z, mu, cov, y, _log_priors(priors, C, cov.device))

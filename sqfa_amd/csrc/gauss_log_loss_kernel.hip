@@ -18,16 +18,13 @@
 //                         double by a fixed tree.
 //     gl_reduce_kernel    one workgroup: the partial sums in a fixed order, the flags, the loss.
 //   backward, sample-owned (gradZ)
-//     gl_sample_kernel    the geometry of gauss_scores_kernel: workgroup (64 samples, split s of the classes), a lane
-//                         (j = l & 15, q = l >> 4) keeps z[j][4 s + q]; W_c staged through LDS as [row][k].  Per class
-//                         y = W_c (z - mu_c) on the exact MFMA with all row blocks kept: register `reg` of block rb in lane
-//                         (j, q) is y[16 rb + acc_row(q, reg)][j].  |y|^2 is summed over the quarters by a butterfly (the
-//                         same bits in all four, and the bits of the score the scores pass put into lse: the order of that
-//                         pass), r = g exp(s - lse) / N for c != label and 0 for the label (P_n += p), and the second product
-//                         u[k][j] += sum_i W_c[i][k] (r y[i][j]) takes the contraction index i = 16 rb + acc_row(q, reg)
-//                         for step (rb, reg) and quarter q: the accumulators of y are its B operand as they stand, and the
-//                         A operand is read from the same LDS copy of W_c, rows on the quarters.  The zero blocks of W_c
-//                         are skipped in both products.
+//     gl_sample_kernel    the geometry, stage and product of gauss_scores_kernel (gauss_whiten.hpp), all row blocks of y
+//                         kept.  |y|^2 is summed over the quarters by that header's butterfly (the bits of the score the scores
+//                         pass put into lse), r = g exp(s - lse) / N for c != label and 0 for the label (P_n += p), and the
+//                         second product u[k][j] += sum_i W_c[i][k] (r y[i][j]) takes the contraction index
+//                         i = 16 rb + acc_row(q, reg) for step (rb, reg) and quarter q: the accumulators of y are its B
+//                         operand as they stand, and the A operand is read from the same LDS copy of W_c, rows on the
+//                         quarters.  The zero blocks of W_c are skipped in both products.
 //     gl_sample_finish_kernel  one sample per lane: P_n and u summed over the class splits in split order, the labelled
 //                         class's term -g P_n / N W_y^T y on the VALU in double (label range-checked first), gradZ = -u.
 //                         The pass runs whichever gradients are asked for: the class-owned pass reads P_n.
@@ -36,33 +33,28 @@
 //                         16-sample tiles in turn.  y^T = (Z - mu)^T W^T, samples on the rows: register `reg` of column
 //                         block ib in lane (i, q) is y[sample acc_row(q, reg)][16 ib + i], which is the A operand
 //                         (y[.][i]) and, times r, the B operand of M_c += sum_n r y y^T with the samples as the
-//                         contraction index; only the blocks on and below the diagonal are formed.  r comes from a second
-//                         evaluation of y with the features on the rows, as in gl_sample_kernel, so that the score has the
-//                         bits of the scores pass; a cross-lane read brings it to the accumulator rows.  R_c = sum r and
-//                         v_c = sum r y ride along on the VALU.
+//                         contraction index; only the blocks on and below the diagonal are formed (this operand map is this
+//                         kernel's own).  r comes from a second evaluation of y with the features on the rows, by
+//                         gauss_whiten.hpp, so that the score has the bits of the scores pass; a cross-lane read brings it to
+//                         the accumulator rows.  R_c = sum r and v_c = sum r y ride along on the VALU.
 //                         The 4 waves' partials are added in wave order through LDS and written to the slab
 //                         (sample splits, C, K^2 + K + 1).
 //     gl_finish_kernel    one workgroup per class: the slab summed in split order in double (lower triangle, mirrored),
 //                         grad_mu = W^T v, grad_cov = 1/2 W^T (M - R I) W in double, every entry (a, b) computed as the
 //                         entry (max, min): exactly symmetric.
-// Sample tails, class tails and K not a multiple of 4 or 16 are exact zeros in registers / LDS; no address past a tensor's
-// end is formed.
+// gl_label_kernel forms z - mu in T and accumulates in double, gl_sample_finish_kernel forms the difference in double: two
+// arithmetics, each with its bits, so the two VALU passes are not merged with each other or with the MFMA product.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
 
 #include "../../include/sqfa_hip.h"
-#include "class_pair_loss.hpp"   // namespace math, dispatch_dtype, WorkspaceCursor, set_last_error
-#include "proj_traits.hpp"
+#include "class_pair_loss.hpp"   // namespace math, dispatch_dtype, WorkspaceCursor
+#include "gauss_whiten.hpp"
 
 namespace sqfa {
 
-constexpr int GL_THREADS = 256;
-constexpr int GL_ROWS = 64;               // samples per workgroup of the sample-owned pass and of the label pass
-constexpr int GL_KMAX = 64;
-constexpr int GL_MAX_SPLIT = 16;          // class splits of the sample-owned pass at most
-constexpr int GL_TARGET_WG = 1024;        // workgroups asked for before the classes stop being split
 constexpr int GL_CLASS_TARGET_WG = 2048;  // workgroups asked for by the class-owned pass
 constexpr int GL_TILES_MIN = 16;          // 16-sample tiles per workgroup of the class-owned pass before the samples are split
 constexpr int GL_MAX_SAMPLE_SPLIT = 1024;
@@ -90,20 +82,18 @@ template <typename T> struct GlParams {
   T* slab;                              // (sample_splits, C, K K + K + 1): M (lower triangle), v, R
 };
 
-template <typename T> __device__ __forceinline__ T gl_shfl_xor(T v, int mask) { return __shfl_xor(v, mask, 64); }
-
 // ---- forward: the label pass ---------------------------------------------------------------------------------------------------
 
 template <typename T, bool MEANS>
-__global__ __launch_bounds__(GL_ROWS) void gl_label_kernel(const T* __restrict__ Z, const long long* __restrict__ labels,
+__global__ __launch_bounds__(GW_ROWS) void gl_label_kernel(const T* __restrict__ Z, const long long* __restrict__ labels,
                                                            long long N, const T* __restrict__ mu, const T* __restrict__ W,
                                                            const double* __restrict__ offset, int C, int K,
                                                            const T* __restrict__ lse, T* __restrict__ ll_out,
                                                            double* __restrict__ part, int* __restrict__ flags) {
-  __shared__ T sD[GL_KMAX * GL_ROWS];   // [k][lane]: a lane reads back only what it wrote
-  __shared__ double sSum[GL_ROWS];
+  __shared__ T sD[GW_KMAX * GW_ROWS];   // [k][lane]: a lane reads back only what it wrote
+  __shared__ double sSum[GW_ROWS];
   const int tid = threadIdx.x;
-  const long long n = (long long)blockIdx.x * GL_ROWS + tid;
+  const long long n = (long long)blockIdx.x * GW_ROWS + tid;
   const bool live = n < N;
   const long long lab = live ? labels[n] : 0;
   const bool in_range = lab >= 0 && lab < (long long)C;
@@ -116,13 +106,13 @@ __global__ __launch_bounds__(GL_ROWS) void gl_label_kernel(const T* __restrict__
       d = Z[(size_t)n * K + k];
       if constexpr (MEANS) d -= mu[(size_t)c * K + k];
     }
-    sD[k * GL_ROWS + tid] = d;
+    sD[k * GW_ROWS + tid] = d;
   }
   const T* w = W + (size_t)c * K * K;
   double sq = 0.0;
   for (int i = 0; i < K; ++i) {
     double a = 0.0;
-    for (int k = 0; k <= i; ++k) a += (double)w[i * K + k] * (double)sD[k * GL_ROWS + tid];
+    for (int k = 0; k <= i; ++k) a += (double)w[i * K + k] * (double)sD[k * GW_ROWS + tid];
     sq += a * a;
   }
   const T l = live ? lse[n] : T(0);
@@ -134,7 +124,7 @@ __global__ __launch_bounds__(GL_ROWS) void gl_label_kernel(const T* __restrict__
   if (live && ll_out != nullptr) ll_out[n] = (T)ll;
   sSum[tid] = live && !flagged ? ll : 0.0;
   __syncthreads();
-  for (int s = GL_ROWS / 2; s > 0; s >>= 1) {
+  for (int s = GW_ROWS / 2; s > 0; s >>= 1) {
     if (tid < s) sSum[tid] += sSum[tid + s];
     __syncthreads();
   }
@@ -147,15 +137,15 @@ __global__ __launch_bounds__(GL_ROWS) void gl_label_kernel(const T* __restrict__
 }
 
 template <typename T>
-__global__ __launch_bounds__(GL_THREADS) void gl_reduce_kernel(const double* __restrict__ part, long long n_parts, long long N,
+__global__ __launch_bounds__(GW_THREADS) void gl_reduce_kernel(const double* __restrict__ part, long long n_parts, long long N,
                                                                const int* __restrict__ flags, T* __restrict__ loss_out) {
-  __shared__ double sSum[GL_THREADS];
+  __shared__ double sSum[GW_THREADS];
   const int tid = threadIdx.x;
   double s = 0.0;
-  for (long long i = tid; i < n_parts; i += GL_THREADS) s += part[i];
+  for (long long i = tid; i < n_parts; i += GW_THREADS) s += part[i];
   sSum[tid] = s;
   __syncthreads();
-  for (int h = GL_THREADS / 2; h > 0; h >>= 1) {
+  for (int h = GW_THREADS / 2; h > 0; h >>= 1) {
     if (tid < h) sSum[tid] += sSum[tid + h];
     __syncthreads();
   }
@@ -168,71 +158,28 @@ __global__ __launch_bounds__(GL_THREADS) void gl_reduce_kernel(const double* __r
 // ---- backward, sample-owned: gradZ ------------------------------------------------------------------------------------------
 
 template <typename T, int KB, bool MEANS>
-__global__ __launch_bounds__(GL_THREADS) void gl_sample_kernel(const GlParams<T> p) {
+__global__ __launch_bounds__(GW_THREADS) void gl_sample_kernel(const GlParams<T> p) {
   using Tr = ProjTraits<T>;
-  constexpr int CS = KB <= 2 ? 4 : 1;       // classes per stage
-  constexpr int KP = KB * 16;               // padded K
-  constexpr int PITCH = KP + 2;
-  constexpr int PER = CS * KB * KB;         // W values per thread and stage
-  __shared__ T sW[CS * KP * PITCH];
-  __shared__ T sMu[CS * KP];
+  using Stage = WhitenStage<T, KB>;
+  constexpr int CS = Stage::CS, KP = Stage::KP, PITCH = Stage::PITCH;
+  __shared__ T sW[Stage::W_ELEMS];
+  __shared__ T sMu[Stage::MU_ELEMS];
   const int tid = threadIdx.x, l = tid & 63, wave = tid >> 6, q = l >> 4, j = l & 15;
-  const int K = p.K, C = p.C, K4 = (K + 3) / 4, kk = K * K;
+  const int K = p.K, C = p.C, K4 = (K + 3) / 4;
   const long long N = p.N;
-  const long long n = (long long)blockIdx.x * GL_ROWS + wave * 16 + j;
-  const int n_groups = (C + 3) / 4;
-  const int g_lo = blockIdx.y * p.groups_per_split;
-  const int g_hi = g_lo + p.groups_per_split < n_groups ? g_lo + p.groups_per_split : n_groups;
-  const int c_end = 4 * g_hi < C ? 4 * g_hi : C;   // the classes of this split: 4 g_lo .. c_end - 1
-  const size_t w_end = (size_t)c_end * kk;
+  const long long n = (long long)blockIdx.x * GW_ROWS + wave * 16 + j;
+  const auto [g_lo, g_hi, c_end] = whiten_class_range(C, p.groups_per_split, blockIdx.y);
   const bool live = n < N;
 
-  // this lane's sample: z[s] = Z[n][4 s + q], zeros past K and past N
   T z[4 * KB];
-#pragma unroll
-  for (int s = 0; s < 4 * KB; ++s) {
-    const int k = 4 * s + q;
-    const bool ok = live && k < K;
-    const T v = p.Z[ok ? (size_t)n * K + k : 0];
-    z[s] = ok ? v : T(0);
-  }
+  whiten_load_sample<T, KB>(z, p.Z, n, N, K, q);
   const T lse_n = p.lse[live ? n : 0];
   const long long lab = p.labels[live ? n : 0];   // only ever compared with a class index
   const T gs = (p.upstream != nullptr ? p.upstream[0] : T(1)) / (T)N;
 
-  T wv[PER], mv = T(0);
-  auto load = [&](int cb) {
-    const size_t base = (size_t)cb * kk;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int idx = tid + e * GL_THREADS;
-      const bool ok = idx < CS * kk && base + idx < w_end;
-      const T v = p.W[ok ? base + idx : 0];
-      wv[e] = ok ? v : T(0);
-    }
-    if constexpr (MEANS) {
-      const int cls = tid / KP, k = tid % KP;
-      const bool ok = tid < CS * KP && cb + cls < c_end && k < K;
-      const T v = p.mu[ok ? (size_t)(cb + cls) * K + k : 0];
-      mv = ok ? v : T(0);
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int idx = tid + e * GL_THREADS;
-      if (idx < CS * kk) {
-        const int cls = idx / kk, rem = idx % kk;
-        sW[cls * KP * PITCH + (rem / K) * PITCH + rem % K] = wv[e];
-      }
-    }
-    if constexpr (MEANS) {
-      if (tid < CS * KP) sMu[tid] = mv;
-    }
-  };
-
-  for (int i = tid; i < CS * KP * PITCH; i += GL_THREADS) sW[i] = T(0);
-  if (g_lo < g_hi) load(4 * g_lo);
+  Stage stage(c_end, K, tid);
+  stage.zero(sW);
+  if (g_lo < g_hi) stage.template load<MEANS>(p.W, p.mu, 4 * g_lo);
 
   typename Tr::Acc u[KB];
 #pragma unroll
@@ -243,9 +190,9 @@ __global__ __launch_bounds__(GL_THREADS) void gl_sample_kernel(const GlParams<T>
   for (int g = g_lo; g < g_hi; ++g) {
     if constexpr (CS == 4) {
       __syncthreads();   // the previous stage has been consumed (first pass: the zero fill is done)
-      store();
+      stage.template store<MEANS>(sW, sMu);
       __syncthreads();
-      if (g + 1 < g_hi) load(4 * (g + 1));
+      if (g + 1 < g_hi) stage.template load<MEANS>(p.W, p.mu, 4 * (g + 1));
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -253,36 +200,17 @@ __global__ __launch_bounds__(GL_THREADS) void gl_sample_kernel(const GlParams<T>
       if (c >= c_end) continue;   // uniform over the workgroup
       if constexpr (CS == 1) {
         __syncthreads();
-        store();
+        stage.template store<MEANS>(sW, sMu);
         __syncthreads();
-        if (c + 1 < c_end) load(c + 1);
+        if (c + 1 < c_end) stage.template load<MEANS>(p.W, p.mu, c + 1);
       }
       const T* w = sW + (CS == 4 ? t : 0) * KP * PITCH;
-      const T* m = sMu + (CS == 4 ? t : 0) * KP;
       T b[4 * KB];
-#pragma unroll
-      for (int s = 0; s < 4 * KB; ++s) {
-        if constexpr (MEANS) b[s] = s < K4 ? z[s] - m[4 * s + q] : T(0);
-        else b[s] = z[s];
-      }
+      whiten_center<T, KB, MEANS>(b, z, sMu + (CS == 4 ? t : 0) * KP, K4, q);
       typename Tr::Acc y[KB];
-      T sq = T(0);
-#pragma unroll
-      for (int rb = 0; rb < KB; ++rb) {
-        y[rb] = typename Tr::Acc{};
-        if (rb * 16 < K) {
-#pragma unroll
-          for (int s = 0; s < 4 * (rb + 1); ++s)   // the blocks above the diagonal of W are zero: skipped
-            if (s < K4) y[rb] = Tr::mfma(w[(rb * 16 + j) * PITCH + 4 * s + q], b[s], y[rb]);
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) sq += y[rb][reg] * y[rb][reg];
-        }
-      }
-      // the quarters' partial sums by a butterfly: a + b commutes, so all four hold the same bits -- and, paired as the
-      // scores pass pairs them ((q, q ^ 2) first), the bits of the score that went into lse_n: exp(s - lse) is then as
-      // consistent as a softmax of stored scores, which is what keeps r accurate where the posterior is nearly 1
-      sq += gl_shfl_xor(sq, 32);
-      sq += gl_shfl_xor(sq, 16);
+      // the score in the bits that went into lse_n: exp(s - lse) is then as consistent as a softmax of stored scores, which
+      // is what keeps r accurate where the posterior is nearly 1
+      const T sq = whiten_quarters_sum(whiten_product<T, KB>(y, w, b, K, K4, j, q));
       const T off = (T)p.offset[c];
       const T sc = T(-0.5) * sq + off;
       const T post = lab == (long long)c ? T(0) : math::exp(sc - lse_n);   // the labelled class: gl_sample_finish_kernel
@@ -324,11 +252,11 @@ __global__ __launch_bounds__(GL_THREADS) void gl_sample_kernel(const GlParams<T>
 // p - 1, which cancels where the posterior is nearly 1).  The label is range-checked before it addresses anything; an
 // out-of-range label gathers class 0.
 template <typename T, bool MEANS>
-__global__ __launch_bounds__(GL_ROWS) void gl_sample_finish_kernel(const GlParams<T> p) {
-  __shared__ double sY[GL_KMAX * GL_ROWS];   // [k][lane]: a lane reads back only what it wrote
+__global__ __launch_bounds__(GW_ROWS) void gl_sample_finish_kernel(const GlParams<T> p) {
+  __shared__ double sY[GW_KMAX * GW_ROWS];   // [k][lane]: a lane reads back only what it wrote
   const int tid = threadIdx.x, K = p.K;
   const long long N = p.N;
-  const long long n = (long long)blockIdx.x * GL_ROWS + tid;
+  const long long n = (long long)blockIdx.x * GW_ROWS + tid;
   if (n >= N) return;   // no barrier below
   T Ps = p.P_part[n];
   for (int sp = 1; sp < p.class_splits; ++sp) Ps += p.P_part[(size_t)sp * (size_t)N + n];
@@ -339,19 +267,19 @@ __global__ __launch_bounds__(GL_ROWS) void gl_sample_finish_kernel(const GlParam
   for (int k = 0; k < K; ++k) {
     double d = (double)p.Z[(size_t)n * K + k];
     if constexpr (MEANS) d -= (double)p.mu[(size_t)c * K + k];
-    sY[k * GL_ROWS + tid] = d;
+    sY[k * GW_ROWS + tid] = d;
   }
   const T* w = p.W + (size_t)c * K * K;
   for (int i = K - 1; i >= 0; --i) {   // y = W d in place: row i reads d_k, k <= i, and no later row reads slot i
     double a = 0.0;
-    for (int k = 0; k <= i; ++k) a += (double)w[i * K + k] * sY[k * GL_ROWS + tid];
-    sY[i * GL_ROWS + tid] = a;
+    for (int k = 0; k <= i; ++k) a += (double)w[i * K + k] * sY[k * GW_ROWS + tid];
+    sY[i * GW_ROWS + tid] = a;
   }
   const double scale = (double)(p.upstream != nullptr ? p.upstream[0] : T(1)) / (double)N * (double)Ps;
   const size_t total = (size_t)N * K;
   for (int k = 0; k < K; ++k) {
     double t = 0.0;
-    for (int i = k; i < K; ++i) t += (double)w[i * K + k] * sY[i * GL_ROWS + tid];
+    for (int i = k; i < K; ++i) t += (double)w[i * K + k] * sY[i * GW_ROWS + tid];
     const size_t at = (size_t)n * K + k;
     T us = p.u_part[at];
     for (int sp = 1; sp < p.class_splits; ++sp) us += p.u_part[(size_t)sp * total + at];
@@ -362,10 +290,9 @@ __global__ __launch_bounds__(GL_ROWS) void gl_sample_finish_kernel(const GlParam
 // ---- backward, class-owned: grad_means, grad_cov --------------------------------------------------------------------------
 
 template <typename T, int KB, bool MEANS>
-__global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> p) {
+__global__ __launch_bounds__(GW_THREADS) void gl_class_kernel(const GlParams<T> p) {
   using Tr = ProjTraits<T>;
-  constexpr int KP = KB * 16;
-  constexpr int PITCH = KP + 2;
+  constexpr int KP = WhitenStage<T, KB>::KP, PITCH = WhitenStage<T, KB>::PITCH;   // W_c resident, in the stage's image
   constexpr int NB = KB * (KB + 1) / 2;   // blocks of M on and below the diagonal
   __shared__ T sW[KP * PITCH];
   __shared__ T sMu[KP];
@@ -376,7 +303,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> 
   const long long N = p.N;
   const int c = blockIdx.x;
 
-  for (int i = tid; i < KP * PITCH; i += GL_THREADS) {
+  for (int i = tid; i < KP * PITCH; i += GW_THREADS) {
     const int row = i / PITCH, col = i % PITCH;
     const bool ok = row < K && col < K;
     const T v = p.W[ok ? (size_t)c * kk + row * K + col : 0];
@@ -407,13 +334,16 @@ __global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> 
 #pragma unroll 1
   for (long long t = t_lo + wave; t < t_hi; t += 4) {
     const long long n = t * 16 + j;
+    // whiten_load_sample and whiten_center in one statement (the same bits: sMu is zero from K on): through the two helpers
+    // this kernel waits on every mean it reads and loses 7 to 12 % at K > 32 (profiles/gauss_whiten_refactor.txt)
     T b[4 * KB];
 #pragma unroll
     for (int s = 0; s < 4 * KB; ++s) {
       const int k = 4 * s + q;
       const bool ok = n < N && k < K;
       const T zv = p.Z[ok ? (size_t)n * K + k : 0];
-      b[s] = (ok ? zv : T(0)) - (s < K4 ? sMu[k] : T(0));
+      b[s] = ok ? zv : T(0);
+      if constexpr (MEANS) b[s] -= s < K4 ? sMu[k] : T(0);
     }
     // y^T = (Z - mu)^T W^T: register reg of block ib in lane (i, q) is y[sample acc_row(q, reg)][16 ib + i]
     typename Tr::Acc y[KB];
@@ -427,21 +357,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> 
       }
     }
     // r of sample j, with the score in the bits of the scores pass (see gl_sample_kernel): y = W (z - mu) with the features
-    // on the rows once more, squared and summed in that pass's order
-    T sq = T(0);
-#pragma unroll
-    for (int rb = 0; rb < KB; ++rb) {
-      if (rb * 16 < K) {
-        typename Tr::Acc acc = {};
-#pragma unroll
-        for (int s = 0; s < 4 * (rb + 1); ++s)
-          if (s < K4) acc = Tr::mfma(sW[(rb * 16 + j) * PITCH + 4 * s + q], b[s], acc);
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) sq += acc[reg] * acc[reg];
-      }
-    }
-    sq += gl_shfl_xor(sq, 32);
-    sq += gl_shfl_xor(sq, 16);
+    // on the rows once more
+    const T sq = whiten_quarters_sum(whiten_sq_partial<T, KB>(sW, b, K, K4, j, q));
     const bool live = n < N;
     const T lse_n = p.lse[live ? n : 0];
     const long long lab = p.labels[live ? n : 0];   // only ever compared with a class index
@@ -472,11 +389,11 @@ __global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> 
   // the quarters of v and R by a butterfly, then the 4 waves in wave order through LDS (W_c is no longer needed)
 #pragma unroll
   for (int ib = 0; ib < KB; ++ib) {
-    v[ib] += gl_shfl_xor(v[ib], 16);
-    v[ib] += gl_shfl_xor(v[ib], 32);
+    v[ib] += gw_shfl_xor(v[ib], 16);
+    v[ib] += gw_shfl_xor(v[ib], 32);
   }
-  R += gl_shfl_xor(R, 16);
-  R += gl_shfl_xor(R, 32);
+  R += gw_shfl_xor(R, 16);
+  R += gw_shfl_xor(R, 32);
   if (q == 0) {
 #pragma unroll
     for (int ib = 0; ib < KB; ++ib) sV[wave * KP + ib * 16 + j] = v[ib];
@@ -501,7 +418,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> 
     __syncthreads();
   }
   T* out = p.slab + ((size_t)blockIdx.y * C + c) * (size_t)(kk + K + 1);
-  for (int idx = tid; idx < kk; idx += GL_THREADS) {
+  for (int idx = tid; idx < kk; idx += GW_THREADS) {
     const int row = idx / K, col = idx % K;
     if (col <= row) out[idx] = sW[row * PITCH + col];
   }
@@ -511,14 +428,14 @@ __global__ __launch_bounds__(GL_THREADS) void gl_class_kernel(const GlParams<T> 
 
 // one workgroup per class: the slab in split order, grad_mu = W^T v, grad_cov = 1/2 W^T (M - R I) W, in double
 template <typename T>
-__global__ __launch_bounds__(GL_THREADS) void gl_finish_kernel(const GlParams<T> p) {
-  __shared__ double sH[GL_KMAX * GL_KMAX];
-  __shared__ double sv[GL_KMAX];
+__global__ __launch_bounds__(GW_THREADS) void gl_finish_kernel(const GlParams<T> p) {
+  __shared__ double sH[GW_KMAX * GW_KMAX];
+  __shared__ double sv[GW_KMAX];
   __shared__ double sRc;
   const int tid = threadIdx.x, K = p.K, C = p.C, kk = K * K, c = blockIdx.x;
   const size_t per = (size_t)(kk + K + 1);
   const T* W = p.W + (size_t)c * kk;
-  for (int idx = tid; idx < kk + K + 1; idx += GL_THREADS) {
+  for (int idx = tid; idx < kk + K + 1; idx += GW_THREADS) {
     int at = idx;
     if (idx < kk) {
       const int row = idx / K, col = idx % K;
@@ -537,11 +454,11 @@ __global__ __launch_bounds__(GL_THREADS) void gl_finish_kernel(const GlParams<T>
     p.grad_mu[(size_t)c * K + tid] = (T)s;
   }
   if (p.grad_cov == nullptr) return;   // uniform
-  constexpr int PER = GL_KMAX * GL_KMAX / GL_THREADS;
+  constexpr int PER = GW_KMAX * GW_KMAX / GW_THREADS;
   double pv[PER];
 #pragma unroll
   for (int e = 0; e < PER; ++e) {   // P = (M - R I) W
-    const int idx = tid + e * GL_THREADS;
+    const int idx = tid + e * GW_THREADS;
     pv[e] = 0.0;
     if (idx < kk) {
       const int a = idx / K, b = idx % K;
@@ -553,13 +470,13 @@ __global__ __launch_bounds__(GL_THREADS) void gl_finish_kernel(const GlParams<T>
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
-    const int idx = tid + e * GL_THREADS;
+    const int idx = tid + e * GW_THREADS;
     if (idx < kk) sH[idx] = pv[e];
   }
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < PER; ++e) {   // G = W^T P, the entry (a, b) computed as (max, min)
-    const int idx = tid + e * GL_THREADS;
+    const int idx = tid + e * GW_THREADS;
     if (idx < kk) {
       const int a0 = idx / K, b0 = idx % K;
       const int a = a0 >= b0 ? a0 : b0, b = a0 >= b0 ? b0 : a0;
@@ -582,21 +499,11 @@ struct GlLayout {
 };
 
 static bool gl_layout(long long N, int C, int K, int dtype, GlLayout* w) {
-  if (N < 1 || C < 1 || K < 1 || K > GL_KMAX || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
-  const long long blocks = (N + GL_ROWS - 1) / GL_ROWS;
-  if (blocks > (long long)INT_MAX || C > INT_MAX - 3) return false;
-  w->scores_bytes = sqfa_gauss_scores_workspace_bytes(N, C, K, dtype);
-  if (w->scores_bytes == 0) return false;
-  const size_t esz = dtype_bytes(dtype);
   // the sample-owned pass: the class splits of the scores pass
-  const int groups = (C + 3) / 4;
-  long long splits = (GL_TARGET_WG + blocks - 1) / blocks;
-  if (splits > GL_MAX_SPLIT) splits = GL_MAX_SPLIT;
-  if (splits > groups) splits = groups;
-  if (splits < 1) splits = 1;
-  const int per = (int)((groups + splits - 1) / splits);
-  w->groups_per_split = per;
-  w->class_splits = (groups + per - 1) / per;   // no empty split
+  if (!whiten_class_split(N, C, K, dtype, &w->groups_per_split, &w->class_splits)) return false;
+  const long long blocks = (N + GW_ROWS - 1) / GW_ROWS;
+  w->scores_bytes = sqfa_gauss_scores_workspace_bytes(N, C, K, dtype);
+  const size_t esz = dtype_bytes(dtype);
   // the class-owned pass: sample splits while workgroups are wanted, tiles are there and the slab stays small
   const long long tiles = (N + 15) / 16;
   const size_t per_class = ((size_t)K * K + K + 1) * esz;
@@ -628,7 +535,7 @@ static hipError_t run_label_pass(const void* Z, const long long* labels, long lo
                                  const double* offset, int C, int K, void* loss, void* ll, const void* lse, int* flags,
                                  char* ws, const GlLayout& lay, hipStream_t stream) {
   double* part = reinterpret_cast<double*>(ws + lay.off_part);
-  const dim3 grid((unsigned)lay.label_blocks), block(GL_ROWS);
+  const dim3 grid((unsigned)lay.label_blocks), block(GW_ROWS);
   if (mu != nullptr)
     hipLaunchKernelGGL((gl_label_kernel<T, true>), grid, block, 0, stream, static_cast<const T*>(Z), labels, N,
                        static_cast<const T*>(mu), static_cast<const T*>(W), offset, C, K, static_cast<const T*>(lse),
@@ -639,25 +546,9 @@ static hipError_t run_label_pass(const void* Z, const long long* labels, long lo
                        static_cast<T*>(ll), part, flags);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((gl_reduce_kernel<T>), dim3(1), dim3(GL_THREADS), 0, stream, part, lay.label_blocks, N, flags,
+  hipLaunchKernelGGL((gl_reduce_kernel<T>), dim3(1), dim3(GW_THREADS), 0, stream, part, lay.label_blocks, N, flags,
                      static_cast<T*>(loss));
   return hipGetLastError();
-}
-
-template <typename T, int KB>
-static void launch_sample_pass(const GlParams<T>& p, hipStream_t stream) {
-  const dim3 grid((unsigned)((p.N + GL_ROWS - 1) / GL_ROWS), (unsigned)p.class_splits);
-  if (p.mu != nullptr) hipLaunchKernelGGL((gl_sample_kernel<T, KB, true>), grid, dim3(GL_THREADS), 0, stream, p);
-  else hipLaunchKernelGGL((gl_sample_kernel<T, KB, false>), grid, dim3(GL_THREADS), 0, stream, p);
-}
-
-template <typename T, int KB>
-static void launch_class_pass(const GlParams<T>& p, bool class_pass, hipStream_t stream) {
-  if (class_pass) {
-    const dim3 grid((unsigned)p.C, (unsigned)p.sample_splits);
-    if (p.mu != nullptr) hipLaunchKernelGGL((gl_class_kernel<T, KB, true>), grid, dim3(GL_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL((gl_class_kernel<T, KB, false>), grid, dim3(GL_THREADS), 0, stream, p);
-  }
 }
 
 template <typename T>
@@ -688,29 +579,27 @@ static hipError_t run_backward(const void* Z, const long long* labels, long long
   p.slab = reinterpret_cast<T*>(ws + lay.off_slab);
   // the sample-owned pass always runs: it also yields P_n, which the class-owned pass reads (without gradZ it stores no u)
   const bool class_pass = grad_mu != nullptr || grad_cov != nullptr;
-  const int KB = (K + 15) / 16;
-  if (KB == 1) launch_sample_pass<T, 1>(p, stream);
-  else if (KB == 2) launch_sample_pass<T, 2>(p, stream);
-  else if (KB == 3) launch_sample_pass<T, 3>(p, stream);
-  else launch_sample_pass<T, 4>(p, stream);
+  const dim3 sgrid((unsigned)lay.label_blocks, (unsigned)lay.class_splits);
+  dispatch_kb(K, mu != nullptr, [&](auto kb, auto means) {
+    hipLaunchKernelGGL((gl_sample_kernel<T, decltype(kb)::value, decltype(means)::value>), sgrid, dim3(GW_THREADS), 0, stream,
+                       p);
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const dim3 fgrid((unsigned)lay.label_blocks), fblock(GL_ROWS);
+  const dim3 fgrid((unsigned)lay.label_blocks), fblock(GW_ROWS);
   if (mu != nullptr) hipLaunchKernelGGL((gl_sample_finish_kernel<T, true>), fgrid, fblock, 0, stream, p);
   else hipLaunchKernelGGL((gl_sample_finish_kernel<T, false>), fgrid, fblock, 0, stream, p);
   e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (KB == 1) launch_class_pass<T, 1>(p, class_pass, stream);
-  else if (KB == 2) launch_class_pass<T, 2>(p, class_pass, stream);
-  else if (KB == 3) launch_class_pass<T, 3>(p, class_pass, stream);
-  else launch_class_pass<T, 4>(p, class_pass, stream);
+  if (e != hipSuccess || !class_pass) return e;
+  const dim3 cgrid((unsigned)C, (unsigned)lay.sample_splits);
+  dispatch_kb(K, mu != nullptr, [&](auto kb, auto means) {
+    hipLaunchKernelGGL((gl_class_kernel<T, decltype(kb)::value, decltype(means)::value>), cgrid, dim3(GW_THREADS), 0, stream,
+                       p);
+  });
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (class_pass) {
-    hipLaunchKernelGGL((gl_finish_kernel<T>), dim3((unsigned)C), dim3(GL_THREADS), 0, stream, p);
-    e = hipGetLastError();
-  }
-  return e;
+  hipLaunchKernelGGL((gl_finish_kernel<T>), dim3((unsigned)C), dim3(GW_THREADS), 0, stream, p);
+  return hipGetLastError();
 }
 
 }  // namespace sqfa
@@ -747,29 +636,14 @@ extern "C" int sqfa_gauss_log_loss(const void* Z, const long long* labels, long 
                                    void* label_log_proba_out, void* logsumexp_out, int* flags_out, void* workspace,
                                    size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  set_last_error("");
-  if (Z == nullptr || labels == nullptr || W == nullptr || offset == nullptr || loss_out == nullptr ||
-      logsumexp_out == nullptr || flags_out == nullptr || N < 1 || C < 1 || K < 1) {
-    set_last_error("sqfa_gauss_log_loss: null samples, labels, factors, offsets, loss, logsumexp or flags, N < 1, C < 1 or K < 1");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
-    set_last_error("sqfa_gauss_log_loss: dtype");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (K > GL_KMAX) {
-    set_last_error("sqfa_gauss_log_loss: K > 64");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
   GlLayout lay;
-  if (!gl_layout(N, C, K, dtype, &lay)) {
-    set_last_error("sqfa_gauss_log_loss: more than 2^31 - 1 sample tiles or classes");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
-  if (workspace == nullptr || workspace_bytes < lay.forward_total) {
-    set_last_error("sqfa_gauss_log_loss: workspace is null or smaller than sqfa_gauss_log_loss_workspace_bytes");
-    return SQFA_ERR_WORKSPACE;
-  }
+  const size_t need = gl_layout(N, C, K, dtype, &lay) ? lay.forward_total : 0;
+  const bool nulls = Z == nullptr || labels == nullptr || W == nullptr || offset == nullptr || loss_out == nullptr ||
+                     logsumexp_out == nullptr || flags_out == nullptr || N < 1 || C < 1 || K < 1;
+  const int rc = check_gauss_args("sqfa_gauss_log_loss", nulls,
+                                  "null samples, labels, factors, offsets, loss, logsumexp or flags, N < 1, C < 1 or K < 1", dtype,
+                                  nullptr, K, true, need, workspace, workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   char* ws = static_cast<char*>(workspace);
   if (hipMemsetAsync(flags_out, 0, 3 * sizeof(int), stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   // the log-sum-exp of every sample: the scores pass, which counts the samples with a NaN in their row into flags[0]
@@ -789,37 +663,17 @@ extern "C" int sqfa_gauss_log_loss_backward(const void* Z, const long long* labe
                                             void* grad_means_out, void* grad_cov_out, void* workspace,
                                             size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  set_last_error("");
-  if (Z == nullptr || labels == nullptr || W == nullptr || offset == nullptr || logsumexp == nullptr || N < 1 || C < 1 ||
-      K < 1) {
-    set_last_error("sqfa_gauss_log_loss_backward: null samples, labels, factors, offsets or logsumexp, N < 1, C < 1 or K < 1");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
-    set_last_error("sqfa_gauss_log_loss_backward: dtype");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (gradZ_out == nullptr && grad_means_out == nullptr && grad_cov_out == nullptr) {
-    set_last_error("sqfa_gauss_log_loss_backward: no gradient asked for");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (means == nullptr && grad_means_out != nullptr) {
-    set_last_error("sqfa_gauss_log_loss_backward: grad_means_out without means");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (K > GL_KMAX) {
-    set_last_error("sqfa_gauss_log_loss_backward: K > 64");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
   GlLayout lay;
-  if (!gl_layout(N, C, K, dtype, &lay)) {
-    set_last_error("sqfa_gauss_log_loss_backward: more than 2^31 - 1 sample tiles or classes");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
-  if (workspace == nullptr || workspace_bytes < (lay.backward_total < 16 ? 16 : lay.backward_total)) {
-    set_last_error("sqfa_gauss_log_loss_backward: workspace is null or smaller than sqfa_gauss_log_loss_backward_workspace_bytes");
-    return SQFA_ERR_WORKSPACE;
-  }
+  const size_t need = gl_layout(N, C, K, dtype, &lay) ? (lay.backward_total < 16 ? 16 : lay.backward_total) : 0;
+  const bool nulls = Z == nullptr || labels == nullptr || W == nullptr || offset == nullptr || logsumexp == nullptr || N < 1 ||
+                     C < 1 || K < 1;
+  const char* own = nullptr;
+  if (gradZ_out == nullptr && grad_means_out == nullptr && grad_cov_out == nullptr) own = "no gradient asked for";
+  else if (means == nullptr && grad_means_out != nullptr) own = "grad_means_out without means";
+  const int rc = check_gauss_args("sqfa_gauss_log_loss_backward", nulls,
+                                  "null samples, labels, factors, offsets or logsumexp, N < 1, C < 1 or K < 1", dtype, own, K, true,
+                                  need, workspace, workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   const hipError_t e = dispatch_dtype(dtype, [&](auto t) {
     return run_backward<decltype(t)>(Z, labels, N, means, W, offset, C, K, logsumexp, upstream, gradZ_out, grad_means_out,
                                      grad_cov_out, static_cast<char*>(workspace), lay, stream);

@@ -11,40 +11,26 @@
 //                         the diagonal; offset_c = -sum log diag L_c - K/2 log 2 pi + log pi_c in double; a class with a
 //                         pivot that is not positive and finite, a mean that is not finite or a log prior that is NaN or
 //                         +inf gets NaN and is counted (integer atomic).
-//   gauss_scores_kernel   workgroup (64 samples, split s of the classes), 4 waves of 16 samples.  A lane (j = l & 15,
-//                         q = l >> 4) keeps z[j][4 s + q] of its sample in registers for the whole kernel.  Classes come in
-//                         groups of 4.  W_c is staged through LDS as [row][k], pitch 16 KB + 2 (rows on the lanes: banks
-//                         all distinct, see class_points_kernel.hip), the next stage's global loads in flight during the
-//                         MFMAs: 4 classes per stage up to K = 32, one class per stage above (34 KB of LDS at most).  Per
-//                         class y = W_c (z - mu_c) on the exact MFMA: A[i][k] = W_c[i][k], B[k][j] = (z_j - mu_c)[k], the
-//                         16 x 16 blocks of W_c above the diagonal skipped; a lane squares and sums its 4 rows of every row
-//                         block.  The 4 classes' partial sums are then reduced ACROSS the 4 lane quarters and transposed in
-//                         3 cross-lane moves, so that lane (j, q) holds the full sum of class 4 g + q: one score, one
-//                         compare and one exp per lane and group.  Every lane carries (max, index) and (max, sum exp) of
-//                         its classes; the quarters are merged by a butterfly at the end (both partners compute the same
-//                         bits: max and a + b commute).
+//   gauss_scores_kernel   workgroup (64 samples, split s of the classes) in the geometry of gauss_whiten.hpp, which has the
+//                         stage of W_c, the product y = W_c (z - mu_c) and the order of its squares.  The 4 classes' partial
+//                         sums of a group are reduced ACROSS the 4 lane quarters and transposed, so that lane (j, q) holds
+//                         the full sum of class 4 g + q: one score, one compare and one exp per lane and group.  Every lane
+//                         carries (max, index) and (max, sum exp) of its classes; the quarters are merged by a butterfly at
+//                         the end (both partners compute the same bits: max and a + b commute).
 //   gauss_merge_kernel    only where the classes are split (few sample tiles): merges the splits' partial (max, index),
 //                         (max, sum exp) in the order s = 0, 1, ...
-// Sample tails, class tails and K not a multiple of 4 or 16 are exact zeros in registers / LDS (a padded class scores
-// -inf by select); no address past a tensor's end is formed.
+// A padded class scores -inf by select.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
-#include <type_traits>
 
 #include "../../include/sqfa_hip.h"
-#include "class_pair_loss.hpp"   // namespace math, dispatch_dtype, WorkspaceCursor, set_last_error
-#include "proj_traits.hpp"
+#include "class_pair_loss.hpp"   // namespace math, dispatch_dtype, WorkspaceCursor
+#include "gauss_whiten.hpp"
 #include "spd_class.hpp"
 
 namespace sqfa {
-
-constexpr int GS_THREADS = 256;
-constexpr int GS_ROWS = 64;         // samples per workgroup
-constexpr int GS_KMAX = 64;
-constexpr int GS_MAX_SPLIT = 16;    // class splits at most
-constexpr int GS_TARGET_WG = 1024;  // workgroups asked for (four per CU) before the classes stop being split
 
 // ---- the factor pass --------------------------------------------------------------------------------------------------------
 
@@ -147,71 +133,24 @@ template <typename T> __device__ __forceinline__ void gs_merge(GsRun<T>& a, T be
   a.nan = a.nan || nan;
 }
 
-template <typename T> __device__ __forceinline__ T gs_shfl_xor(T v, int mask) { return __shfl_xor(v, mask, 64); }
-
 template <typename T, int KB, bool MEANS>
-__global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams<T> p) {
-  using Tr = ProjTraits<T>;
-  constexpr int CS = KB <= 2 ? 4 : 1;       // classes per stage
-  constexpr int KP = KB * 16;               // padded K
-  constexpr int PITCH = KP + 2;
-  constexpr int PER = CS * KB * KB;         // W values per thread and stage: CS K K <= CS KP KP = 256 PER
-  __shared__ T sW[CS * KP * PITCH];
-  __shared__ T sMu[CS * KP];
+__global__ __launch_bounds__(GW_THREADS) void gauss_scores_kernel(const GsParams<T> p) {
+  using Stage = WhitenStage<T, KB>;
+  constexpr int CS = Stage::CS, KP = Stage::KP, PITCH = Stage::PITCH;
+  __shared__ T sW[Stage::W_ELEMS];
+  __shared__ T sMu[Stage::MU_ELEMS];
   const int tid = threadIdx.x, l = tid & 63, wave = tid >> 6, q = l >> 4, j = l & 15;
-  const int K = p.K, C = p.C, K4 = (K + 3) / 4, kk = K * K;
+  const int K = p.K, C = p.C, K4 = (K + 3) / 4;
   const long long N = p.N;
-  const long long n = (long long)blockIdx.x * GS_ROWS + wave * 16 + j;
-  const int n_groups = (C + 3) / 4;
-  const int g_lo = blockIdx.y * p.groups_per_split;
-  const int g_hi = g_lo + p.groups_per_split < n_groups ? g_lo + p.groups_per_split : n_groups;
-  const int c_end = 4 * g_hi < C ? 4 * g_hi : C;   // the classes of this split: 4 g_lo .. c_end - 1
-  const size_t w_end = (size_t)c_end * kk;
+  const long long n = (long long)blockIdx.x * GW_ROWS + wave * 16 + j;
+  const auto [g_lo, g_hi, c_end] = whiten_class_range(C, p.groups_per_split, blockIdx.y);
 
-  // this lane's sample: z[s] = Z[n][4 s + q], zeros past K and past N
   T z[4 * KB];
-#pragma unroll
-  for (int s = 0; s < 4 * KB; ++s) {
-    const int k = 4 * s + q;
-    const bool ok = n < N && k < K;
-    const T v = p.Z[ok ? (size_t)n * K + k : 0];
-    z[s] = ok ? v : T(0);
-  }
+  whiten_load_sample<T, KB>(z, p.Z, n, N, K, q);
 
-  // a stage: the CS classes from cb on.  W through registers into LDS as [class][row][k]; rows and columns K.. stay zero
-  T wv[PER], mv = T(0);
-  auto load = [&](int cb) {
-    const size_t base = (size_t)cb * kk;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int idx = tid + e * GS_THREADS;
-      const bool ok = idx < CS * kk && base + idx < w_end;
-      const T v = p.W[ok ? base + idx : 0];
-      wv[e] = ok ? v : T(0);
-    }
-    if constexpr (MEANS) {
-      const int cls = tid / KP, k = tid % KP;
-      const bool ok = tid < CS * KP && cb + cls < c_end && k < K;
-      const T v = p.mu[ok ? (size_t)(cb + cls) * K + k : 0];
-      mv = ok ? v : T(0);
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int idx = tid + e * GS_THREADS;
-      if (idx < CS * kk) {
-        const int cls = idx / kk, rem = idx % kk;
-        sW[cls * KP * PITCH + (rem / K) * PITCH + rem % K] = wv[e];
-      }
-    }
-    if constexpr (MEANS) {
-      if (tid < CS * KP) sMu[tid] = mv;
-    }
-  };
-
-  for (int i = tid; i < CS * KP * PITCH; i += GS_THREADS) sW[i] = T(0);
-  if (g_lo < g_hi) load(4 * g_lo);
+  Stage stage(c_end, K, tid);
+  stage.zero(sW);
+  if (g_lo < g_hi) stage.template load<MEANS>(p.W, p.mu, 4 * g_lo);
 
   GsRun<T> run;
   run.best = math::neg_inf<T>();
@@ -226,9 +165,9 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
     const T off = c_mine < C ? (T)p.offset[c_mine] : math::neg_inf<T>();
     if constexpr (CS == 4) {
       __syncthreads();   // the previous stage has been consumed (first pass: the zero fill is done)
-      store();
+      stage.template store<MEANS>(sW, sMu);
       __syncthreads();
-      if (g + 1 < g_hi) load(4 * (g + 1));
+      if (g + 1 < g_hi) stage.template load<MEANS>(p.W, p.mu, 4 * (g + 1));
     }
     T part[4];
 #pragma unroll
@@ -237,37 +176,15 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
       if constexpr (CS == 1) {
         if (4 * g + t >= c_end) continue;   // uniform over the workgroup: a class past the end has no stage
         __syncthreads();
-        store();
+        stage.template store<MEANS>(sW, sMu);
         __syncthreads();
-        if (4 * g + t + 1 < c_end) load(4 * g + t + 1);
+        if (4 * g + t + 1 < c_end) stage.template load<MEANS>(p.W, p.mu, 4 * g + t + 1);
       }
-      const T* w = sW + (CS == 4 ? t : 0) * KP * PITCH;
-      const T* m = sMu + (CS == 4 ? t : 0) * KP;
       T b[4 * KB];
-#pragma unroll
-      for (int s = 0; s < 4 * KB; ++s) {
-        if constexpr (MEANS) b[s] = s < K4 ? z[s] - m[4 * s + q] : T(0);
-        else b[s] = z[s];
-      }
-      T sq = T(0);
-#pragma unroll
-      for (int rb = 0; rb < KB; ++rb) {
-        if (rb * 16 < K) {
-          typename Tr::Acc acc = {};
-#pragma unroll
-          for (int s = 0; s < 4 * (rb + 1); ++s)   // the blocks above the diagonal of W are zero: skipped
-            if (s < K4) acc = Tr::mfma(w[(rb * 16 + j) * PITCH + 4 * s + q], b[s], acc);
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) sq += acc[reg] * acc[reg];
-        }
-      }
-      part[t] = sq;
+      whiten_center<T, KB, MEANS>(b, z, sMu + (CS == 4 ? t : 0) * KP, K4, q);
+      part[t] = whiten_sq_partial<T, KB>(sW + (CS == 4 ? t : 0) * KP * PITCH, b, K, K4, j, q);
     }
-    // reduce over the 4 lane quarters and transpose: lane (j, q) ends with the sum of class 4 g + q
-    const bool hi = (q & 2) != 0, odd = (q & 1) != 0;
-    const T r0 = gs_shfl_xor(hi ? part[0] : part[2], 32), r1 = gs_shfl_xor(hi ? part[1] : part[3], 32);
-    const T a0 = (hi ? part[2] : part[0]) + r0, a1 = (hi ? part[3] : part[1]) + r1;
-    const T tot = (odd ? a1 : a0) + gs_shfl_xor(odd ? a0 : a1, 16);
+    const T tot = whiten_quarters_transpose(part, q);   // of class c_mine
     const T sc = c_mine < C ? T(-0.5) * tot + off : math::neg_inf<T>();
     if (c_mine < C) {
       if (p.scores != nullptr && n < N) p.scores[(size_t)n * C + c_mine] = sc;
@@ -278,7 +195,7 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
   // merge the quarters: a butterfly, the same bits in both partners
 #pragma unroll
   for (int mask = 16; mask <= 32; mask *= 2) {
-    const T ob = gs_shfl_xor(run.best, mask), om = gs_shfl_xor(run.m, mask), os = gs_shfl_xor(run.sum, mask);
+    const T ob = gw_shfl_xor(run.best, mask), om = gw_shfl_xor(run.m, mask), os = gw_shfl_xor(run.sum, mask);
     const int oi = __shfl_xor(run.idx, mask, 64), on = __shfl_xor(run.nan ? 1 : 0, mask, 64);
     gs_merge(run, ob, oi, om, os, on != 0);
   }
@@ -304,8 +221,8 @@ __global__ __launch_bounds__(GS_THREADS) void gauss_scores_kernel(const GsParams
 
 // one thread per sample: the splits' partial reductions in the order s = 0, 1, ...
 template <typename T>
-__global__ __launch_bounds__(GS_THREADS) void gauss_merge_kernel(const GsParams<T> p) {
-  const long long n = (long long)blockIdx.x * GS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GW_THREADS) void gauss_merge_kernel(const GsParams<T> p) {
+  const long long n = (long long)blockIdx.x * GW_THREADS + threadIdx.x;
   bool nan = false;
   if (n < p.N) {
     GsRun<T> run;
@@ -336,18 +253,7 @@ struct GsLayout {
 };
 
 static bool gs_layout(long long N, int C, int K, int dtype, GsLayout* w) {
-  if (N < 1 || C < 1 || K < 1 || K > GS_KMAX || (dtype != SQFA_F32 && dtype != SQFA_F64)) return false;
-  const long long tiles = (N + GS_ROWS - 1) / GS_ROWS;
-  if (tiles > (long long)INT_MAX) return false;
-  if (C > INT_MAX - 3) return false;
-  const int groups = (C + 3) / 4;
-  long long splits = (GS_TARGET_WG + tiles - 1) / tiles;
-  if (splits > GS_MAX_SPLIT) splits = GS_MAX_SPLIT;
-  if (splits > groups) splits = groups;
-  if (splits < 1) splits = 1;
-  const int per = (int)((groups + splits - 1) / splits);
-  w->groups_per_split = per;
-  w->splits = (groups + per - 1) / per;   // no empty split
+  if (!whiten_class_split(N, C, K, dtype, &w->groups_per_split, &w->splits)) return false;
   const size_t cells = w->splits > 1 ? (size_t)w->splits * (size_t)N : 0;
   WorkspaceCursor ws{1};   // the four arrays back to back
   w->off_best = ws.take(cells * dtype_bytes(dtype));
@@ -356,12 +262,6 @@ static bool gs_layout(long long N, int C, int K, int dtype, GsLayout* w) {
   w->off_idx = ws.take(cells * sizeof(int));
   w->total = ws.at;
   return true;
-}
-
-template <typename T, int KB>
-static void launch_scores(const GsParams<T>& p, dim3 grid, hipStream_t stream) {
-  if (p.mu != nullptr) hipLaunchKernelGGL((gauss_scores_kernel<T, KB, true>), grid, dim3(GS_THREADS), 0, stream, p);
-  else hipLaunchKernelGGL((gauss_scores_kernel<T, KB, false>), grid, dim3(GS_THREADS), 0, stream, p);
 }
 
 template <typename T>
@@ -391,16 +291,15 @@ static hipError_t run_scores(const void* Z, long long N, const void* mu, const v
   }
   hipError_t e = hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
   if (e != hipSuccess) return e;
-  const dim3 grid((unsigned)((N + GS_ROWS - 1) / GS_ROWS), (unsigned)lay.splits);
-  const int KB = (K + 15) / 16;
-  if (KB == 1) launch_scores<T, 1>(p, grid, stream);
-  else if (KB == 2) launch_scores<T, 2>(p, grid, stream);
-  else if (KB == 3) launch_scores<T, 3>(p, grid, stream);
-  else launch_scores<T, 4>(p, grid, stream);
+  const dim3 grid((unsigned)((N + GW_ROWS - 1) / GW_ROWS), (unsigned)lay.splits);
+  dispatch_kb(K, mu != nullptr, [&](auto kb, auto means) {
+    hipLaunchKernelGGL((gauss_scores_kernel<T, decltype(kb)::value, decltype(means)::value>), grid, dim3(GW_THREADS), 0,
+                       stream, p);
+  });
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (lay.splits > 1) {
-    hipLaunchKernelGGL((gauss_merge_kernel<T>), dim3((unsigned)((N + GS_THREADS - 1) / GS_THREADS)), dim3(GS_THREADS), 0,
+    hipLaunchKernelGGL((gauss_merge_kernel<T>), dim3((unsigned)((N + GW_THREADS - 1) / GW_THREADS)), dim3(GW_THREADS), 0,
                        stream, p);
     e = hipGetLastError();
   }
@@ -420,19 +319,10 @@ extern "C" size_t sqfa_gauss_scores_workspace_bytes(long long N, int C, int K, i
 extern "C" int sqfa_gauss_class_factors(const void* means, const void* cov, const double* log_priors, int C, int K, int dtype,
                                         void* W_out, double* offset_out, int* bad_out, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  set_last_error("");
-  if (cov == nullptr || W_out == nullptr || offset_out == nullptr || bad_out == nullptr || C < 1 || K < 1) {
-    set_last_error("sqfa_gauss_class_factors: null covariances or outputs, C < 1 or K < 1");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
-    set_last_error("sqfa_gauss_class_factors: dtype");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (K > GS_KMAX) {
-    set_last_error("sqfa_gauss_class_factors: K > 64");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
+  const bool nulls = cov == nullptr || W_out == nullptr || offset_out == nullptr || bad_out == nullptr || C < 1 || K < 1;
+  const int rc = check_gauss_args("sqfa_gauss_class_factors", nulls, "null covariances or outputs, C < 1 or K < 1", dtype,
+                                  nullptr, K, false, 0, nullptr, 0);
+  if (rc != SQFA_OK) return rc;
   if (hipMemsetAsync(bad_out, 0, sizeof(int), stream) != hipSuccess) return SQFA_ERR_LAUNCH;
   dispatch_dtype(dtype, [&](auto t) {
     using T = decltype(t);
@@ -447,32 +337,13 @@ extern "C" int sqfa_gauss_scores(const void* Z, long long N, const void* means, 
                                  void* logsumexp_out, int* nonfinite_out, void* workspace, size_t workspace_bytes,
                                  void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  set_last_error("");
-  if (Z == nullptr || W == nullptr || offset == nullptr || nonfinite_out == nullptr || N < 1 || C < 1 || K < 1) {
-    set_last_error("sqfa_gauss_scores: null samples, factors, offsets or counter, N < 1, C < 1 or K < 1");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (dtype != SQFA_F32 && dtype != SQFA_F64) {
-    set_last_error("sqfa_gauss_scores: dtype");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (best_out != nullptr && argmax_out == nullptr) {
-    set_last_error("sqfa_gauss_scores: best_out without argmax_out");
-    return SQFA_ERR_BAD_ARGUMENT;
-  }
-  if (K > GS_KMAX) {
-    set_last_error("sqfa_gauss_scores: K > 64");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
   GsLayout lay;
-  if (!gs_layout(N, C, K, dtype, &lay)) {
-    set_last_error("sqfa_gauss_scores: more than 2^31 - 1 sample tiles or classes");
-    return SQFA_ERR_UNSUPPORTED_M;
-  }
-  if (workspace == nullptr || workspace_bytes < (lay.total < 16 ? 16 : lay.total)) {
-    set_last_error("sqfa_gauss_scores: workspace is null or smaller than sqfa_gauss_scores_workspace_bytes");
-    return SQFA_ERR_WORKSPACE;
-  }
+  const size_t need = gs_layout(N, C, K, dtype, &lay) ? (lay.total < 16 ? 16 : lay.total) : 0;
+  const bool nulls = Z == nullptr || W == nullptr || offset == nullptr || nonfinite_out == nullptr || N < 1 || C < 1 || K < 1;
+  const int rc = check_gauss_args("sqfa_gauss_scores", nulls, "null samples, factors, offsets or counter, N < 1, C < 1 or K < 1",
+                                  dtype, best_out != nullptr && argmax_out == nullptr ? "best_out without argmax_out" : nullptr,
+                                  K, true, need, workspace, workspace_bytes);
+  if (rc != SQFA_OK) return rc;
   const hipError_t e = dispatch_dtype(dtype, [&](auto t) {
     return run_scores<decltype(t)>(Z, N, means, W, offset, C, K, scores_out, argmax_out, best_out, logsumexp_out, nonfinite_out,
                                    static_cast<char*>(workspace), lay, stream);

@@ -103,6 +103,36 @@ def test_layout_query(lib, dtype):
     assert lib.sqfa_gauss_log_loss_layout(1000, 10, 4, dtype, None, None, None, None) == -1
 
 
+# (N, C, K): the shapes of tests/test_gpu_log_loss.py, the timing tools' large cases, and both sides of the class split
+# (fewer and more than 1024 / 16 sample tiles, fewer groups of 4 classes than splits)
+SPLIT_GRID = [(1, 1, 1), (65, 2, 1), (17, 3, 3), (257, 17, 4), (1000, 37, 16), (1000, 37, 17), (513, 130, 5), (300, 9, 33),
+              (200, 5, 64), (100, 4, 48), (2000, 300, 16), (65537, 5, 3), (60000, 1000, 16), (60000, 1000, 32),
+              (60000, 1000, 64), (65536, 300, 16), (65537, 300, 16), (64 * 1023, 5, 3), (64 * 1024, 5, 3), (64 * 63, 1000, 16),
+              (64 * 64, 1000, 16), (64 * 64 + 1, 1000, 16), (64 * 70, 57, 16), (64 * 70, 61, 16), (10 ** 6, 1, 1)]
+
+
+@pytest.mark.parametrize("dtype", [_lib.SQFA_F32, _lib.SQFA_F64])
+def test_class_splits_are_those_of_the_scores_pass(lib, dtype):
+    """The sample-owned backward pass splits the classes as the scores pass does: class_splits of the layout query against
+    the splits the scores workspace implies -- splits * N * (3 * element size + 4) bytes where the classes are split (at
+    least 32 bytes), the 16-byte minimum where they are not."""
+    esz = 4 if dtype == _lib.SQFA_F32 else 8
+    seen = set()
+    for N, C, K in SPLIT_GRID:
+        status, (cs, _, _, _) = _layout(lib, N, C, K, dtype)
+        assert status == 0
+        ws = lib.sqfa_gauss_scores_workspace_bytes(N, C, K, dtype)
+        if ws == 16:
+            implied = 1
+        else:
+            assert ws % (N * (3 * esz + 4)) == 0
+            implied = ws // (N * (3 * esz + 4))
+            assert implied >= 2
+        assert cs == implied, (N, C, K)
+        seen.add(cs > 1)
+    assert seen == {False, True}
+
+
 def _forward(lib, Z=1, labels=1, N=100, means=0, W=1, off=1, C=4, K=8, dtype=_lib.SQFA_F32, loss=1, ll=0, lse=1, flags=1,
              ws=1, ws_bytes=1 << 26):
     p = lambda on: FAKE if on else NULL

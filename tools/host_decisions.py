@@ -1,6 +1,7 @@
 """Every host-side decision of the pairwise C ABI as a text table: tilings, workspace sizes, and the return code and
 message of each argument rejection -- the affine-invariant, Bures-Wasserstein and SPD-function entry points, the four fused
-class-pair losses (Gaussian, log-Euclidean, Jeffreys, Stein), the Gaussian class factors and scores.  Needs no GPU (without
+class-pair losses (Gaussian, log-Euclidean, Jeffreys, Stein), the Gaussian class factors and scores, the Gaussian log-loss
+and its backward (both workspace queries, sqfa_gauss_log_loss_layout, the rejections).  Needs no GPU (without
 one the library assumes 256 CUs, the MI355X's count; every call below is rejected before it launches anything).  The check is
 the diff of two runs:
 
@@ -202,6 +203,78 @@ def class_pair_rejections(lib):
                scores(N=N, C=C, K=K, dtype=dtype, nbytes=need - 1))
 
 
+# (N, C, K) of the Gaussian log-loss: the SHAPES of tests/test_gpu_log_loss.py, the timing tools' large cases, and both
+# sides of every split -- classes split (few sample tiles) and not, samples split and not, the slab bound (many classes,
+# K = 64), the cap of 1024 sample splits (one class, many tiles), and sizes that are refused
+LL_GRID = [(N, C, K) for C, K, N in ((1, 1, 1), (2, 1, 65), (3, 3, 17), (17, 4, 257), (37, 16, 1000), (37, 17, 1000),
+                                     (130, 5, 513), (9, 33, 300), (5, 64, 200), (4, 48, 100), (300, 16, 2000), (5, 3, 65537))] + \
+          [(60000, 1000, 16), (60000, 1000, 32), (60000, 1000, 64), (65536, 300, 16), (65537, 300, 16), (1000, 300, 16),
+           (256, 5, 3), (257, 5, 3), (2000, 5, 3), (1000, 100000, 64), (10 ** 6, 10, 64), (10 ** 6, 1, 1), (10 ** 6, 1000, 16),
+           (64 * 1023, 5, 3), (64 * 1024, 5, 3), (64 * 1024, 1000, 16), (64 * 63, 1000, 16), (64 * 64, 1000, 16),
+           (64 * 64 + 1, 1000, 16), (64 * 70, 57, 16), (64 * 70, 61, 16), (0, 3, 3), (17, 0, 3), (17, 3, 0), (17, 3, 65),
+           (1 << 40, 3, 3), (17, (1 << 31) - 2, 3)]
+
+
+def log_loss_sizes(lib):
+    for (N, C, K), dtype in itertools.product(LL_GRID, (_lib.SQFA_F32, _lib.SQFA_F64, 7)):
+        out = [ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_longlong(-1)]
+        rc = lib.sqfa_gauss_log_loss_layout(N, C, K, dtype, *[ctypes.byref(v) for v in out])
+        print(f"log-loss N={N} C={C} K={K} dtype={dtype}: layout rc={rc} {[v.value for v in out]}"
+              f" forward_ws={lib.sqfa_gauss_log_loss_workspace_bytes(N, C, K, dtype)}"
+              f" backward_ws={lib.sqfa_gauss_log_loss_backward_workspace_bytes(N, C, K, dtype)}"
+              f" scores_ws={lib.sqfa_gauss_scores_workspace_bytes(N, C, K, dtype)}")
+    print(f"log-loss layout [null outputs]: rc={lib.sqfa_gauss_log_loss_layout(17, 3, 3, 0, None, None, None, None)}")
+
+
+def log_loss_rejections(lib):
+    """sqfa_gauss_log_loss and sqfa_gauss_log_loss_backward: every call is rejected before a launch."""
+    buf = ctypes.create_string_buffer(64)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    BIG = 1 << 40
+
+    def report(fn, name, rc):
+        print(f"{fn} [{name}]: rc={rc} error={lib.sqfa_hip_last_error().decode()!r}")
+
+    def forward(Z=ptr, labels=ptr, N=17, mu=ptr, W=ptr, offset=ptr, C=3, K=16, dtype=0, loss=ptr, ll=None, lse=ptr, flags=ptr,
+                ws=ptr, nbytes=BIG):
+        return lib.sqfa_gauss_log_loss(Z, labels, N, mu, W, offset, C, K, dtype, loss, ll, lse, flags, ws, nbytes, None)
+
+    def backward(Z=ptr, labels=ptr, N=17, mu=ptr, W=ptr, offset=ptr, C=3, K=16, dtype=0, lse=ptr, up=None, gZ=ptr, gmu=ptr,
+                 gcov=ptr, ws=ptr, nbytes=BIG):
+        return lib.sqfa_gauss_log_loss_backward(Z, labels, N, mu, W, offset, C, K, dtype, lse, up, gZ, gmu, gcov, ws, nbytes,
+                                                None)
+
+    # single faults, then several at once: the later ones show the order of the checks
+    shared = {"null samples": dict(Z=None), "null labels": dict(labels=None), "null factors": dict(W=None),
+              "null offsets": dict(offset=None), "null logsumexp": dict(lse=None), "N=0": dict(N=0), "N=-1": dict(N=-1),
+              "C=0": dict(C=0), "K=0": dict(K=0), "bad dtype": dict(dtype=7), "K=65": dict(K=65), "K=128": dict(K=128),
+              "too many tiles": dict(N=1 << 40), "too many classes": dict(C=(1 << 31) - 2), "null workspace": dict(ws=None),
+              "no bytes": dict(nbytes=0), "null labels, bad dtype": dict(labels=None, dtype=7),
+              "null labels, K=65": dict(labels=None, K=65), "bad dtype, K=65": dict(dtype=7, K=65),
+              "K=65, null workspace": dict(K=65, ws=None), "K=65, no bytes": dict(K=65, nbytes=0),
+              "too many tiles, null workspace": dict(N=1 << 40, ws=None),
+              "bad dtype, K=65, null workspace": dict(dtype=7, K=65, ws=None)}
+    only_forward = {"null loss": dict(loss=None), "null flags": dict(flags=None), "no means": dict(mu=None, ws=None),
+                    "null loss, bad dtype": dict(loss=None, dtype=7)}
+    only_backward = {"no gradient": dict(gZ=None, gmu=None, gcov=None), "grad_means without means": dict(mu=None),
+                     "no means, no grad_means": dict(mu=None, gmu=None, ws=None), "upstream": dict(up=ptr, ws=None),
+                     "bad dtype, no gradient": dict(dtype=7, gZ=None, gmu=None, gcov=None),
+                     "no gradient, grad_means without means": dict(mu=None, gZ=None, gmu=None, gcov=None),
+                     "no gradient, K=65": dict(gZ=None, gmu=None, gcov=None, K=65),
+                     "grad_means without means, K=65": dict(mu=None, K=65),
+                     "grad_means without means, null workspace": dict(mu=None, ws=None)}
+    for fn, call, query, own in (("sqfa_gauss_log_loss", forward, lib.sqfa_gauss_log_loss_workspace_bytes, only_forward),
+                                 ("sqfa_gauss_log_loss_backward", backward, lib.sqfa_gauss_log_loss_backward_workspace_bytes,
+                                  only_backward)):
+        for name, kw in {**shared, **own}.items():
+            report(fn, name, call(**kw))
+        for (N, C, K), dtype in itertools.product(LL_GRID, (_lib.SQFA_F32, _lib.SQFA_F64)):
+            need = query(N, C, K, dtype)
+            if need:
+                report(fn, f"workspace one byte short N={N} C={C} K={K} dtype={dtype}",
+                       call(N=N, C=C, K=K, dtype=dtype, nbytes=need - 1))
+
+
 if __name__ == "__main__":
     library = _lib.load()
     print(f"# version {library.sqfa_hip_version()} arch {library.sqfa_hip_arch().decode()} max_dim {library.sqfa_hip_max_dim()}")
@@ -209,3 +282,5 @@ if __name__ == "__main__":
     rejections(library)
     class_pair_sizes(library)
     class_pair_rejections(library)
+    log_loss_sizes(library)
+    log_loss_rejections(library)

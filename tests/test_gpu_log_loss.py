@@ -21,6 +21,11 @@ The module asserts through sqfa_gauss_log_loss_layout that both passes run split
 Tolerances, the project's convention: float64 error <= 1e-10 (1 + max |value|) for values and <= 1e-10 max |gradient| per
 gradient tensor; float32 error <= max(1e-5 x that scale, 5 x the error of the same formula in float32 torch with autograd on
 the same inputs), printed beside the observed error and their ratio.
+
+Per entry as well (test_loss_and_gradients_match_the_oracle): every case with C N K^2 <= 2e7 is also held, entry by entry, to
+the long double truth and the bounds of tests/log_loss_hard.py on the same inputs: in float32 the a priori bound of the
+documented arithmetic, in float64 max(1e-10, 5 x the float64 oracle's own error) x the entry's scale.  The two cases at
+(C, K, N) = (300, 16, 2000) are left to the rule above alone: their long double reference is too large for a quick test.
 """
 import ctypes
 import functools
@@ -29,7 +34,9 @@ import numpy as np
 import pytest
 import torch
 
+import classify_hard
 import classify_oracle
+import log_loss_hard
 import log_loss_oracle
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +71,37 @@ def _reference(case, dtype):
         out["torch32"] = log_loss_oracle.evaluate(out["Z"], out["labels"], out["mu"], out["cov"], out["w"], UPSTREAM,
                                                   dtype=torch.float32)
     return out
+
+
+PER_ENTRY_LIMIT = 2e7   # C N K^2 of the long double reference
+
+
+@functools.lru_cache(maxsize=None)
+def _per_entry(case, dtype):
+    """(truth, quantity -> per-entry bound) of log_loss_hard on the inputs of `_reference(case, dtype)`."""
+    ref = _reference(case, dtype)
+    C, K, N = case[:3]
+    ev = log_loss_hard.evaluate(ref["Z"], ref["labels"], ref["mu"], ref["cov"], classify_hard.log_priors(ref["w"], C), UPSTREAM)
+    if dtype == torch.float32:
+        return ev, {q: ev["b_" + q] for q in log_loss_hard.QUANTITIES}
+    # the float64 oracle's own error against the truth, on the same numbers; nothing a kernel returned
+    tol = log_loss_hard.tolerances64(log_loss_hard.yardsticks(ev, ref["ref"]))
+    return ev, {q: t * ev["A_" + q] for q, t in tol.items()}
+
+
+def _check_per_entry(got, case, dtype):
+    ev, bounds = _per_entry(case, dtype)
+    for q, value in got.items():
+        if value is None:
+            continue   # zero means: no gradient of the means
+        want, bound = np.asarray(ev[q]), np.asarray(bounds[q])
+        value = value.detach().double().cpu().numpy() if torch.is_tensor(value) else np.float64(value)
+        err = np.abs(value.astype(np.longdouble).reshape(want.shape) - want)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ratio = np.where(err == 0, 0, err / bound)
+        at = np.unravel_index(int(ratio.argmax()), ratio.shape) if ratio.ndim else ()
+        print(f"{q} per entry: worst err {float(err[at]):.3e} bound {float(bound[at]):.3e} ratio {float(ratio[at]):.3f}")
+        assert ratio[at] <= 1, (q, at, float(err[at]), float(bound[at]))
 
 
 def _device_inputs(ref, dtype, requires_grad=(True, True, True)):
@@ -136,6 +174,9 @@ def test_loss_and_gradients_match_the_oracle(case, dtype):
     assert (ll <= 0).all()
     value = clf.log_loss(Z.detach(), y)
     assert isinstance(value, float) and value == loss.item()
+    if case[0] * case[2] * case[1] ** 2 <= PER_ENTRY_LIMIT:
+        _check_per_entry(dict(loss=loss.item(), ll=ll, gZ=Z.grad, gmu=None if mu is None else mu.grad, gcov=cov.grad), case,
+                         dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])

@@ -24,6 +24,8 @@
  *   sqfa_gauss_class_factors, sqfa_gauss_scores   the step the reference's tutorial judges a fit by
  *       get_qda_accuracy           docs/source/tutorials/digit_processing.md (scikit-learn's
  *                                  QuadraticDiscriminantAnalysis on the features, on the host)
+ *   sqfa_gauss_*_nested            the same figure against the number of filters kept, all K leading counts in one pass
+ *                                  (no counterpart in the reference)
  *
  * The reference-side binding a maintainer would add is shown in INTEGRATION.md.
  */
@@ -580,6 +582,56 @@ int sqfa_gauss_log_loss_backward(const void *Z, const long long *labels, long lo
                                  const double *offset, int C, int K, int dtype, const void *logsumexp,
                                  const void *upstream, void *gradZ_out, void *grad_means_out, void *grad_cov_out,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Nested Gaussian class scores (gauss_nested_kernel.hip): the K classifiers that see only the first k = 1 .. K features,
+ * from one pass.  The leading k x k block of L_c is the Cholesky factor of the leading block of Sigma_c and the first k
+ * entries of y = L_c^-1 (z - mu_c) depend on the first k features only, so
+ *     score_k[n][c] = -1/2 sum_{i<k} y_i^2 + offset_k[c],   offset_k[c] = -sum_{i<k} log (L_c)_ii - k/2 log 2 pi + log pi_c
+ * is a prefix sum over the rows of the y of sqfa_gauss_scores.  Column k - 1 of every (N,K) output belongs to the classifier
+ * on the first k features; column K - 1 is the full classifier (to rounding: the squares are summed in another order than
+ * in sqfa_gauss_scores).  All entries run on the caller's stream, allocate, synchronise and read back nothing and use no
+ * float atomics: every sum is in a fixed order, the results are bitwise reproducible and do not depend on which outputs
+ * are asked for.  Nothing of size (N,C) or (N,C,K) is formed.
+ *
+ * sqfa_gauss_class_factors_nested -- sqfa_gauss_class_factors with offsets_out (C,K) FLOAT64: offsets_out[c][k-1] =
+ *   offset_k[c], the log-pivots accumulated in double in ascending order.  W_out has the bits sqfa_gauss_class_factors
+ *   writes; offsets_out[c][K-1] is its offset to rounding (the same terms, which the compiler is free to contract
+ *   differently in the two kernels).  A bad class gets NaN in W and in all K offsets and counts once.
+ *
+ * sqfa_gauss_scores_nested -- the geometry, LDS stage and MFMA product of sqfa_gauss_scores; the inclusive prefix of y^2
+ *   over the rows is a scan over the lane's accumulator registers, an exclusive scan across the four lane quarters and a
+ *   carry between the 16-row blocks, and every lane carries (max, index) and (max, sum exp) for each of its rows across the
+ *   classes.  Where the classes are split over workgroups a second launch merges the (splits, N, K) partials in split order.
+ *   Z (N,K) dtype; means (C,K) or NULL; W (C,K,K), offsets (C,K) FLOAT64 as written by sqfa_gauss_class_factors_nested
+ *   argmax_out (N,K) int64 or NULL: ties to the lowest class index in every column
+ *   logsumexp_out (N,K) dtype or NULL (at least one of the two is asked for; argmax alone evaluates no exp)
+ *   A sample is flagged when any of its K prefix rows holds a NaN (a zero of W times a non-finite feature is NaN on the
+ *   MFMA, so the early prefixes of such a sample are not kept): all K of its columns are -1 / NaN and it is counted once
+ *   in nonfinite_out (1) int32 (never NULL; the call sets it).
+ *   workspace: sqfa_gauss_scores_nested_workspace_bytes(N, C, K, dtype) bytes (0 = shape or dtype not supported): K times
+ *   that of sqfa_gauss_scores; 16 bytes where the classes are not split.
+ *
+ * sqfa_gauss_label_scores_nested -- the label pass of the log-loss with prefixes: one sample per lane, y = W_y (z - mu_y)
+ *   in double with a running sum of squares, ll_out[n][k-1] = score_k[n][y_n] - logsumexp[n][k-1] (<= 0, 0 with C = 1).
+ *   labels (N) int64, range-checked before anything is addressed with them (an out-of-range label gathers class 0);
+ *   logsumexp (N,K) as written by sqfa_gauss_scores_nested; ll_out (N,K) dtype, NaN in all K columns for a flagged sample
+ *   flags_out (3) int32: [1] labels outside [0, C) and [2] labels whose class has offset -inf are set by the call; [0] is
+ *   left alone: hand flags_out to sqfa_gauss_scores_nested as its nonfinite_out first and the three read as those of
+ *   sqfa_gauss_log_loss.
+ * 1 <= K <= 64, C >= 1, N >= 1.  Return SQFA_ERR_BAD_ARGUMENT (null input or required output, sizes < 1, dtype, no output
+ * asked for), SQFA_ERR_UNSUPPORTED_M (K > 64, or more than 2^31 - 1 sample tiles), SQFA_ERR_WORKSPACE, checked in that
+ * order; every argument check runs before the first HIP call.
+ */
+size_t sqfa_gauss_scores_nested_workspace_bytes(long long N, int C, int K, int dtype);
+int sqfa_gauss_class_factors_nested(const void *means, const void *cov, const double *log_priors, int C, int K, int dtype,
+                                    void *W_out, double *offsets_out, int *bad_out, void *stream);
+int sqfa_gauss_scores_nested(const void *Z, long long N, const void *means, const void *W, const double *offsets, int C,
+                             int K, int dtype, long long *argmax_out, void *logsumexp_out, int *nonfinite_out,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int sqfa_gauss_label_scores_nested(const void *Z, const long long *labels, long long N, const void *means, const void *W,
+                                   const double *offsets, int C, int K, int dtype, const void *logsumexp, void *ll_out,
+                                   int *flags_out, void *stream);
 
 /*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the

@@ -29,6 +29,14 @@ sqfa_gauss_log_loss_backward form nothing of size (N, C) or (C, N, K), and the f
 bad-class count and the three flags together), the backward none.  Elsewhere the torch expression applies, chunked over the
 classes for the forward; with a gradient wanted it holds what autograd holds: the (classes, N, K) whitened differences of
 every chunk.
+
+Nested classifiers (``nested_predict``, ``nested_log_evidence``, ``nested_accuracy``, ``nested_label_log_proba``,
+``nested_log_loss``): column k - 1 of every result belongs to the classifier that sees only the first k features, so one
+call gives accuracy and log-loss against the number of filters kept.  The leading k x k block of L_c is the Cholesky factor
+of the leading block of Sigma_c, and the first k entries of L_c^-1 (z - mu_c) depend on the first k features only: score_k
+is a prefix sum over the squares the full classifier sums anyway, plus a (C, K) table of offsets.  Native under the
+conditions of the class scores (gauss_nested_kernel.hip; switch ``NATIVE_NESTED``) at N C K^2 work, with nothing of size
+(N, C) or (N, C, K) formed; elsewhere a chunked torch expression under ``no_grad``.  Results carry no graph.
 """
 import math
 import time
@@ -44,6 +52,7 @@ __all__ = ["gaussian_class_scores", "GaussianClassifier", "FeatureClassifier"]  
 
 NATIVE_CLASS_SCORES = True
 NATIVE_LOG_LOSS = True
+NATIVE_NESTED = True
 NATIVE_MAX_FEATURES = 64
 # the torch expression's (classes, N, K) temporaries (the differences and the solve's result) stay below this many bytes
 FALLBACK_BYTES = 1 << 28
@@ -350,6 +359,165 @@ class GaussianClassifier:
         """The log-loss -1/N sum_n log p(y_n | z_n), a Python float (one read from the device)."""
         return self._labelled(Z, y)[1]
 
+    # ------------------------------------------------------------------ nested classifiers: the first k features, k = 1 .. K
+    _nested_native = None   # (C, K) float64 offsets of the native path, built by the first nested call
+    _nested_torch = None    # (C, K) offsets of the torch expression, in the dtype
+
+    def _nested_offsets_native(self):
+        """offset_k[c] (C, K) float64 from sqfa_gauss_class_factors_nested, once.  Its W has the bits of the constructor's
+        factor pass, which stays in use; the classes were judged there, so its counter is not read."""
+        if self._nested_native is None:
+            lib = _lib.load()
+            cov, C, K = self.covariances.detach().contiguous(), self.n_classes, self.n_features
+            with _native._on_stream(cov.device) as stream:
+                W = torch.empty_like(cov)
+                offsets = torch.empty((C, K), dtype=torch.float64, device=cov.device)
+                bad = torch.empty(1, dtype=torch.int32, device=cov.device)
+                lp = self.log_priors.contiguous()
+                _lib.check(lib.sqfa_gauss_class_factors_nested(_native._ptr(self._means_native), _native._ptr(cov),
+                                                               _native._ptr(lp), C, K, _native._dtype_code(cov),
+                                                               _native._ptr(W), _native._ptr(offsets), _native._ptr(bad),
+                                                               stream), "sqfa_gauss_class_factors_nested")
+            self._nested_native = offsets
+        return self._nested_native
+
+    def _nested_offsets_torch(self):
+        """offset_k[c] (C, K) in the dtype, once: -sum_{i<k} log (L_c)_ii - k/2 log 2 pi + log pi_c."""
+        if self._nested_torch is None:
+            cov = self.covariances.detach()
+            logdiag = torch.log(torch.diagonal(torch.linalg.cholesky_ex(cov)[0], dim1=-2, dim2=-1)).cumsum(-1)
+            k = torch.arange(1, self.n_features + 1, dtype=cov.dtype, device=cov.device)
+            self._nested_torch = -logdiag - 0.5 * math.log(2.0 * math.pi) * k + self.log_priors.to(cov.dtype)[:, None]
+        return self._nested_torch
+
+    def _use_nested_native(self, Z):
+        return bool(NATIVE_NESTED) and self._use_native(Z)
+
+    def _native_nested_call(self, Z, argmax=False, logsumexp=False, labels=None):
+        """sqfa_gauss_scores_nested and, with labels, sqfa_gauss_label_scores_nested: (argmax (N,K) int64 | None, logsumexp
+        (N,K) | None, ll (N,K) | None, flags (3,) int32 on the device: flagged samples and, with labels, labels outside
+        [0, C) and labels on a class of prior 0)."""
+        lib = _lib.load()
+        Z = Z.detach().contiguous()
+        W, offsets = self._factors[0], self._nested_offsets_native()
+        N, K, C = Z.shape[0], self.n_features, self.n_classes
+        code = _native._dtype_code(Z)
+        logsumexp = logsumexp or labels is not None
+        with _native._on_stream(Z.device) as stream:
+            ws, nbytes = _native._workspace(lib.sqfa_gauss_scores_nested_workspace_bytes, N, C, K, code)
+            out_a = torch.empty((N, K), dtype=torch.int64, device=Z.device) if argmax else None
+            out_l = torch.empty((N, K), dtype=Z.dtype, device=Z.device) if logsumexp else None
+            flags = torch.zeros(3, dtype=torch.int32, device=Z.device)
+            mu = self._means_native
+            _lib.check(lib.sqfa_gauss_scores_nested(_native._ptr(Z), N, _native._ptr(mu), _native._ptr(W),
+                                                    _native._ptr(offsets), C, K, code, _native._ptr(out_a),
+                                                    _native._ptr(out_l), _native._ptr(flags), _native._ptr(ws), nbytes,
+                                                    stream), "sqfa_gauss_scores_nested")
+            ll = None
+            if labels is not None:
+                ll = torch.empty((N, K), dtype=Z.dtype, device=Z.device)
+                _lib.check(lib.sqfa_gauss_label_scores_nested(_native._ptr(Z), _native._ptr(labels), N, _native._ptr(mu),
+                                                              _native._ptr(W), _native._ptr(offsets), C, K, code,
+                                                              _native._ptr(out_l), _native._ptr(ll), _native._ptr(flags),
+                                                              stream), "sqfa_gauss_label_scores_nested")
+        return out_a, out_l, ll, flags
+
+    def _torch_nested(self, Z, argmax=False, logsumexp=False, labels=None):
+        """The same four as a torch expression without a graph: the chunked whitened differences of ``_torch_scores``, the
+        cumulative sum of their squares over the feature axis plus the (C, K) offsets, and a running argmax, log-sum-exp
+        and labelled score across the chunks, so that nothing of size (N, C, K) beyond one chunk is alive.  A sample with
+        a NaN in any prefix is -1 / NaN in all K columns and counted."""
+        with torch.no_grad():
+            if self._torch is None:
+                self._torch_factors()
+            W, offsets = self._torch[0].detach(), self._nested_offsets_torch()
+            Z = Z.detach()
+            means = self.means.detach() if self.means is not None else None
+            N, K, C = Z.shape[0], self.n_features, self.n_classes
+            logsumexp = logsumexp or labels is not None
+            step = max(1, min(C, FALLBACK_BYTES // max(1, 5 * N * K * Z.element_size())))
+            nan = torch.zeros(N, dtype=torch.bool, device=Z.device)
+            best = torch.full((K, N), -math.inf, dtype=Z.dtype, device=Z.device)
+            arg = torch.zeros((K, N), dtype=torch.int64, device=Z.device)
+            lse = torch.full((K, N), -math.inf, dtype=Z.dtype, device=Z.device)
+            labelled = torch.zeros((K, N), dtype=Z.dtype, device=Z.device)
+            inside = prior0 = None
+            if labels is not None:
+                inside = (labels >= 0) & (labels < C)
+                yc = labels.clamp(0, C - 1)
+                prior0 = inside & (self.log_priors[yc] == -math.inf)
+            for c0 in range(0, C, step):
+                Wc = W[c0:c0 + step]
+                y = Wc @ Z.T if means is None else Wc @ (Z[None] - means[c0:c0 + step, None]).transpose(-1, -2)
+                S = -0.5 * (y * y).cumsum(1) + offsets[c0:c0 + step, :, None]                 # (c, K, N)
+                nan |= torch.isnan(S).flatten(0, 1).any(0)
+                if argmax:
+                    top, where = S.max(0)            # the first of equal maxima
+                    better = top > best              # strictly: an earlier chunk keeps a tie
+                    best = torch.where(better, top, best)
+                    arg = torch.where(better, where + c0, arg)
+                if logsumexp:
+                    lse = torch.logaddexp(lse, torch.logsumexp(S, 0))
+                if labels is not None:
+                    mine = yc[None] == torch.arange(c0, c0 + Wc.shape[0], device=Z.device)[:, None]   # (c, N)
+                    labelled = labelled + torch.where(mine[:, None], S, torch.zeros((), dtype=S.dtype, device=S.device)).sum(0)
+            A = torch.where(nan[:, None], -1, arg.T) if argmax else None
+            E = torch.where(nan[:, None], math.nan, lse.T) if logsumexp else None
+            ll = None
+            counts = [nan.sum()]
+            if labels is not None:
+                ll = (labelled.T - E).clamp(max=0.0) if C > 1 else torch.zeros_like(E)
+                ll = torch.where((nan | ~inside | prior0)[:, None], math.nan, ll)
+                counts += [(~inside).sum(), prior0.sum()]
+            else:
+                counts += [torch.zeros_like(counts[0])] * 2
+            return A, E, ll, torch.stack(counts)
+
+    def _nested(self, Z, argmax=False, logsumexp=False, labels=None):
+        """(argmax, logsumexp, ll, the three counts as a device tensor) on whichever path applies."""
+        Z = _samples(Z, self.covariances)
+        if labels is not None:
+            labels = _labels(labels, Z.shape[0], self.device)
+        call = self._native_nested_call if self._use_nested_native(Z) else self._torch_nested
+        return call(Z, argmax=argmax, logsumexp=logsumexp, labels=labels)
+
+    def nested_predict(self, Z):
+        """(N, K) int64: column k - 1 is ``predict`` of the classifier on the first k features; ties to the lowest index
+        in every column."""
+        A, _, _, flags = self._nested(Z, argmax=True)
+        self._refuse(int(flags[0].item()))
+        return A
+
+    def nested_log_evidence(self, Z):
+        """(N, K): column k - 1 is log p(z_n[:k]), the log evidence of the classifier on the first k features."""
+        _, E, _, flags = self._nested(Z, logsumexp=True)
+        self._refuse(int(flags[0].item()))
+        return E
+
+    def nested_accuracy(self, Z, y):
+        """(K,) float64 CPU tensor: the share of samples predicted as y by the classifiers on the first 1 .. K features
+        (one read from the device)."""
+        labels = _labels(y, torch.as_tensor(Z).shape[0], self.device)
+        A, _, _, flags = self._nested(Z, argmax=True)
+        read = torch.cat(((A == labels[:, None]).sum(0), flags[:1].to(torch.int64))).tolist()
+        self._refuse(read[-1])
+        return torch.tensor(read[:-1], dtype=torch.float64) / A.shape[0]
+
+    def nested_label_log_proba(self, Z, y):
+        """(N, K) without a graph: column k - 1 is ``label_log_proba`` of the classifier on the first k features.  The
+        refusals are those of ``label_log_proba``."""
+        _, _, ll, flags = self._nested(Z, labels=y)
+        _refuse_labelled(*flags.tolist(), self.n_classes)
+        return ll
+
+    def nested_log_loss(self, Z, y):
+        """(K,) float64 CPU tensor: the log-loss of the classifiers on the first 1 .. K features, reduced over the samples
+        in float64 (one read from the device, with the three flags)."""
+        _, _, ll, flags = self._nested(Z, labels=y)
+        read = torch.cat((ll.double().sum(0), flags.double())).tolist()
+        _refuse_labelled(*(int(v) for v in read[-3:]), self.n_classes)
+        return -torch.tensor(read[:-3], dtype=torch.float64) / ll.shape[0]
+
 
 def gaussian_class_scores(Z, means, covariances, priors=None):
     """(N, C) scores log p(z_n, c) of the samples Z (N, K) under the class Gaussians: means (C, K) or None (zero means),
@@ -550,3 +718,18 @@ class FeatureClassifier:
 
     def log_loss(self, X, y):
         return self.classifier.log_loss(self.transform(X), y)
+
+    def nested_predict(self, X):
+        return self.classifier.nested_predict(self.transform(X))
+
+    def nested_log_evidence(self, X):
+        return self.classifier.nested_log_evidence(self.transform(X))
+
+    def nested_accuracy(self, X, y):
+        return self.classifier.nested_accuracy(self.transform(X), y)
+
+    def nested_label_log_proba(self, X, y):
+        return self.classifier.nested_label_log_proba(self.transform(X), y)
+
+    def nested_log_loss(self, X, y):
+        return self.classifier.nested_log_loss(self.transform(X), y)

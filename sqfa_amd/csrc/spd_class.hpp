@@ -2,7 +2,7 @@
 // matrix, m <= 64, by ONE 64-thread workgroup (one wave).  The matrix lives in a 64 x SPD_LD array of doubles in LDS that
 // the kernel declares (33 KB); thread r owns row r of the lower triangle.  Every function is called by the whole workgroup
 // and holds its own barriers.  Users: spd_inverse_kernel (spd_class.hip; stage 1 of jeffreys_kernel.hip and stein_kernel.hip)
-// and gauss_factor_kernel (gauss_scores_kernel.hip).
+// and gauss_factor_kernel (gauss_scores_kernel.hip), gauss_nested_factor_kernel (gauss_nested_kernel.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +34,31 @@ template <bool FINITE> __device__ __forceinline__ bool spd_cholesky(double* a, i
     logsum += log(d);
     const double root = sqrt(d), inv = 1.0 / root;
     __syncthreads();
+    if (r == k) a[k * LD + k] = root;
+    if (r > k && r < m) a[r * LD + k] *= inv;
+    __syncthreads();
+    if (r > k && r < m) {
+      const double lrk = a[r * LD + k];
+      for (int c = k + 1; c <= r; ++c) a[r * LD + c] -= lrk * a[c * LD + k];
+    }
+    __syncthreads();
+  }
+  return true;
+}
+
+// spd_cholesky with the running sums of the log-pivots kept: prefix[k] = sum_{i <= k} log(pivot_i) = logdet of the leading
+// (k+1) x (k+1) block of S, accumulated in ascending order, so that prefix[m - 1] has the bits of spd_cholesky's logsum and
+// a has the bits it leaves.  prefix: m doubles in LDS, written by thread 0, readable by all after a true return.
+template <bool FINITE> __device__ __forceinline__ bool spd_cholesky_prefix(double* a, int m, int r, double* prefix) {
+  constexpr int LD = SPD_LD;
+  double logsum = 0.0;
+  for (int k = 0; k < m; ++k) {
+    const double d = a[k * LD + k];   // the same value in every thread: the exit below is uniform
+    if (!(d > 0.0 && (!FINITE || d < (double)INFINITY))) return false;
+    logsum += log(d);
+    const double root = sqrt(d), inv = 1.0 / root;
+    __syncthreads();
+    if (r == 0) prefix[k] = logsum;
     if (r == k) a[k * LD + k] = root;
     if (r > k && r < m) a[r * LD + k] *= inv;
     __syncthreads();

@@ -634,6 +634,50 @@ int sqfa_gauss_label_scores_nested(const void *Z, const long long *labels, long 
                                    int *flags_out, void *stream);
 
 /*
+ * The k best classes of every sample and the rank of its labelled class (gauss_topk_kernel.hip), from the scores of
+ * sqfa_gauss_scores without the (N,C) matrix.  Both rest on one total order of (score, class): higher score first, equal
+ * scores: lower class index first; a -inf score (a class of prior 0) is an ordinary entry that comes after every finite one.
+ * Every score is formed by the statements of sqfa_gauss_scores on the same geometry and has the bits that call writes into
+ * scores_out, so the results are those of a stable descending sort of that matrix.  Both entries run on the caller's stream,
+ * allocate, synchronise and read back nothing, use no float atomics, choose every grid and split from (N, C, K, dtype, k)
+ * alone, are bitwise reproducible and do not depend on which optional outputs are asked for.  Nothing of size (N,C) is formed.
+ *
+ * sqfa_gauss_scores_topk -- the loop of sqfa_gauss_scores with a sorted list of 1, 2, 4 or 8 (the smallest >= k) entries per
+ *   lane in place of (max, index); the lane quarters and, in a second launch, the class splits are joined by list merges.
+ *   Z (N,K) dtype; means (C,K) or NULL; W (C,K,K), offset (C) FLOAT64 as written by sqfa_gauss_class_factors
+ *   index_out (N,k) int64: the k first classes under the order, best first; column 0 is argmax_out of sqfa_gauss_scores
+ *   score_out (N,k) dtype or NULL: their scores, non-increasing
+ *   A sample whose score row holds a NaN gets index -1 and score NaN in all k columns and is counted once in
+ *   nonfinite_out (1) int32 (never NULL; the call sets it).
+ *   workspace: sqfa_gauss_scores_topk_workspace_bytes(N, C, K, dtype, k) bytes: the partial lists, (splits <= 16) x N x list
+ *   size x (a value and an int32); 16 bytes where the classes are not split.
+ *
+ * sqfa_gauss_label_rank -- rank_out[n] = the number of classes c != y_n with s_nc > t_n or (s_nc == t_n and c < y_n), where
+ *   t_n = s_{n, y_n}: 0 where argmax_out of sqfa_gauss_scores is y_n.  A pre-pass forms t_n with the bits of the scores pass
+ *   (one wave takes its 16 samples in turn, stages the labelled class and runs the 16-column product; column j of an MFMA
+ *   product depends on column j of its right operand alone), then the loop of sqfa_gauss_scores counts per lane; quarters and
+ *   class splits are joined by integer sums.
+ *   labels (N) int64, range-checked before anything is addressed with them (an out-of-range label gathers class 0)
+ *   rank_out (N) int64: -1 for a label outside [0, C) and for a sample whose score row holds a NaN
+ *   label_score_out (N) dtype or NULL: t_n, NaN for a label outside [0, C)
+ *   flags_out (2) int32 (the call sets them): samples whose score row holds a NaN, labels outside [0, C)
+ *   workspace: sqfa_gauss_label_rank_workspace_bytes(N, C, K, dtype) bytes: 8 N and, where the classes are split,
+ *   (splits <= 16) x N int32.
+ * 1 <= k <= min(8, C), 1 <= K <= 64, C >= 1, N >= 1.  Return SQFA_ERR_BAD_ARGUMENT (null input or required output, sizes < 1,
+ * dtype, k outside [1, min(8, C)]), SQFA_ERR_UNSUPPORTED_M (K > 64, or more than 2^31 - 1 sample tiles), SQFA_ERR_WORKSPACE,
+ * checked in that order; every argument check runs before the first HIP call.  The workspace queries return 0 for an
+ * unsupported shape, dtype or k.
+ */
+size_t sqfa_gauss_scores_topk_workspace_bytes(long long N, int C, int K, int dtype, int k);
+int sqfa_gauss_scores_topk(const void *Z, long long N, const void *means, const void *W, const double *offset, int C, int K,
+                           int dtype, int k, long long *index_out, void *score_out, int *nonfinite_out, void *workspace,
+                           size_t workspace_bytes, void *stream);
+size_t sqfa_gauss_label_rank_workspace_bytes(long long N, int C, int K, int dtype);
+int sqfa_gauss_label_rank(const void *Z, const long long *labels, long long N, const void *means, const void *W,
+                          const double *offset, int C, int K, int dtype, long long *rank_out, void *label_score_out,
+                          int *flags_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Matrix functions of SPD matrices, f(S) = Q f(Lambda) Q^T per class, and their backward -- spd_log and spd_sqrt of the
  * reference (src/sqfa/linalg.py:165-183, 121-141: torch.linalg.eigh + einsum), as used by log_euclidean[_sq]
  * (src/sqfa/distances.py:92-138).  The eigen-decomposition is one-sided Jacobi, run to convergence, on the Cholesky

@@ -37,6 +37,15 @@ of the leading block of Sigma_c, and the first k entries of L_c^-1 (z - mu_c) de
 is a prefix sum over the squares the full classifier sums anyway, plus a (C, K) table of offsets.  Native under the
 conditions of the class scores (gauss_nested_kernel.hip; switch ``NATIVE_NESTED``) at N C K^2 work, with nothing of size
 (N, C) or (N, C, K) formed; elsewhere a chunked torch expression under ``no_grad``.  Results carry no graph.
+
+Top-k and the label's rank (``predict_topk``, ``label_rank``, ``topk_accuracy``): the k best classes of every sample and
+the number of classes placed before the labelled one, under one total order: higher score first, equal scores: lower class
+index first (a class of prior 0 scores -inf and comes after every finite one).  Native under the conditions of the class
+scores, and k <= 8 for ``predict_topk`` (gauss_topk_kernel.hip; switch ``NATIVE_TOPK``): the scorer's pass with a short
+sorted list, or a counter, per lane in place of (max, index), on scores with the bits of ``scores(Z)``, with nothing of
+size (N, C) formed.  One shape condition, from the measurement in the README: with K > 48 and fewer than 512 classes
+``label_rank`` counts on the native scores, a chunk of samples at a time (the same ranks).  Elsewhere ``_torch_scores`` and a
+stable descending sort, or the count, under ``no_grad``, chunked over the samples.  Results carry no graph.
 """
 import math
 import time
@@ -53,6 +62,12 @@ __all__ = ["gaussian_class_scores", "GaussianClassifier", "FeatureClassifier"]  
 NATIVE_CLASS_SCORES = True
 NATIVE_LOG_LOSS = True
 NATIVE_NESTED = True
+NATIVE_TOPK = True
+NATIVE_TOPK_MAX = 8      # entries of the native top-k list at most
+# label_rank by the rank kernels unless K > RANK_WIDE_FEATURES and C < RANK_WIDE_MIN_CLASSES: there the native scores and the
+# count on them are faster (the label pre-pass stages a 16 KB class image per sample at K = 64; README, the top-k table)
+RANK_WIDE_FEATURES = 48
+RANK_WIDE_MIN_CLASSES = 512
 NATIVE_MAX_FEATURES = 64
 # the torch expression's (classes, N, K) temporaries (the differences and the solve's result) stay below this many bytes
 FALLBACK_BYTES = 1 << 28
@@ -519,6 +534,152 @@ class GaussianClassifier:
         return -torch.tensor(read[:-3], dtype=torch.float64) / ll.shape[0]
 
 
+    # ------------------------------------------------------------------ top-k and the label's rank
+    def _use_topk_native(self, Z):
+        return bool(NATIVE_TOPK) and self._use_native(Z)
+
+    def _sample_chunks(self, N, per_sample):
+        """Ranges of samples whose temporaries of `per_sample` bytes each stay below FALLBACK_BYTES."""
+        step = max(1, min(N, FALLBACK_BYTES // max(1, per_sample)))
+        return [(n0, min(N, n0 + step)) for n0 in range(0, N, step)]
+
+    def _native_topk(self, Z, k, scores):
+        """One sqfa_gauss_scores_topk call: (indices (N,k) int64, scores (N,k) | None, the count of NaN rows (1,) int32)."""
+        lib = _lib.load()
+        Z = Z.detach().contiguous()
+        W, offset = self._factors
+        N, K, C = Z.shape[0], self.n_features, self.n_classes
+        code = _native._dtype_code(Z)
+        with _native._on_stream(Z.device) as stream:
+            ws, nbytes = _native._workspace(lib.sqfa_gauss_scores_topk_workspace_bytes, N, C, K, code, k)
+            index = torch.empty((N, k), dtype=torch.int64, device=Z.device)
+            score = torch.empty((N, k), dtype=Z.dtype, device=Z.device) if scores else None
+            bad = torch.empty(1, dtype=torch.int32, device=Z.device)
+            _lib.check(lib.sqfa_gauss_scores_topk(_native._ptr(Z), N, _native._ptr(self._means_native), _native._ptr(W),
+                                                  _native._ptr(offset), C, K, code, k, _native._ptr(index),
+                                                  _native._ptr(score), _native._ptr(bad), _native._ptr(ws), nbytes, stream),
+                       "sqfa_gauss_scores_topk")
+        return index, score, bad
+
+    def _torch_topk(self, Z, k, scores):
+        """The same three from ``_torch_scores`` and a stable descending sort (equal scores keep their class order;
+        torch.topk does not promise that), a chunk of samples at a time."""
+        with torch.no_grad():
+            Z = Z.detach()
+            N, K, C, esz = Z.shape[0], self.n_features, self.n_classes, Z.element_size()
+            index, score, bad = [], [], torch.zeros((), dtype=torch.int64, device=Z.device)
+            for n0, n1 in self._sample_chunks(N, C * (3 * K * esz + 3 * esz + 16)):
+                S = self._torch_scores(Z[n0:n1]).detach()
+                nan = torch.isnan(S).any(1)
+                top, where = torch.sort(S, dim=1, descending=True, stable=True)
+                index.append(torch.where(nan[:, None], -1, where[:, :k]))
+                if scores:
+                    score.append(torch.where(nan[:, None], math.nan, top[:, :k]))
+                bad = bad + nan.sum()
+            return torch.cat(index), torch.cat(score) if scores else None, bad.reshape(1)
+
+    def predict_topk(self, Z, k, return_scores=False):
+        """(N, k) int64: the k classes of the largest scores, best first, equal scores in the order of their indices, so
+        column 0 is ``predict(Z)``; with ``return_scores`` also their (N, k) scores.  1 <= k <= n_classes (ValueError
+        otherwise); k <= 8 runs natively."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= self.n_classes:
+            raise ValueError(f"k must be an int in [1, {self.n_classes}], got {k!r}")
+        Z = _samples(Z, self.covariances)
+        call = self._native_topk if k <= NATIVE_TOPK_MAX and self._use_topk_native(Z) else self._torch_topk
+        index, score, bad = call(Z, k, return_scores)
+        self._refuse(int(bad.item()))
+        return (index, score) if return_scores else index
+
+    def _native_rank(self, Z, labels):
+        """One sqfa_gauss_label_rank call: (ranks (N,) int64, flags (2,) int32 on the device: samples with a NaN in their
+        score row, labels outside [0, C))."""
+        lib = _lib.load()
+        Z = Z.detach().contiguous()
+        W, offset = self._factors
+        N, K, C = Z.shape[0], self.n_features, self.n_classes
+        code = _native._dtype_code(Z)
+        with _native._on_stream(Z.device) as stream:
+            ws, nbytes = _native._workspace(lib.sqfa_gauss_label_rank_workspace_bytes, N, C, K, code)
+            rank = torch.empty(N, dtype=torch.int64, device=Z.device)
+            flags = torch.empty(2, dtype=torch.int32, device=Z.device)
+            _lib.check(lib.sqfa_gauss_label_rank(_native._ptr(Z), _native._ptr(labels), N, _native._ptr(self._means_native),
+                                                 _native._ptr(W), _native._ptr(offset), C, K, code, _native._ptr(rank), None,
+                                                 _native._ptr(flags), _native._ptr(ws), nbytes, stream),
+                       "sqfa_gauss_label_rank")
+        return rank, flags
+
+    def _torch_rank(self, Z, labels):
+        """The same two as the count ((S > s_y) | ((S == s_y) & (c < y))).sum(1), a chunk of samples at a time."""
+        with torch.no_grad():
+            Z = Z.detach()
+            N, K, C, esz = Z.shape[0], self.n_features, self.n_classes, Z.element_size()
+            inside = (labels >= 0) & (labels < C)
+            yc = labels.clamp(0, C - 1)
+            classes = torch.arange(C, device=Z.device)
+            rank, bad = [], torch.zeros((), dtype=torch.int64, device=Z.device)
+            for n0, n1 in self._sample_chunks(N, C * (3 * K * esz + 2 * esz + 16)):
+                S = self._torch_scores(Z[n0:n1]).detach()
+                y = yc[n0:n1, None]
+                s_y = S.gather(1, y)
+                nan = torch.isnan(S).any(1)
+                count = ((S > s_y) | ((S == s_y) & (classes < y))).sum(1)
+                rank.append(torch.where(nan | ~inside[n0:n1], -1, count))
+                bad = bad + nan.sum()
+            return torch.cat(rank), torch.stack((bad, (~inside).sum()))
+
+    def _scores_rank(self, Z, labels):
+        """The same two from the native scores (sqfa_gauss_scores) and the count on them, a chunk of samples at a time: the
+        same ranks as ``_native_rank``, whose scores have these bits."""
+        N, C = Z.shape[0], self.n_classes
+        inside = (labels >= 0) & (labels < C)
+        yc = labels.clamp(0, C - 1)
+        classes = torch.arange(C, device=Z.device)
+        rank, bad = [], torch.zeros((), dtype=torch.int64, device=Z.device)
+        for n0, n1 in self._sample_chunks(N, C * (Z.element_size() + 16)):
+            S = self._native_call(Z[n0:n1], scores=True)[0]
+            y = yc[n0:n1, None]
+            s_y = S.gather(1, y)
+            nan = torch.isnan(S).any(1)
+            count = ((S > s_y) | ((S == s_y) & (classes < y))).sum(1)
+            rank.append(torch.where(nan | ~inside[n0:n1], -1, count))
+            bad = bad + nan.sum()
+        return torch.cat(rank), torch.stack((bad, (~inside).sum()))
+
+    def _rank(self, Z, y):
+        """(ranks, the two counts as a device tensor) on whichever path applies."""
+        Z = _samples(Z, self.covariances)
+        labels = _labels(y, Z.shape[0], self.device)
+        if not self._use_topk_native(Z):
+            return self._torch_rank(Z, labels)
+        if self.n_features > RANK_WIDE_FEATURES and self.n_classes < RANK_WIDE_MIN_CLASSES:
+            return self._scores_rank(Z, labels)
+        return self._native_rank(Z, labels)
+
+    def label_rank(self, Z, y):
+        """(N,) int64: the number of classes placed before the labelled one (a higher score, or an equal score and a lower
+        index): 0 where ``predict(Z) == y``.  A label on a class of prior 0 is ranked like any other.  ValueError, naming
+        the count, for labels that are not (N,) integers or lie outside [0, C), and for samples with a non-finite score
+        row."""
+        rank, flags = self._rank(Z, y)
+        n_nan, n_outside = flags.tolist()
+        _refuse_labelled(n_nan, n_outside, 0, self.n_classes)
+        return rank
+
+    def topk_accuracy(self, Z, y, k=(1, 5)):
+        """The shares of samples whose labelled class is among the k best, from one ``label_rank`` pass and one read from
+        the device: a (len(k),) float64 CPU tensor, or a Python float for an int ``k``.  Any k >= 1 (k >= n_classes gives
+        1.0)."""
+        ks = list(k) if isinstance(k, (tuple, list)) else [k]
+        if not ks or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in ks):
+            raise ValueError(f"k must be an int >= 1 or a sequence of them, got {k!r}")
+        rank, flags = self._rank(Z, y)
+        below = rank[:, None] < torch.tensor(ks, dtype=torch.int64, device=rank.device)[None]
+        read = torch.cat((below.sum(0), flags.to(torch.int64))).tolist()
+        _refuse_labelled(read[-2], read[-1], 0, self.n_classes)
+        shares = torch.tensor(read[:-2], dtype=torch.float64) / rank.shape[0]
+        return shares[0].item() if isinstance(k, int) else shares
+
+
 def gaussian_class_scores(Z, means, covariances, priors=None):
     """(N, C) scores log p(z_n, c) of the samples Z (N, K) under the class Gaussians: means (C, K) or None (zero means),
     covariances (C, K, K), priors None / "uniform" / (C,) non-negative weights.  Differentiable where an input asks for it
@@ -733,3 +894,12 @@ class FeatureClassifier:
 
     def nested_log_loss(self, X, y):
         return self.classifier.nested_log_loss(self.transform(X), y)
+
+    def predict_topk(self, X, k, return_scores=False):
+        return self.classifier.predict_topk(self.transform(X), k, return_scores)
+
+    def label_rank(self, X, y):
+        return self.classifier.label_rank(self.transform(X), y)
+
+    def topk_accuracy(self, X, y, k=(1, 5)):
+        return self.classifier.topk_accuracy(self.transform(X), y, k)
